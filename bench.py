@@ -3,21 +3,26 @@
 graph of BASELINE.json (configs[3] / SURVEY.md §8(d) "config 4": 1344 images, ~147k tracks, ~5.0M directed edges).
 
 `value` (the bench contract): K steps of the hot path with its inputs resident in HBM - every solve kernel over
-the assembled batch; the output array is fully rewritten by each step.
-Next to it, first class, the reference's own two spans, each over --span-reps one-shot repetitions:
+the assembled batch; the output array is fully rewritten by each step.  A plain run measures only that: it sets up,
+warms up, times the K steps, writes the positions of the last step with --dump-outputs DIR, and prints the line.
+With --full, next to it, first class, the reference's own two spans, each over --span-reps one-shot repetitions:
   solver_span   solve.cc:615-638  problem construction (device assembly of the batch) + solve + results on the host
   total_span    solve.cc:487-641  + tracks / roots / components; the graph starts on the HOST, its PCIe upload is inside
   total_span_resident_graph       the same with the graph already in HBM (streamed-ingest / device-producer contract)
-and the CPU baseline over the same two spans.
+and the CPU baseline over the same two spans, per-kernel times and rooflines, and the two secondary workloads (long tracks,
+cap-sized sparse components).
 
 N > 1: one process per GPU (torch.distributed / RCCL), no data-path collective (components are independent,
 solve.cc:594-597); the statistics vector is all-reduced once for reporting.  The default for N > 1 is --scaling strong
 (BASELINE.json's configuration: ONE 5M-edge graph, seed 2, its components sharded over the ranks on the device - the
-same graph as the N = 1 run, so a scaling curve compares like with like); the line then carries a `weak_scaling`
-object (every rank its OWN 5M-edge graph, seed 2 + rank).  --scaling weak makes that the headline instead and
-carries a `strong_scaling` object.  `python bench.py --gpus N` without a launcher environment starts the N ranks itself.
+same graph as the N = 1 run, so a scaling curve compares like with like); with --full the line then carries a `weak_scaling`
+object (every rank its OWN 5M-edge graph, seed 2 + rank) and the `multi_gpu` self-check.  --scaling weak makes that the
+headline instead and carries a `strong_scaling` object.  `python bench.py --gpus N` without a launcher environment starts
+the N ranks itself.
 
-    python bench.py --gpus 1 --steps 20 --warmup 3
+    python bench.py --gpus 1 --steps 20 --warmup 3                              # the headline only
+    python bench.py --gpus 1 --steps 20 --warmup 3 --dump-outputs DIR           # + DIR/positions.npy of the last timed step
+    python bench.py --gpus 1 --steps 20 --warmup 3 --full                       # + spans, CPU baseline, rooflines, other workloads
 """
 import argparse
 import json
@@ -104,6 +109,31 @@ def self_launch(args):
     os.execv(sys.executable, cmd)
 
 
+def positive_int(s):
+    v = int(s)
+    if v < 1:
+        raise argparse.ArgumentTypeError("must be at least 1")
+    return v
+
+
+WARMUP_MIN_S = 0.5                  # least time the GPU solves before the timed steps start
+DUMP_BUDGET_BYTES = 60_000_000      # all .npy files of one run stay under 64 MB
+
+
+def dump_array(out_dir, name, arr, budget_bytes):
+    """out_dir/<name>.npy; an array above budget_bytes is replaced by a fixed, seeded sample of its rows, whose row
+    numbers go to out_dir/<name>_rows.npy (float64: exact for any row count here)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    if arr.nbytes > budget_bytes:
+        row_bytes = arr.nbytes // arr.shape[0]
+        k = budget_bytes // (row_bytes + 8)
+        rows = np.sort(np.random.Generator(np.random.PCG64(0)).choice(arr.shape[0], size=k, replace=False))
+        np.save(os.path.join(out_dir, name + "_rows.npy"), rows.astype(np.float64))
+        arr = arr[rows]
+    np.save(os.path.join(out_dir, name + ".npy"), arr)
+
+
 def spans(fn, reps, sync):
     """median / min of `reps` one-shot repetitions of fn() (wall clock, device idle before and after)."""
     ts = []
@@ -119,17 +149,22 @@ def spans(fn, reps, sync):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=20)
-    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--steps", type=positive_int, default=20, help="timed steps")
+    ap.add_argument("--warmup", type=int, default=3, help="untimed steps first (then more until the GPU has solved for %.1f s)" % WARMUP_MIN_S)
+    ap.add_argument("--full", action="store_true",
+                    help="measure everything beside the headline: spans, per-kernel times / rooflines, CPU baseline, the long-tracks and "
+                         "sparse workloads, the multi-GPU self-check and the other scaling mode (off: the headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="write the positions the last timed step computed as DIR/positions.npy (float64; DIR/positions_rank<r>.npy for N > 1)")
     ap.add_argument("--tracks", type=int, default=147_000, help="tracks of the synthetic graph (147000 -> ~5.0M edges)")
     ap.add_argument("--scaling", choices=["auto", "weak", "strong"], default="auto",
                     help="auto: strong (ONE config-4 graph sharded over the ranks) when N > 1; N = 1 is the same either way")
-    ap.add_argument("--span-reps", type=int, default=7)
+    ap.add_argument("--span-reps", type=int, default=7, help="one-shot repetitions per span (--full)")
     ap.add_argument("--devices", default="", help="comma-separated HIP device per rank (default: the local rank); with LFR_DIST_BACKEND=gloo "
                                                   "several ranks may share one GPU (tests)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-long-tracks", action="store_true", help="skip the second, workgroup-kernel dominated workload (config 5 stand-in)")
-    ap.add_argument("--no-sparse", action="store_true", help="skip the third workload (cap-sized sparse components, elimination-tree kernel)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-long-tracks", action="store_true", help="--full without the second, workgroup-kernel dominated workload (config 5 stand-in)")
+    ap.add_argument("--no-sparse", action="store_true", help="--full without the third workload (cap-sized sparse components, elimination-tree kernel)")
     ap.add_argument("--sparse-tracks", type=int, default=12000)
     ap.add_argument("--cpu-threads", type=int, default=0)
     args = ap.parse_args()
@@ -209,23 +244,31 @@ def main():
         for _ in range(5):
             sync(); t0 = time.perf_counter(); fn(); ts.append((time.perf_counter() - t0) * 1e3)
         return statistics.median(ts)
-    positions_ms = {"f32": d2h(batch.positions_view_f32), "f64": d2h(batch.positions_view),
-                    "what": "the spans read the results back as float32 (converted on the device: the precision the reference's SolutionFile "
-                            "holds, solve.cc:661-664); f64 = the same read-back in the solver's own precision (until round 5 inside the spans)"}
 
     reps = max(1, args.span_reps)
-    sp_total = spans(total_cold, reps, sync)
-    graph.to_device(local)
-    sp_total_res = spans(total_resident, reps, sync)
-    sp_solver = spans(solver_only, reps, sync)
-    for sp in (sp_total, sp_total_res, sp_solver):   # a span ends when the slowest rank is done
-        sp["ms"] = dist.max_over_ranks(sp["ms"])
-        sp["min_ms"] = dist.max_over_ranks(sp["min_ms"])
+    if args.full:
+        positions_ms = {"f32": d2h(batch.positions_view_f32), "f64": d2h(batch.positions_view),
+                        "what": "the spans read the results back as float32 (converted on the device: the precision the reference's SolutionFile "
+                                "holds, solve.cc:661-664); f64 = the same read-back in the solver's own precision (until round 5 inside the spans)"}
+        sp_total = spans(total_cold, reps, sync)
+        graph.to_device(local)
+        sp_total_res = spans(total_resident, reps, sync)
+        sp_solver = spans(solver_only, reps, sync)
+        for sp in (sp_total, sp_total_res, sp_solver):   # a span ends when the slowest rank is done
+            sp["ms"] = dist.max_over_ranks(sp["ms"])
+            sp["min_ms"] = dist.max_over_ranks(sp["min_ms"])
 
     # ---- the timed steps: every solve kernel over the resident batch ----
+    # warm-up: --warmup steps, then more until the GPU has solved for WARMUP_MIN_S: a few steps alone leave it short of its steady
+    # state (20 timed steps measured ~5 % slow on an MI355X with nothing run before them)
+    t_warm = time.perf_counter()
     for _ in range(args.warmup):
         batch.solve(stream, want_stats=False)
     torch.cuda.synchronize()
+    while time.perf_counter() - t_warm < WARMUP_MIN_S:
+        for _ in range(16):
+            batch.solve(stream, want_stats=False)
+        torch.cuda.synchronize()
     dist.barrier()
     t_start = time.perf_counter()
     for _ in range(args.steps):
@@ -236,18 +279,24 @@ def main():
     elapsed_local = elapsed
     elapsed = dist.max_over_ranks(elapsed)
 
+    # ---- what the last timed step computed: the positions a caller of the solve receives (the solver's float64) ----
+    if args.dump_outputs:
+        dump_array(args.dump_outputs, "positions" if world == 1 else "positions_rank%d" % rank, batch.download(),
+                   DUMP_BUDGET_BYTES // world)
+
     # ---- per-kernel durations of the timed steps (HIP events recorded on the launch stream) ----
-    n_ev = min(args.steps, 64)
-    cls_ms = np.zeros(capi.NUM_KERNEL_CLASSES)
-    tot_ms = 0.0
-    for back in range(n_ev):
-        t, c, cls_edges = batch.timing(back)
-        tot_ms += t
-        cls_ms += c
-    cls_ms /= n_ev
-    tot_ms /= n_ev
+    if args.full:
+        n_ev = min(args.steps, 64)
+        cls_ms = np.zeros(capi.NUM_KERNEL_CLASSES)
+        tot_ms = 0.0
+        for back in range(n_ev):
+            t, c, cls_edges = batch.timing(back)
+            tot_ms += t
+            cls_ms += c
+        cls_ms /= n_ev
+        tot_ms /= n_ev
+        dom = int(np.argmax(cls_ms))
     st = batch.solve(stream, want_stats=True)            # deterministic: same pass counts as every timed step
-    dom = int(np.argmax(cls_ms))
     glob = dist.allreduce_stats(st)
 
     edges_total = glob["n_edges"]
@@ -272,15 +321,20 @@ def main():
                    "edges_per_gpu": st["n_edges"], "tracks_per_gpu": st["n_tracks"], "components_per_gpu": st["n_components"],
                    "parallelism": ("components sharded, %d rank(s), no data-path collective" % world) +
                                   (" (graph stage, assembly and solve per rank over its connected components of the match graph)" if strong and problem.cc_sharded else "")},
-        # the reference's own spans (SURVEY 8(d)), one-shot, median of `reps` (max over ranks)
-        "solver_span": dict(rate(sp_solver), what="solve.cc:615-638: device assembly of the batch (problem construction) + solve + positions on the host (float32)"),
-        "positions_d2h_ms": positions_ms,
-        "total_span": dict(rate(sp_total), what="solve.cc:487-641: graph stage + assembly + solve + positions on the host; the graph starts in "
-                                                "(pinned) host memory, its PCIe upload (%.0f MB) is inside" % (graph.n_edges / 2 * 156e-6)),
-        "total_span_resident_graph": dict(rate(sp_total_res), what="solve.cc:487-641 with the match graph already in HBM (lfr_graph_to_device at ingest / "
-                                                                   "device-producer contract): no PCIe upload inside"),
+        "solve": {"converged": st["n_converged"], "no_convergence": st["n_no_convergence"], "failed": st["n_failed"],
+                  "mean_iterations": st["sum_iterations"] / max(1, st["n_components"])},
     }
-    if rank == 0:
+    if args.full:
+        # the reference's own spans (SURVEY 8(d)), one-shot, median of `reps` (max over ranks)
+        res.update({
+            "solver_span": dict(rate(sp_solver), what="solve.cc:615-638: device assembly of the batch (problem construction) + solve + positions on the host (float32)"),
+            "positions_d2h_ms": positions_ms,
+            "total_span": dict(rate(sp_total), what="solve.cc:487-641: graph stage + assembly + solve + positions on the host; the graph starts in "
+                                                    "(pinned) host memory, its PCIe upload (%.0f MB) is inside" % (graph.n_edges / 2 * 156e-6)),
+            "total_span_resident_graph": dict(rate(sp_total_res), what="solve.cc:487-641 with the match graph already in HBM (lfr_graph_to_device at ingest / "
+                                                                       "device-producer contract): no PCIe upload inside"),
+        })
+    if rank == 0 and args.full:
         serial = os.environ.get("LFR_SERIAL_CLASSES") == "1"
         kernel_names = ["solve_group_kernel<8,1,3>", "solve_group_kernel<16,1,6>", "(retired)",
                         "solve_group_kernel<32,1,6>", "solve_group_kernel<32,2,5>", "solve_block_kernel<lds,rows<=88>",
@@ -327,9 +381,7 @@ def main():
         res["setup_ms"] = {"generate": t_gen * 1e3, "ingest_arrays": t_ingest * 1e3,
                            "graph_stage_kernels": {"tracks": pst["tracks_ms"], "roots": pst["roots_ms"], "components": pst["graph_cut_ms"]},
                            "assembly_incl_flow_wait": st["h2d_ms"]}
-        res["solve"] = {"converged": st["n_converged"], "no_convergence": st["n_no_convergence"], "failed": st["n_failed"],
-                        "mean_iterations": st["sum_iterations"] / max(1, st["n_components"])}
-    if world > 1:
+    if world > 1 and args.full:
         # Self-verification of a multi-GPU line: how many ranks the process group really had (an all-reduced count of
         # ones), which device each rank ran on (name, PCI bus id / uuid where torch exposes them), what each rank solved and how long
         # its K steps took locally - the headline is total edges / the slowest rank's time.
@@ -350,7 +402,7 @@ def main():
             if n1:
                 res["multi_gpu"]["efficiency_vs_n1"] = value / (world * float(n1))
                 res["multi_gpu"]["n1_value"] = float(n1)
-    if world > 1 and not strong:
+    if world > 1 and not strong and args.full:
         # strong scaling beside the weak headline: ONE graph (seed 2), components sharded on the device, Total span
         mas = ma if rank == 0 else synthetic.config4(n_tracks=args.tracks, seed=2)
         gs = graph if rank == 0 else capi.Graph.from_arrays(mas)
@@ -383,7 +435,7 @@ def main():
                                           "predicted_parallel_ms": parallel_ms,
                                           "model": "serial (graph stage + 20 B/match + 4 B/node over PCIe at 57 GB/s, repeated by every rank) + "
                                                    "(one-GPU Solver span + 144 B/match of flows over PCIe) / N"})
-    if world > 1 and strong:
+    if world > 1 and strong and args.full:
         # weak scaling beside the strong headline: every rank its OWN 5M-edge graph (seed 2 + rank), whole batches, the same K steps
         maw = ma if rank == 0 else synthetic.config4(n_tracks=args.tracks, seed=2 + rank)
         gw = graph if rank == 0 else capi.Graph.from_arrays(maw)
@@ -408,7 +460,7 @@ def main():
                                            "HBM-resident batches, max over ranks; linear by construction (no data-path collective)" % args.steps}
         del bw, pw
     if rank == 0:
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             sys.path.insert(0, os.path.join(ROOT, "oracle"))
             import lfr_oracle
             cores = args.cpu_threads or os.cpu_count() or 1
@@ -447,7 +499,7 @@ def main():
             res["speedup_vs_cpu_baseline"] = {"solver_span": ref["solver_ms"] / res["solver_span"]["ms"],
                                               "total_span": (ref["solver_ms"] + ref["graph_ms"]) / res["total_span"]["ms"],
                                               "solver_span_vs_8_threads": runs[min(8, cores)]["solver_ms"] / res["solver_span"]["ms"]}
-        if not args.no_long_tracks and world == 1:
+        if args.full and not args.no_long_tracks and world == 1:
             # config 4 holds only components of <= 32 rows (packed kernel).  Real long-track data (BASELINE
             # configs[4], ETH3D) runs in the workgroup-per-component kernels: a second, clearly labelled workload.
             t0 = time.perf_counter()
@@ -537,7 +589,7 @@ def main():
                 "cpu_baseline": cpu5,
             }
             del b5, p5, g5, ma5
-        if not args.no_sparse and world == 1:
+        if args.full and not args.no_sparse and world == 1:
             # cap-sized SPARSE components - 1344 images, short tracks matched along a ring lattice, chained by wrong
             # matches; the size cap leaves components of up to 1344 nodes (2.7 k-row systems, tree-plus-few-cycles sparse): the
             # elimination-tree kernel of the HBM class (round 2: a dense packed matrix; round 3: a block envelope factored as one chain of panels)
@@ -637,7 +689,7 @@ def main():
             }
             del bs, ps, gs, mas
         ref_bin = os.environ.get("LFR_REFERENCE_SOLVE")
-        if ref_bin and world == 1:
+        if args.full and ref_bin and world == 1:
             # a reference-built `solve`, if someone supplies one, on the same graph as a .pb
             import tempfile
             sys.path.insert(0, os.path.join(ROOT, "scripts"))

@@ -3,7 +3,7 @@
 # usage: scripts/prof_pipeline.sh <tag>     (every step under its own timeout: a faulting run must not eat the lease)
 R=$GRAFT_REPO_ROOT; OUT=$R/gpurun_out/pipe_$1; mkdir -p $OUT
 cd /tmp; export TMPDIR=/tmp
-timeout -k 5 180 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o bench -- python $R/bench.py --steps 5 --warmup 1 --span-reps 5 --no-cpu-baseline > $OUT/bench_under_rocprof.log 2>&1 || { echo "profiled bench failed"; tail -5 $OUT/bench_under_rocprof.log; exit 1; }
+timeout -k 5 180 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o bench -- python $R/bench.py --full --steps 5 --warmup 1 --span-reps 5 --no-cpu-baseline > $OUT/bench_under_rocprof.log 2>&1 || { echo "profiled bench failed"; tail -5 $OUT/bench_under_rocprof.log; exit 1; }
 python - <<PY
 import csv
 rows = list(csv.DictReader(open("$OUT/trace/bench_kernel_stats.csv")))

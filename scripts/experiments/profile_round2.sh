@@ -5,8 +5,8 @@
 # Every step under its own timeout: a faulting run must not eat the lease.
 R=$GRAFT_REPO_ROOT; OUT=$R/gpurun_out/prof_r02; mkdir -p $OUT
 cd /tmp; export TMPDIR=/tmp
-timeout -k 5 240 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o bench -- python $R/bench.py --steps 20 --warmup 3 --no-cpu-baseline > $OUT/bench_under_rocprof.log 2>&1 || echo "kernel-trace pass failed"
-SHORT="python $R/bench.py --steps 5 --warmup 1 --span-reps 1 --no-cpu-baseline --no-long-tracks"
+timeout -k 5 240 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o bench -- python $R/bench.py --full --steps 20 --warmup 3 --no-cpu-baseline > $OUT/bench_under_rocprof.log 2>&1 || echo "kernel-trace pass failed"
+SHORT="python $R/bench.py --full --steps 5 --warmup 1 --span-reps 1 --no-cpu-baseline --no-long-tracks"
 for c in FETCH_SIZE WRITE_SIZE "SQ_WAVE_CYCLES SQ_ACTIVE_INST_VALU SQ_INSTS_VALU" "SQ_WAIT_ANY SQ_INSTS_LDS SQ_LDS_BANK_CONFLICT"; do
     tag=$(echo $c | tr ' ' '_' | cut -c1-40)
     timeout -k 5 200 rocprofv3 --pmc $c --kernel-trace --output-format csv -d $OUT/pmc_$tag -o pmc -- $SHORT > $OUT/pmc_$tag.log 2>&1 || echo "pmc pass $tag failed"

@@ -2,7 +2,7 @@
 # Runs on the GPU box (through gpurun) after scripts/profile_round5.sh + `python scripts/pmc_summarize.py r05`: the un-profiled bench line (its
 # roofline.traffic now comes from PMC summaries of THIS tree), smoke(), the whole GPU suite.
 R=$GRAFT_REPO_ROOT; OUT=$R/gpurun_out/prof_r05; mkdir -p $OUT; cd $R
-timeout -k 5 900 python bench.py --steps 20 --warmup 3 > $OUT/r05_bench_line.json 2> $OUT/r05_bench.err || echo "bench failed"
+timeout -k 5 900 python bench.py --full --steps 20 --warmup 3 > $OUT/r05_bench_line.json 2> $OUT/r05_bench.err || echo "bench failed"
 timeout -k 5 300 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > $OUT/r05_smoke.txt 2>&1 || echo "smoke failed"
 timeout -k 5 1500 python -m pytest tests -m gpu -q 2>&1 | tail -5 > $OUT/r05_gpu_tests.txt
 tail -2 $OUT/r05_smoke.txt; cat $OUT/r05_gpu_tests.txt; python - <<PY

@@ -1,12 +1,13 @@
 #!/bin/bash
-# usage: scripts/pmc.sh <tag> "<counters>"   (run on the GPU box through gpurun; one --pmc pass per call)
+# usage: scripts/pmc.sh <tag> "<counters>"   (on the GPU box; one --pmc pass per call, results under $LFR_PROF_OUT, default prof_out/)
 set -e
+R=$(cd "$(dirname "$0")/.." && pwd); OUT=${LFR_PROF_OUT:-$R/prof_out}; mkdir -p $OUT
 cd /tmp; export TMPDIR=/tmp
 tag=$1; shift
-rocprofv3 --pmc $1 --kernel-trace --output-format csv -d $GRAFT_REPO_ROOT/gpurun_out/pmc_$tag -o pmc -- python $GRAFT_REPO_ROOT/bench.py --steps 3 --warmup 1 --no-cpu-baseline > $GRAFT_REPO_ROOT/gpurun_out/pmc_$tag.log 2>&1 || true
+rocprofv3 --pmc $1 --kernel-trace --output-format csv -d $OUT/pmc_$tag -o pmc -- python $R/bench.py --full --steps 3 --warmup 1 --no-cpu-baseline > $OUT/pmc_$tag.log 2>&1 || true
 python - <<PY
 import csv, collections, glob
-f = glob.glob("$GRAFT_REPO_ROOT/gpurun_out/pmc_$tag/*counter_collection.csv")
+f = glob.glob("$OUT/pmc_$tag/*counter_collection.csv")
 agg = collections.defaultdict(lambda: collections.defaultdict(float)); cnt = collections.Counter()
 for row in csv.DictReader(open(f[0])):
     k = row["Kernel_Name"][:60]

@@ -114,8 +114,8 @@ if pk and "FETCH_SIZE" in pk:
                                            "note": "solve_packed_kernel<true>: 8-byte loads of isolated 72-byte flow rows (FETCH_SIZE not doubled: the correction is for 16 B/lane reads); "
                                                    "a row straddles cache lines, ~2x the bytes it needs - the price of not writing and re-reading 400 MB of records in a one-shot run"}
                                           if pk_gather and "FETCH_SIZE" in pk_gather else None),
-           "source": "round %s: scripts/profile_round%s.sh (rocprofv3 --kernel-trace --stats of python bench.py --steps 20 --warmup 3 --no-cpu-baseline; separate --pmc passes of "
-                     "python bench.py --steps 5 --warmup 1 --span-reps 1 --no-cpu-baseline --no-long-tracks --no-sparse), summarised by scripts/pmc_summarize.py" % (TAG[-1], TAG[-1])}
+           "source": "round %s: scripts/profile_round%s.sh (rocprofv3 --kernel-trace --stats of python bench.py --full --steps 20 --warmup 3 --no-cpu-baseline; separate --pmc passes of "
+                     "python bench.py --full --steps 5 --warmup 1 --span-reps 1 --no-cpu-baseline --no-long-tracks --no-sparse), summarised by scripts/pmc_summarize.py" % (TAG[-1], TAG[-1])}
     json.dump(new, open(os.path.join(prof, "pmc_traffic.json"), "w"), indent=1)
     print("pmc_traffic.json:", {k: new[k] for k in ("hbm_bytes_per_launch", "valu_busy", "rocprof_avg_launch_us")})
 # kernel stats of the bench command: the 60 kernels with the largest total duration

@@ -257,6 +257,36 @@ def test_equal_similarities_keep_the_reference_order(lfr_lib, monkeypatch, road,
             _labels_equal(ma)
 
 
+def test_bench_plain_run_dumps_the_last_step(lfr_lib, tmp_path):
+    """A plain bench.py run prints the headline only (everything else is behind --full), times exactly --steps steps, and
+    --dump-outputs writes the positions the timed path computed: those of the same graph solved here."""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ)
+    for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "LFR_DIST_BACKEND"):
+        env.pop(k, None)
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--tracks", "20000",
+                        "--dump-outputs", str(tmp_path)], capture_output=True, text=True, env=env, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    out = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+    assert out["metric"] == "edges_per_s" and out["unit"] == "edges/s" and out["higher_is_better"] is True and out["dtype"] == "f64"
+    assert out["steps"] == 3 and out["ms_per_step"] > 0 and out["solve"]["failed"] == 0
+    assert abs(out["value"] * out["ms_per_step"] * 1e-3 - out["config"]["edges_per_gpu"]) / out["config"]["edges_per_gpu"] < 1e-6
+    for k in ("solver_span", "total_span", "roofline", "cpu_baseline", "long_tracks_workload", "sparse_capsized_workload"):
+        assert k not in out, k
+    assert sorted(os.listdir(tmp_path)) == ["positions.npy"]
+    got = np.load(tmp_path / "positions.npy")
+    g = capi.Graph.from_arrays(synthetic.config4(n_tracks=20000, seed=2))
+    b = capi.Batch(capi.Problem(g, device_graph_stage=0), 0)
+    b.solve(want_stats=False)
+    want = b.download()
+    assert got.dtype == np.float64 and got.shape == want.shape and np.abs(want).max() > 0
+    np.testing.assert_allclose(got, want, rtol=0, atol=1e-12)
+
+
 @pytest.mark.parametrize("scaling", ["weak", "strong"])
 def test_bench_two_ranks_on_one_gpu(lfr_lib, scaling):
     """bench.py's N>1 path end to end: two ranks (gloo, both on GPU 0) started by bench.py itself; weak = one graph per
@@ -270,7 +300,7 @@ def test_bench_two_ranks_on_one_gpu(lfr_lib, scaling):
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK"):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--devices", "0,0", "--steps", "2", "--warmup", "1",
-                        "--tracks", "20000", "--span-reps", "2", "--no-cpu-baseline", "--scaling", scaling],
+                        "--tracks", "20000", "--span-reps", "2", "--no-cpu-baseline", "--scaling", scaling, "--full"],
                        capture_output=True, text=True, env=env, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     out = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
@@ -304,7 +334,7 @@ def test_bench_four_ranks_on_one_gpu_at_full_size(lfr_lib):
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK"):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "4", "--devices", "0,0,0,0", "--steps", "2", "--warmup", "1",
-                        "--span-reps", "1", "--no-cpu-baseline"], capture_output=True, text=True, env=env, timeout=1200)
+                        "--span-reps", "1", "--no-cpu-baseline", "--full"], capture_output=True, text=True, env=env, timeout=1200)
     assert r.returncode == 0, r.stderr[-3000:]
     out = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
     # the default for N > 1 is STRONG scaling: `value` is ONE config-4 graph whose components are sharded four ways
@@ -331,7 +361,7 @@ def test_bench_two_gpus_over_rccl(lfr_lib):
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "LFR_DIST_BACKEND"):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--tracks", "20000",
-                        "--span-reps", "2", "--no-cpu-baseline"], capture_output=True, text=True, env=env, timeout=900)
+                        "--span-reps", "2", "--no-cpu-baseline", "--full"], capture_output=True, text=True, env=env, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     out = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
     assert out["n_gpus"] == 2 and out["scaling"] == "strong" and out["weak_scaling"]["edges"] > 0
