@@ -317,6 +317,18 @@ int lfr_debug_eval_edges(int device, int64_t n, const float *flows, const float 
  * version of the workgroup-per-component kernel, 2 = the wave-cooperative form of the elimination-tree kernel (the pieces of the
  * root isolation a lane each; one case per wave).  Test infrastructure, not part of the solve path. */
 int lfr_debug_ls_next_step(int device, int64_t n, const double *samples, const double *dir_max, int register_version, double *step);
+/* Unit-level probe of the LM step solves: for each of n_sys systems (A + D) y = g, the solve of one solver kernel on the GPU.  solver
+ * 0-3 = the packed classes' Gauss-Jordan elimination <8,1,3>, <16,1,6>, <32,1,6>, <32,2,5> (n_rows <= 8, 16, 24, 32; 0 = an empty group;
+ * the groups of a wave take consecutive systems - 8, 4, 2, 1 per wave - exactly as the packed kernel places components, so the caller
+ * decides which systems share a wave); 4-6 = the blocked LDL^T and back substitution of the workgroup classes of up to 88, 130, 192 rows
+ * (n_rows >= 2; one workgroup per system, all in one launch, the class's full LDS).  n_rows even.  A: the lower triangles, packed row
+ * by row (element (i, j), j <= i, at i (i + 1) / 2 + j), one system after the other; damp, g, y: n_rows[s] doubles per system.  The
+ * damping goes onto the diagonal as each kernel adds it: a_ii + damp_i (packed: the kernels' dd) or a_ii + damp_i * damp_i with one
+ * rounding (workgroup classes: the kernels' D / s, a fused multiply-add).  y solves (A + D) y = g: the LM step the kernels take is -y.
+ * status[s] = 0 for a valid solve; bit 0: the kernel found a pivot that is not positive (its y is NaN), bit 1: a bounded spin-wait of
+ * the factorization ran out.  Test infrastructure, not part of the solve path. */
+int lfr_debug_solve_damped(int device, int solver, int64_t n_sys, const int32_t *n_rows, const double *A, const double *damp, const double *g,
+                           double *y, int32_t *status);
 /* The library's persistent host workers (they make the elimination-tree plans of a batch, solve.cc:79-143 for components above 192 rows:
  * the reference builds one problem per pool thread, solve.cc:617-635): `items` increments of one counter dealt to `threads` threads, the
  * caller among them, `reps` times.  Returns the number of increments performed (items * reps when nothing was lost).  Callable from

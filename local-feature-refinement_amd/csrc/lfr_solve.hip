@@ -217,6 +217,65 @@ struct alignas(16) GroupLds {
     int ls_prev_flags, ls_iter, n_successful, n_ls_evals, n_cand, exec_passes;
 };
 
+// The LM step of a packed group: (A + dd I) x = rhs0 with A the lower triangle in the group's LDS (rows >= nv2 zero), the padded rows
+// identity.  Builds the lane's columns (LPR*c + part of the own row), eliminates in the GaussJordan instantiation sized for the largest
+// system of the wave (nv2_max, wave-uniform), and returns the step -x of the row (0 in padded rows); fail: a pivot was not positive.
+// `mark` runs after the matrix build (the phase marks of the profiling builds).  Every lane of the wave must be active.
+template <int NV, int LPR, class Mark>
+__device__ __forceinline__ double packed_step(const double *A, const int row, const int part, const bool is_row, const int nv2, const int nv2_max,
+                                              const double dd, const double rhs0, bool &fail, Mark &&mark) {
+    constexpr int CPL = NV / LPR, LD = NV + 1;
+    const double dd_lane = is_row ? dd : 1.0;             // padded rows are identity
+    double rhs = rhs0;
+    double piv_own = 1.0;
+    double minpiv = 1.0;
+    // build the lane's columns (LPR*c + part of the own row) and eliminate, in the instantiation
+    // sized for the largest system of the wave
+    auto lm_solve = [&](auto cl_tag) {
+        constexpr int CL = decltype(cl_tag)::value;
+        double h[CL];
+#pragma unroll
+        for (int c = 0; c < CL; ++c) {
+            const int j = LPR * c + part;
+            if constexpr (NV == 32) {     // (the unconditional form below lets the 24 loads run ahead together: 40-60 spilled VGPRs here)
+                double v = 0.0;
+                if (is_row && j < nv2) v = (j <= row ? A[row * LD + j] : A[j * LD + row]);
+                if (j == row) v = is_row ? v + dd : 1.0;
+                h[c] = v;
+            } else {
+                // rows >= nv2 of A are zero (prologue), so columns beyond the system and padded rows read 0 without a mask
+                const double v = (j <= row ? A[row * LD + j] : A[j * LD + row]);
+                h[c] = (j == row) ? v + dd_lane : v;
+            }
+        }
+        mark();
+        ISA_MARK("gauss_jordan");
+        GaussJordan<NV, LPR, 0, CL>::run(h, rhs, piv_own, minpiv, row, part, nv2_max);
+    };
+    const int c_hi = (nv2_max + LPR - 1) / LPR;          // wave-uniform
+#ifdef LFR_ABL_GJ              // matrix build + elimination twice (the first result discarded through an opaque reset)
+#define LFR_CL(n) do { lm_solve(std::integral_constant<int, n>{}); asm volatile("" : "+v"(rhs), "+v"(piv_own), "+v"(minpiv)); rhs = rhs0; piv_own = 1.0; minpiv = 1.0; lm_solve(std::integral_constant<int, n>{}); } while (0)
+#else
+#define LFR_CL(n) lm_solve(std::integral_constant<int, n>{})
+#endif
+    if constexpr (CPL == 8 && LPR == 1) {             // rows come in pairs: even sizes only
+        if (c_hi <= 2) LFR_CL(2); else if (c_hi <= 4) LFR_CL(4); else if (c_hi <= 6) LFR_CL(6); else LFR_CL(8);
+    } else if constexpr (CPL == 8) {
+        if (c_hi <= 4) LFR_CL(4); else if (c_hi <= 6) LFR_CL(6); else if (c_hi <= 7) LFR_CL(7); else LFR_CL(8);
+    } else if constexpr (CPL == 32) {                  // two <=32-row systems per wave
+        if (c_hi <= 18) LFR_CL(18); else if (c_hi <= 20) LFR_CL(20); else if (c_hi <= 22) LFR_CL(22);
+        else LFR_CL(24);                              // the class holds <= 24 rows (classify())
+    } else if constexpr (LPR == 1) {
+        if (c_hi <= 10) LFR_CL(10); else if (c_hi <= 12) LFR_CL(12); else if (c_hi <= 14) LFR_CL(14); else LFR_CL(16);
+    } else {
+        if (c_hi <= 10) LFR_CL(10); else if (c_hi <= 12) LFR_CL(12); else if (c_hi <= 14) LFR_CL(14); else LFR_CL(16);
+    }
+#undef LFR_CL
+    ISA_MARK("step_reductions");
+    fail = !(minpiv > 0.0);
+    return is_row ? -(rhs * fast_rcp(piv_own)) : 0.0;
+}
+
 #ifndef LFR_GROUP_WAVES
 #define LFR_GROUP_WAVES 2          // waves per SIMD the packed kernel is register-budgeted for
 #endif
@@ -358,57 +417,9 @@ __device__ __forceinline__ void solve_group_body(const KernelArgs &a, const int 
                 // scaled LM diagonal gives the step directly and saves two multiplies and an LDS read per element.
                 // D^2 = diag / radius (Ceres squares sqrt(diag / radius): the same up to two roundings; radius is in [1e-32, 1e16])
                 const double dd = diag * fast_rcp(radius) * (inv_scale * inv_scale);
-                const double dd_lane = is_row ? dd : 1.0;             // padded rows are identity
-                double rhs = is_row ? gi : 0.0;
-                const double rhs0 = rhs;
-                double piv_own = 1.0;
+                const double rhs0 = is_row ? gi : 0.0;
                 bool fail = false;
-                double minpiv = 1.0;
-                // build the lane's columns (LPR*c + part of the own row) and eliminate, in the instantiation
-                // sized for the largest system of the wave
-                auto lm_solve = [&](auto cl_tag) {
-                    constexpr int CL = decltype(cl_tag)::value;
-                    double h[CL];
-#pragma unroll
-                    for (int c = 0; c < CL; ++c) {
-                        const int j = LPR * c + part;
-                        if constexpr (NV == 32) {     // (the unconditional form below lets the 24 loads run ahead together: 40-60 spilled VGPRs here)
-                            double v = 0.0;
-                            if (is_row && j < nv2) v = (j <= row ? A[row * LD + j] : A[j * LD + row]);
-                            if (j == row) v = is_row ? v + dd : 1.0;
-                            h[c] = v;
-                        } else {
-                            // rows >= nv2 of A are zero (prologue), so columns beyond the system and padded rows read 0 without a mask
-                            const double v = (j <= row ? A[row * LD + j] : A[j * LD + row]);
-                            h[c] = (j == row) ? v + dd_lane : v;
-                        }
-                    }
-                    PROF_MARK(5);                     // 5: step setup (diagonal, h build)
-                    ISA_MARK("gauss_jordan");
-                    GaussJordan<NV, LPR, 0, CL>::run(h, rhs, piv_own, minpiv, row, part, nv2_max);
-                };
-                const int c_hi = (nv2_max + LPR - 1) / LPR;          // wave-uniform
-#ifdef LFR_ABL_GJ              // matrix build + elimination twice (the first result discarded through an opaque reset)
-#define LFR_CL(n) do { lm_solve(std::integral_constant<int, n>{}); asm volatile("" : "+v"(rhs), "+v"(piv_own), "+v"(minpiv)); rhs = rhs0; piv_own = 1.0; minpiv = 1.0; lm_solve(std::integral_constant<int, n>{}); } while (0)
-#else
-#define LFR_CL(n) lm_solve(std::integral_constant<int, n>{})
-#endif
-                if constexpr (CPL == 8 && LPR == 1) {             // rows come in pairs: even sizes only
-                    if (c_hi <= 2) LFR_CL(2); else if (c_hi <= 4) LFR_CL(4); else if (c_hi <= 6) LFR_CL(6); else LFR_CL(8);
-                } else if constexpr (CPL == 8) {
-                    if (c_hi <= 4) LFR_CL(4); else if (c_hi <= 6) LFR_CL(6); else if (c_hi <= 7) LFR_CL(7); else LFR_CL(8);
-                } else if constexpr (CPL == 32) {                  // two <=32-row systems per wave
-                    if (c_hi <= 18) LFR_CL(18); else if (c_hi <= 20) LFR_CL(20); else if (c_hi <= 22) LFR_CL(22);
-                    else LFR_CL(24);                              // the class holds <= 24 rows (classify())
-                } else if constexpr (LPR == 1) {
-                    if (c_hi <= 10) LFR_CL(10); else if (c_hi <= 12) LFR_CL(12); else if (c_hi <= 14) LFR_CL(14); else LFR_CL(16);
-                } else {
-                    if (c_hi <= 10) LFR_CL(10); else if (c_hi <= 12) LFR_CL(12); else if (c_hi <= 14) LFR_CL(14); else LFR_CL(16);
-                }
-#undef LFR_CL
-                ISA_MARK("step_reductions");
-                fail = !(minpiv > 0.0);
-                const double step = is_row ? -(rhs * fast_rcp(piv_own)) : 0.0;
+                const double step = packed_step<NV, LPR>(A, row, part, is_row, nv2, nv2_max, dd, rhs0, fail, [&] { PROF_MARK(5); });   // 5: step setup (diagonal, h build)
                 const unsigned long long badmask = __ballot(is_row && !isfinite(step));
                 const unsigned long long gmask = (S == 64) ? ~0ull : ((1ull << (S & 63)) - 1);
                 const bool bad = ((badmask >> ((gid * S) & 63)) & gmask) != 0;
@@ -1149,6 +1160,76 @@ __device__ __forceinline__ void factor_lds(double *Mat, double *vinv, const int 
     FPROF_FLUSH();
 }
 
+// Back substitution of the factored matrix of factor_lds (n <= 192 rows): vstep = row n of Mat holds w = L^-1 g on entry, y with
+// L D L^T y = g on exit; vinv = 1 / d.  ONE wave with the vector in registers (three values per lane); the other waves skip it, the
+// caller synchronises.
+__device__ __forceinline__ void back_substitute_lds(const double *Mat, const double *vinv, double *vstep, const int n, const int tid) {
+    if (tid < 64) {
+        // L D L^T y = g with w = L^-1 g already in row n of the factored matrix (it rode through the factorization): z = w, then
+        // 16-row tile by tile from the last: inside the tile y = M (D^-1 z) - M = (I + D^-1 U^T)^-1 sits where the tile's strictly
+        // lower part was (factor_diag) - a 16 x 16 triangular matrix-vector product whose terms do not depend on one another
+        // (until round 5: 16 steps, each waiting for the one before: y_k = z_k / d_k, z_j -= a_kj y_k); then z_j -= a_kj y_k for
+        // the rows j above the tile (a_kj: the UNSCALED row k, so no per-entry scaling), again independent terms.  Lane = row:
+        // a term is a v_readlane broadcast and one multiply-add per register with a one-instruction address (row base + lane);
+        // the kernel is VALU-issue bound (one instruction per ~4.8 cycles and wave, scripts/probes/diag16_probe.hip).
+        constexpr int kR = 3;
+        double z[kR], inv[kR], yo[kR];
+#pragma unroll
+        for (int r = 0; r < kR; ++r) {
+            const int i = tid + 64 * r;
+            z[r] = i < n ? vstep[i] : 0.0;
+            inv[r] = i < n ? vinv[i] : 0.0;
+            yo[r] = 0.0;
+        }
+        const double *mlane = Mat + tid;                               // + row base (wave-uniform) + 64 r (immediate)
+        auto back_block = [&](auto r0_tag) {
+            constexpr int r0 = decltype(r0_tag)::value;
+            const int lo = 64 * r0;
+            if (lo >= n) return;
+            const int lrow = tid + lo;                                 // the row this lane holds in register r0
+            for (int kb = min(n - 1, lo + 63) & ~15; kb >= lo; kb -= 16) {
+                double m[16][r0 + 1];
+#pragma unroll
+                for (int u = 15; u >= 0; --u) m[u][r0] = (mlane + tri(min(kb + u, n), 0))[64 * r0];     // (rows above n - 1 only pad the last tile)
+#pragma unroll
+                for (int u = 0; u < 16; ++u) {
+                    const double *row = mlane + tri(min(kb + u, n), 0);
+#pragma unroll
+                    for (int r = 0; r < r0; ++r) m[u][r] = row[64 * r];
+                }
+                const double t = z[r0] * inv[r0];
+                const unsigned rel = (unsigned)(lrow - kb);            // 0..15 inside the tile
+                double y0 = t, y1 = 0.0;
+#pragma unroll
+                for (int u = 15; u >= 1; --u) {
+                    if (kb + u < n) {                                  // wave-uniform
+                        const double tc = readlane_f64(t, (kb + u) & 63);
+                        const double mv = rel < (unsigned)u ? m[u][r0] : 0.0;      // M[rel][u]
+                        if (u & 1) y1 = fma(mv, tc, y1); else y0 = fma(mv, tc, y0);
+                    }
+                }
+                const double y = y0 + y1;
+                yo[r0] = rel < 16u ? y : yo[r0];
+                const bool above = lrow < kb;
+#pragma unroll
+                for (int u = 0; u < 16; ++u) {
+                    if (kb + u < n) {                                  // wave-uniform
+                        const double yk = readlane_f64(y, (kb + u) & 63);
+#pragma unroll
+                        for (int r = 0; r < r0; ++r) z[r] = fma(-m[u][r], yk, z[r]);
+                        z[r0] = fma(-(above ? m[u][r0] : 0.0), yk, z[r0]);
+                    }
+                }
+            }
+        };
+        back_block(std::integral_constant<int, 2>{});
+        back_block(std::integral_constant<int, 1>{});
+        back_block(std::integral_constant<int, 0>{});
+#pragma unroll
+        for (int r = 0; r < kR; ++r) if (tid + 64 * r < n) vstep[tid + 64 * r] = yo[r];
+    }
+}
+
 // vectors live in LDS for both variants: 8 vectors of n doubles
 // (two waves per SIMD = 256 registers each, VGPRs + the MFMA accumulators: what the 4 / 2 workgroups per CU of the two smaller
 // LDS classes need; without the attribute the allocator takes 264)
@@ -1570,74 +1651,8 @@ __device__ __forceinline__ void solve_component(const KernelArgs &a, const int m
         PROF_MARK(1);
         bool valid = sh.flag == 0;
         if (valid) {
-            {
-                // Back substitution by ONE wave with the vector in registers (n <= 192: three values per lane).
-                if (tid < 64) {
-                    // L D L^T y = g with w = L^-1 g already in row n of the factored matrix (it rode through the factorization): z = w, then
-                    // 16-row tile by tile from the last: inside the tile y = M (D^-1 z) - M = (I + D^-1 U^T)^-1 sits where the tile's strictly
-                    // lower part was (factor_diag) - a 16 x 16 triangular matrix-vector product whose terms do not depend on one another
-                    // (until round 5: 16 steps, each waiting for the one before: y_k = z_k / d_k, z_j -= a_kj y_k); then z_j -= a_kj y_k for
-                    // the rows j above the tile (a_kj: the UNSCALED row k, so no per-entry scaling), again independent terms.  Lane = row:
-                    // a term is a v_readlane broadcast and one multiply-add per register with a one-instruction address (row base + lane);
-                    // the kernel is VALU-issue bound (one instruction per ~4.8 cycles and wave, scripts/probes/diag16_probe.hip).
-                    constexpr int kR = 3;
-                    double z[kR], inv[kR], yo[kR];
-#pragma unroll
-                    for (int r = 0; r < kR; ++r) {
-                        const int i = tid + 64 * r;
-                        z[r] = i < n ? vstep[i] : 0.0;
-                        inv[r] = i < n ? vinv[i] : 0.0;
-                        yo[r] = 0.0;
-                    }
-                    const double *mlane = Mat + tid;                               // + row base (wave-uniform) + 64 r (immediate)
-                    auto back_block = [&](auto r0_tag) {
-                        constexpr int r0 = decltype(r0_tag)::value;
-                        const int lo = 64 * r0;
-                        if (lo >= n) return;
-                        const int lrow = tid + lo;                                 // the row this lane holds in register r0
-                        for (int kb = min(n - 1, lo + 63) & ~15; kb >= lo; kb -= 16) {
-                            double m[16][r0 + 1];
-#pragma unroll
-                            for (int u = 15; u >= 0; --u) m[u][r0] = (mlane + tri(min(kb + u, n), 0))[64 * r0];     // (rows above n - 1 only pad the last tile)
-#pragma unroll
-                            for (int u = 0; u < 16; ++u) {
-                                const double *row = mlane + tri(min(kb + u, n), 0);
-#pragma unroll
-                                for (int r = 0; r < r0; ++r) m[u][r] = row[64 * r];
-                            }
-                            const double t = z[r0] * inv[r0];
-                            const unsigned rel = (unsigned)(lrow - kb);            // 0..15 inside the tile
-                            double y0 = t, y1 = 0.0;
-#pragma unroll
-                            for (int u = 15; u >= 1; --u) {
-                                if (kb + u < n) {                                  // wave-uniform
-                                    const double tc = readlane_f64(t, (kb + u) & 63);
-                                    const double mv = rel < (unsigned)u ? m[u][r0] : 0.0;      // M[rel][u]
-                                    if (u & 1) y1 = fma(mv, tc, y1); else y0 = fma(mv, tc, y0);
-                                }
-                            }
-                            const double y = y0 + y1;
-                            yo[r0] = rel < 16u ? y : yo[r0];
-                            const bool above = lrow < kb;
-#pragma unroll
-                            for (int u = 0; u < 16; ++u) {
-                                if (kb + u < n) {                                  // wave-uniform
-                                    const double yk = readlane_f64(y, (kb + u) & 63);
-#pragma unroll
-                                    for (int r = 0; r < r0; ++r) z[r] = fma(-m[u][r], yk, z[r]);
-                                    z[r0] = fma(-(above ? m[u][r0] : 0.0), yk, z[r0]);
-                                }
-                            }
-                        }
-                    };
-                    back_block(std::integral_constant<int, 2>{});
-                    back_block(std::integral_constant<int, 1>{});
-                    back_block(std::integral_constant<int, 0>{});
-#pragma unroll
-                    for (int r = 0; r < kR; ++r) if (tid + 64 * r < n) vstep[tid + 64 * r] = yo[r];
-                }
-                __syncthreads();
-            }
+            back_substitute_lds(Mat, vinv, vstep, n, tid);
+            __syncthreads();
         }
         PROF_MARK(6);                                 // 6: triangular solves
         double model_cost_change = 0.0;
@@ -4003,6 +4018,151 @@ int lfr_debug_ls_next_step(int device, int64_t n, const double *samples, const d
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(step, d_a, 8 * (size_t)n, hipMemcpyDeviceToHost, st));
     HIP_TRY(lfr::stream_wait(st));
+    return LFR_OK;
+}
+
+extern "C++" {   // (templates inside the extern "C" block)
+namespace {
+// lfr_debug_solve_damped: the LM step solves of the solver kernels on given systems.  Systems s of n_rows[s] rows: lower triangle at
+// A + tri_off[s] (packed row by row, element (i, j) at i (i + 1) / 2 + j), damping, right-hand side and result at + vec_off[s].
+// Packed classes: the groups of a wave take consecutive systems, exactly as solve_group_body places components.
+template <int NV, int LPR>
+__global__ __launch_bounds__(64) void debug_solve_packed_kernel(int64_t n_sys, const int32_t *n_rows, const int64_t *tri_off, const int64_t *vec_off,
+                                                                const double *A, const double *damp, const double *g, double *y, int32_t *status) {
+    constexpr int S = NV * LPR, G = 64 / S, LD = NV + 1;
+    __shared__ __attribute__((aligned(16))) unsigned char lds_raw[G * sizeof(GroupLds<NV>)];
+    const int lane = threadIdx.x & 63;
+    const int gid = lane / S, sl = lane % S;
+    const int row = sl % NV, part = sl / NV;
+    const int64_t sys = (int64_t)blockIdx.x * G + gid;
+    const bool have = sys < n_sys;
+    const int nv2 = have ? n_rows[sys] : 0;
+    const int64_t to = have ? tri_off[sys] : 0, vo = have ? vec_off[sys] : 0;
+    GroupLds<NV> &L = reinterpret_cast<GroupLds<NV> *>(lds_raw)[gid];
+    for (int i = sl; i < NV * LD; i += S) L.A[i] = 0.0;           // rows >= nv2 zero, as the kernel's prologue leaves them
+    wave_lds_sync();
+    const bool is_row = row < nv2;
+    if (is_row && part == 0)
+        for (int j = 0; j <= row; ++j) L.A[row * LD + j] = A[to + (row * (row + 1)) / 2 + j];
+    int nv2_max = nv2;
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) nv2_max = max(nv2_max, __shfl_xor(nv2_max, m, 64));
+    nv2_max = __builtin_amdgcn_readfirstlane(nv2_max);
+    wave_lds_sync();
+    const double dd = is_row ? damp[vo + row] : 1.0;
+    const double rhs0 = is_row ? g[vo + row] : 0.0;
+    bool fail = false;
+    const double step = packed_step<NV, LPR>(L.A, row, part, is_row, nv2, nv2_max, dd, rhs0, fail, [] {});
+    if (is_row && part == 0) y[vo + row] = fail ? __builtin_nan("") : -step;
+    if (have && sl == 0) status[sys] = fail ? 1 : 0;
+}
+
+// Workgroup classes: one workgroup per system, the dynamic LDS of a class whose largest component has max_rows rows carved as
+// solve_component carves it (what is not the system reads as NaN), then factor_lds and the back substitution.
+template <int kBlockThreads>
+__global__ __launch_bounds__(kBlockThreads) __attribute__((amdgpu_waves_per_eu(kBlockThreads == 256 ? LFR_BLOCK_WPE_256 : 2, kBlockThreads == 256 ? LFR_BLOCK_WPE_256 : 2)))
+void debug_solve_block_kernel(int max_rows, int64_t lds_doubles, const int32_t *n_rows, const int64_t *tri_off, const int64_t *vec_off, const double *A,
+                              const double *damp, const double *g, double *y, int32_t *status, unsigned int *spin_timeouts) {
+    extern __shared__ double dyn[];
+    __shared__ BlockShared sh;
+    const int tid = threadIdx.x;
+    const int64_t sys = blockIdx.x;
+    const int n = n_rows[sys];
+    const double *As = A + tri_off[sys];
+    const int64_t vo = vec_off[sys];
+    double *Mat = dyn + 2 * (size_t)(max_rows + 2) + 7 * (size_t)max_rows;
+    double *vg = dyn + 2 * (size_t)(max_rows + 2);
+    double *vinv = vg + max_rows;     // (vgn)
+    double *vstep = Mat + tri(n, 0);
+    for (int64_t i = tid; i < lds_doubles; i += kBlockThreads) dyn[i] = __builtin_nan("");
+    __syncthreads();
+    for (uint32_t i = tid; i < tri(n, 0); i += kBlockThreads) Mat[i] = As[i];
+    __syncthreads();
+    for (int i = tid; i < n; i += kBlockThreads) {
+        const double di = damp[vo + i];
+        vstep[i] = g[vo + i];
+        Mat[tri(i, i)] += di * di;
+    }
+    __syncthreads();
+    factor_lds<kBlockThreads>(Mat, vinv, n, sh, nullptr, spin_timeouts + sys);
+    __syncthreads();
+    const bool valid = sh.flag == 0;
+    if (valid) {
+        back_substitute_lds(Mat, vinv, vstep, n, tid);
+        __syncthreads();
+    }
+    for (int i = tid; i < n; i += kBlockThreads) y[vo + i] = valid ? vstep[i] : __builtin_nan("");
+    if (tid == 0) status[sys] = valid ? 0 : 1;
+}
+}  // namespace
+}  // extern "C++"
+
+int lfr_debug_solve_damped(int device, int solver, int64_t n_sys, const int32_t *n_rows, const double *A, const double *damp, const double *g,
+                           double *y, int32_t *status) {
+    static const int kLimit[7] = {8, 16, 24, 32, lfr::kBlockRowsS, lfr::kBlockRowsM, lfr::kBlockMaxRows};
+    if (solver < 0 || solver > 6 || n_sys < 0 || n_sys > (1 << 24) || (n_sys > 0 && (!n_rows || !A || !damp || !g || !y || !status))) {
+        lfr::set_error("bad argument"); return LFR_ERR_ARG;
+    }
+    const bool block = solver >= 4;
+    std::vector<int64_t> off(2 * (size_t)n_sys);
+    int64_t n_tri = 0, n_vec = 0;
+    for (int64_t s = 0; s < n_sys; ++s) {
+        const int n = n_rows[s];
+        if (n < (block ? 2 : 0) || n > kLimit[solver] || (n & 1)) { lfr::set_error("n_rows[%lld] = %d: not an even row count the solver takes", (long long)s, n); return LFR_ERR_ARG; }
+        off[s] = n_tri; off[n_sys + s] = n_vec;
+        n_tri += (int64_t)n * (n + 1) / 2; n_vec += n;
+    }
+    lfr::DevCtx *ctx = lfr::dev_ctx(device);
+    if (!ctx) return LFR_ERR_HIP;
+    if (n_sys == 0) return LFR_OK;
+    HIP_TRY(hipSetDevice(device));
+    lfr::DevArena ar;
+    if (!ar.init(ctx, (size_t)n_sys * (4 + 16 + 4 + 4) + (size_t)n_tri * 8 + (size_t)n_vec * 24 + 16 * 256)) return LFR_ERR_NOMEM;
+    int32_t *d_rows = ar.take_n<int32_t>(n_sys), *d_status = ar.take_n<int32_t>(n_sys);
+    int64_t *d_off = ar.take_n<int64_t>(2 * n_sys);
+    double *d_A = ar.take_n<double>(n_tri), *d_damp = ar.take_n<double>(n_vec), *d_g = ar.take_n<double>(n_vec), *d_y = ar.take_n<double>(n_vec);
+    unsigned int *d_spins = ar.take_n<unsigned int>(n_sys);
+    if (!d_spins) { lfr::set_error("arena exhausted"); return LFR_ERR_NOMEM; }
+    hipStream_t st = ctx->s_main;
+    HIP_TRY(hipMemcpyAsync(d_rows, n_rows, 4 * (size_t)n_sys, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(d_off, off.data(), 16 * (size_t)n_sys, hipMemcpyHostToDevice, st));
+    if (n_tri) HIP_TRY(hipMemcpyAsync(d_A, A, 8 * (size_t)n_tri, hipMemcpyHostToDevice, st));
+    if (n_vec) {
+        HIP_TRY(hipMemcpyAsync(d_damp, damp, 8 * (size_t)n_vec, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(d_g, g, 8 * (size_t)n_vec, hipMemcpyHostToDevice, st));
+    }
+    HIP_TRY(hipMemsetAsync(d_spins, 0, 4 * (size_t)n_sys, st));
+    const int64_t *d_to = d_off, *d_vo = d_off + n_sys;
+    if (!block) {
+        static const int kGroups[4] = {8, 4, 2, 1};
+        const dim3 grid((unsigned)((n_sys + kGroups[solver] - 1) / kGroups[solver]));
+        switch (solver) {
+            case 0: hipLaunchKernelGGL((debug_solve_packed_kernel<8, 1>), grid, dim3(64), 0, st, n_sys, d_rows, d_to, d_vo, d_A, d_damp, d_g, d_y, d_status); break;
+            case 1: hipLaunchKernelGGL((debug_solve_packed_kernel<16, 1>), grid, dim3(64), 0, st, n_sys, d_rows, d_to, d_vo, d_A, d_damp, d_g, d_y, d_status); break;
+            case 2: hipLaunchKernelGGL((debug_solve_packed_kernel<32, 1>), grid, dim3(64), 0, st, n_sys, d_rows, d_to, d_vo, d_A, d_damp, d_g, d_y, d_status); break;
+            default: hipLaunchKernelGGL((debug_solve_packed_kernel<32, 2>), grid, dim3(64), 0, st, n_sys, d_rows, d_to, d_vo, d_A, d_damp, d_g, d_y, d_status); break;
+        }
+    } else {
+        const int max_rows = kLimit[solver];
+        const size_t lds = block_lds_bytes(max_rows, false);
+        const void *fn = solver == 4 ? (const void *)debug_solve_block_kernel<kThreadsS> : solver == 5 ? (const void *)debug_solve_block_kernel<kThreadsM>
+                                                                                                       : (const void *)debug_solve_block_kernel<kThreadsL>;
+        HIP_TRY(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        const dim3 grid((unsigned)n_sys);
+        const int64_t ld = (int64_t)(lds / sizeof(double));
+        switch (solver) {
+            case 4: hipLaunchKernelGGL((debug_solve_block_kernel<kThreadsS>), grid, dim3(kThreadsS), lds, st, max_rows, ld, d_rows, d_to, d_vo, d_A, d_damp, d_g, d_y, d_status, d_spins); break;
+            case 5: hipLaunchKernelGGL((debug_solve_block_kernel<kThreadsM>), grid, dim3(kThreadsM), lds, st, max_rows, ld, d_rows, d_to, d_vo, d_A, d_damp, d_g, d_y, d_status, d_spins); break;
+            default: hipLaunchKernelGGL((debug_solve_block_kernel<kThreadsL>), grid, dim3(kThreadsL), lds, st, max_rows, ld, d_rows, d_to, d_vo, d_A, d_damp, d_g, d_y, d_status, d_spins); break;
+        }
+    }
+    HIP_TRY(hipGetLastError());
+    std::vector<unsigned int> spins(block ? (size_t)n_sys : 0);
+    if (n_vec) HIP_TRY(hipMemcpyAsync(y, d_y, 8 * (size_t)n_vec, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(status, d_status, 4 * (size_t)n_sys, hipMemcpyDeviceToHost, st));
+    if (block) HIP_TRY(hipMemcpyAsync(spins.data(), d_spins, 4 * (size_t)n_sys, hipMemcpyDeviceToHost, st));
+    HIP_TRY(lfr::stream_wait(st));
+    for (size_t s = 0; s < spins.size(); ++s) if (spins[s]) status[s] |= 2;
     return LFR_OK;
 }
 

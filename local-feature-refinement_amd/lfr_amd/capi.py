@@ -113,6 +113,7 @@ def lib():
         "lfr_batch_tree_stats": (i64, [vp, vp, vp, vp, vp, vp]),
         "lfr_debug_eval_edges": (C.c_int, [C.c_int, i64, vp, vp, vp, vp, vp, C.c_int, vp, vp]),
         "lfr_debug_ls_next_step": (C.c_int, [C.c_int, i64, vp, vp, C.c_int, vp]),
+        "lfr_debug_solve_damped": (C.c_int, [C.c_int, C.c_int, i64, vp, vp, vp, vp, vp, vp]),
         "lfr_debug_tree_plan": (i64, [i32, i64, vp, vp, i64, vp]),
         "lfr_debug_pool_selftest": (i64, [C.c_int, i64, C.c_int]),
         "lfr_debug_sort_pairs": (C.c_int, [C.c_int, i64, C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp]),
@@ -133,7 +134,7 @@ def lib():
 
 EXPORTS = ["lfr_version", "lfr_last_error", "lfr_graph_from_files", "lfr_graph_from_matches_file", "lfr_graph_from_matches_file_device",
            "lfr_graph_from_arrays", "lfr_graph_from_arrays_device_flows", "lfr_graph_to_device", "lfr_graph_evict_device",
-           "lfr_problem_build_hip_ex", "lfr_problem_build_hip_shard", "lfr_problem_cc_sharded", "lfr_hip_reserve", "lfr_hip_trim", "lfr_batch_positions_view", "lfr_batch_positions_view_f32", "lfr_bisect_graph", "lfr_debug_eval_edges", "lfr_debug_ls_next_step", "lfr_debug_tree_plan", "lfr_debug_pool_selftest", "lfr_debug_sort_pairs", "lfr_debug_exclusive_sum", "lfr_debug_recursive_cut", "lfr_hip_synchronize", "lfr_graph_free", "lfr_graph_num_nodes", "lfr_graph_num_edges",
+           "lfr_problem_build_hip_ex", "lfr_problem_build_hip_shard", "lfr_problem_cc_sharded", "lfr_hip_reserve", "lfr_hip_trim", "lfr_batch_positions_view", "lfr_batch_positions_view_f32", "lfr_bisect_graph", "lfr_debug_eval_edges", "lfr_debug_ls_next_step", "lfr_debug_solve_damped", "lfr_debug_tree_plan", "lfr_debug_pool_selftest", "lfr_debug_sort_pairs", "lfr_debug_exclusive_sum", "lfr_debug_recursive_cut", "lfr_hip_synchronize", "lfr_graph_free", "lfr_graph_num_nodes", "lfr_graph_num_edges",
            "lfr_graph_num_images", "lfr_graph_get_nodes", "lfr_graph_image_name", "lfr_graph_image_fact",
            "lfr_write_matching_file", "lfr_problem_build", "lfr_problem_build_labels", "lfr_problem_build_hip", "lfr_problem_free", "lfr_problem_get_stats",
            "lfr_problem_get_labels", "lfr_problem_shard_components", "lfr_hip_warmup", "lfr_batch_create", "lfr_batch_free", "lfr_batch_solve",
@@ -318,6 +319,27 @@ def ls_next_step_hip(samples, dir_max, register_version=False, device=0):
     a = np.zeros(n, np.float64)
     _check(lib().lfr_debug_ls_next_step(device, n, _ptr(samples), _ptr(dir_max), int(register_version), _ptr(a)))
     return a
+
+
+SOLVERS = {"g8": 0, "g16": 1, "g64_2": 2, "g64_4": 3, "block_s": 4, "block_m": 5, "block_l": 6}
+SOLVER_MAX_ROWS = {"g8": 8, "g16": 16, "g64_2": 24, "g64_4": 32, "block_s": 88, "block_m": 130, "block_l": 192}
+
+
+def solve_damped_hip(solver, n_rows, A, damp, g, device=0):
+    """The kernels' LM step solve (A + D) y = g on the GPU (lfr_debug_solve_damped).  solver: a key of SOLVERS; n_rows[s] per system;
+    A, damp, g: the systems' packed lower triangles and vectors concatenated (see lfr.h).  Returns (y, status): the LM step is -y;
+    status bit 0 = not positive definite (y NaN), bit 1 = a spin-wait of the factorization ran out."""
+    n_rows = np.ascontiguousarray(n_rows, np.int32)
+    A = np.ascontiguousarray(A, np.float64)
+    damp = np.ascontiguousarray(damp, np.float64)
+    g = np.ascontiguousarray(g, np.float64)
+    n_vec = int(n_rows.astype(np.int64).sum())
+    if A.size != int((n_rows.astype(np.int64) * (n_rows + 1) // 2).sum()) or damp.size != n_vec or g.size != n_vec:
+        raise ValueError("A, damp, g do not match n_rows")
+    y = np.zeros(n_vec, np.float64)
+    status = np.zeros(n_rows.size, np.int32)
+    _check(lib().lfr_debug_solve_damped(device, SOLVERS[solver], n_rows.size, _ptr(n_rows), _ptr(A), _ptr(damp), _ptr(g), _ptr(y), _ptr(status)))
+    return y, status
 
 
 def sort_pairs_hip(keys, vals, begin_bit, end_bit, use_library=False, device=0):
