@@ -61,18 +61,17 @@ __global__ void k_mark_kept(int64_t M, const uint32_t *node1, const uint32_t *no
     if (keyed) match_key[e >> 1] = k ? ((uint32_t)cs | (same_track ? 0u : 0x80000000u)) : dropped_key;
 }
 
-// variable = has a kept out-edge and is not its track's root (solve.cc:127,133-141); sizes of the tracks.  node_key (optional): the key
-// of the node sort - component, variables before constants - whose runs are the components' node counts (k_node_runs); without it the
-// counts are taken here, one atomic per node and counter.
+// variable = has a kept out-edge and is not its track's root (solve.cc:127,133-141); sizes of the tracks.  node_key: the key of the node
+// sort - component, variables before constants - whose runs are the components' node counts (k_node_runs)
 __global__ void k_mark_var(int64_t n_nodes, const uint8_t *opt, const uint8_t *is_root, const int32_t *track, const int32_t *comp,
-                           uint8_t *is_var, uint32_t *c_nodes, uint32_t *c_var, uint32_t *t_size, int32_t *t_comp, uint32_t *node_key, uint32_t *node_id) {
+                           uint8_t *is_var, uint32_t *t_size, int32_t *t_comp, uint32_t *node_key, uint32_t *node_id) {
     const int64_t n = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (n >= n_nodes) return;
     const bool v = opt[n] && !is_root[n];
     const int32_t c = comp[n], t = track[n];
     is_var[n] = v;
-    if (node_key) { node_key[n] = ((uint32_t)c << 1) | (v ? 0u : 1u); node_id[n] = (uint32_t)n; }
-    else { atomicAdd(&c_nodes[c], 1u); if (v) atomicAdd(&c_var[c], 1u); }
+    node_key[n] = ((uint32_t)c << 1) | (v ? 0u : 1u);
+    node_id[n] = (uint32_t)n;
     atomicAdd(&t_size[t], 1u);
     t_comp[t] = c;
 }
@@ -153,7 +152,7 @@ __global__ void k_comp_keys(int64_t n_comp, uint32_t *c_nodes, uint32_t *c_var, 
     const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (c < n_tracks && t_size[c] >= 2) atomicAdd(&c_tracks[t_comp[c]], 1u);      // (thread t doubles as track t: k_count_tracks' launch saved)
     if (c >= n_comp) return;
-    if (node_begin) { c_nodes[c] = node_end[c] - node_begin[c]; c_var[c] = node_var_end[c] - node_begin[c]; }      // nodes sorted before the counts (k_node_runs)
+    c_nodes[c] = node_end[c] - node_begin[c]; c_var[c] = node_var_end[c] - node_begin[c];      // nodes sorted before the counts (k_node_runs)
     if (run_begin) c_edges[c] = 2u * (run_end[c] - run_begin[c]);       // matches sorted before the counts (k_match_keys_comp): both directions of every match of the run
     const bool solvable = c_nodes[c] >= 2 && c_var[c] >= 1;   // solve.cc:619-622; no variable: nothing to solve
     if (solvable && c_nodes[c] > 32767) *too_big = 1u;
@@ -188,24 +187,6 @@ __global__ void k_desc_sizes(int64_t n_comp, const uint32_t *perm, uint32_t *cla
     di_of_comp[c] = solvable ? (int32_t)i : -1;
 }
 
-__global__ void k_node_keys(int64_t n_nodes, const int32_t *comp, const int32_t *di_of_comp, const uint8_t *is_var,
-                            uint32_t dropped_key, uint32_t *keys, uint32_t *ids) {
-    const int64_t n = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (n >= n_nodes) return;
-    const int32_t di = di_of_comp[comp[n]];
-    keys[n] = di < 0 ? dropped_key : (((uint32_t)di << 1) | (is_var[n] ? 0u : 1u));     // variables first, then constants
-    ids[n] = (uint32_t)n;
-}
-
-__global__ void k_node_locals(int64_t cap, const uint32_t *total_nodes, const uint32_t *node_sorted, const int32_t *comp, const int32_t *di_of_comp,
-                              const uint32_t *node_off, uint32_t *node_ids, uint32_t *local_of) {
-    const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= cap || p >= (int64_t)*total_nodes) return;
-    const uint32_t n = node_sorted[p];
-    node_ids[p] = n;
-    local_of[n] = (uint32_t)p - node_off[di_of_comp[comp[n]]];
-}
-
 __global__ void k_edge_keys(int64_t n_dir, const uint32_t *node1, const uint32_t *node2, const int32_t *comp,
                             const int32_t *di_of_comp, const uint32_t *class_of_desc, const uint8_t *kept, int node_bits,
                             uint64_t dropped_key, uint64_t *keys, uint32_t *ids) {
@@ -223,44 +204,6 @@ __global__ void k_edge_keys(int64_t n_dir, const uint32_t *node1, const uint32_t
     const uint32_t by_source = class_of_desc[di] >= (uint32_t)KC_BLOCK ? 0xffffffffu : 0u;
     keys[e] = ((uint64_t)(uint32_t)di << node_bits) | (s & by_source);
     ids[e] = (uint32_t)e;
-}
-
-// the same order when no workgroup class is expected: the key is the descriptor index alone - 32 bits, a third less to move per radix pass
-__global__ void k_edge_keys_packed(int64_t n_dir, const uint32_t *node1, const uint32_t *node2, const int32_t *comp, const int32_t *di_of_comp,
-                                   const uint8_t *kept, uint32_t dropped_key, uint32_t *keys, uint32_t *ids) {
-    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= n_dir) return;
-    uint32_t s, d;
-    edge_ends(node1, node2, e, s, d);
-    const int32_t di = kept[e] ? di_of_comp[comp[s]] : -1;
-    keys[e] = di < 0 ? dropped_key : (uint32_t)di;
-    ids[e] = (uint32_t)e;
-}
-
-// Round 5: ... and per MATCH.  The two directions of a match (edge ids 2 m, 2 m + 1) are kept or dropped together and sort next to each other
-// (same component, consecutive ids), so the order of the edges is the order of the matches with every entry doubled: half the keys through
-// the radix passes, and a kernel that writes the pairs out.
-__global__ void k_match_keys_packed(int64_t M, const uint32_t *node1, const int32_t *comp, const int32_t *di_of_comp, const uint8_t *kept,
-                                    uint32_t dropped_key, uint32_t *keys, uint32_t *ids) {
-    const int64_t m = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (m >= M) return;
-    const int32_t di = kept[2 * m] ? di_of_comp[comp[node1[m]]] : -1;
-    keys[m] = di < 0 ? dropped_key : (uint32_t)di;
-    ids[m] = (uint32_t)m;
-}
-// ... and the record words of both directions with it (words != nullptr: the fused gather's k_edge_words, one walk through the match arrays
-// per match instead of one per directed edge)
-__global__ void k_expand_match_order(int64_t M, const uint32_t *total_edges_p, const uint32_t *match_sorted, const uint32_t *node1, const uint32_t *node2,
-                                     const int32_t *track, const uint32_t *local_of, uint32_t *edge_sorted, uint32_t *words) {
-    const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= M) return;
-    const uint32_t m = match_sorted[p];
-    reinterpret_cast<uint2 *>(edge_sorted)[p] = make_uint2(2u * m, 2u * m + 1u);
-    if (words && 2 * p < (int64_t)*total_edges_p) {
-        const uint32_t a = node1[m], b = node2[m];
-        const uint32_t kind = track[a] != track[b] ? 1u : 0u, la = local_of[a], lb = local_of[b];
-        reinterpret_cast<uint2 *>(words)[p] = make_uint2(la | ((lb | (kind << 15)) << 16), lb | ((la | (kind << 15)) << 16));
-    }
 }
 
 // Round 6: the match-level order BEFORE the counts.  k_count_edges' 2.5 M atomics on 147 k counters (config 4) were 0.106 ms of a 0.76 ms
@@ -290,7 +233,7 @@ __global__ void k_match_runs(int64_t M, const uint32_t *keys, uint32_t n_comp, u
     if (i == 0 || keys[i - 1] != k) run_begin[k] = (uint32_t)i;
     if (i + 1 == M || keys[i + 1] != k) run_end[k] = (uint32_t)(i + 1);
 }
-// ... and every match to its place: both directions' edge ids (and record words, k_expand_match_order) at the component's offset
+// ... and every match to its place: both directions' edge ids (and record words, as k_edge_words writes them) at the component's offset
 __global__ void k_place_matches(int64_t M, const uint32_t *keys, const uint32_t *match_sorted, uint32_t n_comp, const int32_t *di_of_comp,
                                 const uint32_t *edge_off, const uint32_t *run_begin, const uint32_t *node1, const uint32_t *node2,
                                 const uint32_t *local_of, uint32_t *edge_sorted, uint32_t *words) {
@@ -659,28 +602,23 @@ int assemble_on_device(const Problem &p, const DevProblem &dp, int shard_rank, i
     TAKE(kept, uint8_t, E2); TAKE(is_var, uint8_t, N); TAKE(tc, int32_t, T + 1);
     TAKE(nk0, uint32_t, N); TAKE(nk1, uint32_t, N); TAKE(ni0, uint32_t, N); TAKE(ni1, uint32_t, N); TAKE(local, uint32_t, N);
     // Packed classes only (the graph stage's largest component says that no workgroup class can exist): the matches go through their
-    // sort now, by component id, and the runs are the edge counts (k_match_keys_comp).  LFR_EDGE_SORT_BY_EDGE / LFR_MATCH_SORT_LATE keep
-    // the older orders for A/B.
+    // sort now, by component id, and the runs are the edge counts (k_match_keys_comp; the later orders: profiles/r06_ab/trace_c4_match_sort_*.txt).
     TAKE(ek0, uint64_t, E2); TAKE(ek1, uint64_t, E2); TAKE(ei0, uint32_t, E2); TAKE(ei1, uint32_t, E2);      // edge keys / ids of the edge order below
     if (fused) ei1 = out.d_edge_ref;                  // the sorted edge ids ARE the packed kernel's gather list
     const bool expect_workgroup_classes = p.stats.max_component_size > 17;
-    const bool match_sort_first = !expect_workgroup_classes && !getenv("LFR_EDGE_SORT_BY_EDGE") && !getenv("LFR_MATCH_SORT_LATE");
+    const bool match_sort_first = !expect_workgroup_classes;
     // The nodes go through THEIR sort before the counts as well - by (component, variables first): the runs are the components' node and
     // variable counts (k_mark_var's two atomics per node on 147 k counters were half of its 54 us), a node's position in its run is its
-    // local index.  LFR_NODE_SORT_LATE keeps the older order (by the component's rank in the batch) for A/B.
-    const bool node_sort_first = !getenv("LFR_NODE_SORT_LATE");
+    // local index (the later sort, by the component's rank in the batch: profiles/r06_ab/trace_c4_nsl.txt).
     uint32_t *mkey_sorted = nullptr, *match_sorted = nullptr;
     // (keys and ids of the M matches: the four quarters of the first 64-bit edge-key buffer)
     uint32_t *mk0 = reinterpret_cast<uint32_t *>(ek0), *mk1 = mk0 + M, *mi0 = mk1 + M, *mi1 = mi0 + M;
     int rc;
     hipLaunchKernelGGL(k_mark_kept, grid_for(E2), dim3(kThreads), 0, st, M, node1, node2, track, comp, kept, opt, (uint32_t)C,
                        match_sort_first ? mk0 : nullptr);
-    hipLaunchKernelGGL(k_mark_var, grid_for(N), dim3(kThreads), 0, st, N, opt, dp.is_root, track, comp, is_var, cn, cv, ts, tc,
-                       node_sort_first ? nk0 : nullptr, ni0);
-    if (node_sort_first) {
-        if ((rc = sort_pairs(arena, nk0, nk1, ni0, ni1, N, 0, std::min(32, nbits((uint64_t)2 * C)), st)) != LFR_OK) return rc;
-        hipLaunchKernelGGL(k_node_runs, grid_for(N), dim3(kThreads), 0, st, N, nk1, node_begin, node_var_end, node_end);
-    }
+    hipLaunchKernelGGL(k_mark_var, grid_for(N), dim3(kThreads), 0, st, N, opt, dp.is_root, track, comp, is_var, ts, tc, nk0, ni0);
+    if ((rc = sort_pairs(arena, nk0, nk1, ni0, ni1, N, 0, std::min(32, nbits((uint64_t)2 * C)), st)) != LFR_OK) return rc;
+    hipLaunchKernelGGL(k_node_runs, grid_for(N), dim3(kThreads), 0, st, N, nk1, node_begin, node_var_end, node_end);
     if (match_sort_first) {
         hipLaunchKernelGGL(k_match_keys_comp, grid_for(M), dim3(kThreads), 0, st, M, node1, node2, is_var, kept, (uint32_t)C, mk0, mi0);
         if ((rc = sort_pairs(arena, mk0, mk1, mi0, mi1, M, 0, comp_bits, st)) != LFR_OK) return rc;
@@ -708,7 +646,7 @@ int assemble_on_device(const Problem &p, const DevProblem &dp, int shard_rank, i
     while (v_bits < 16 && (v_max >> v_bits) != 0u) ++v_bits;
     const int class_shift = e_bits + v_bits;
     hipLaunchKernelGGL(k_comp_keys, grid_for(std::max(C, T)), dim3(kThreads), 0, st, C, cn, cv, ce, match_sort_first ? run_begin : nullptr, run_end,
-                       node_sort_first ? node_begin : nullptr, node_var_end, node_end, key64, id0, &sum->too_big, (uint32_t)block_max_rows(),
+                       node_begin, node_var_end, node_end, key64, id0, &sum->too_big, (uint32_t)block_max_rows(),
                        T, ts, tc, ct, e_max, v_max, e_bits, v_bits);
     if ((rc = sort_pairs(arena, key64, key64s, id0, id1, C, 0, class_shift + kClassBits, st)) != LFR_OK) return rc;
     uint32_t *perm = id1;                  // perm[i] = component of desc i
@@ -724,7 +662,7 @@ int assemble_on_device(const Problem &p, const DevProblem &dp, int shard_rank, i
     hipLaunchKernelGGL(k_desc_sizes, grid_for(C), dim3(kThreads), 0, st, C, perm, class_sorted, shard_world > 1 ? nullptr : key64s, cn, ce, dn, de, di, class_shift);
     LFR_HIP_TRY(exclusive_sum_one_launch(dn, no, C + 1, scan_state + 0 * scan_words, st));
     LFR_HIP_TRY(exclusive_sum_one_launch(de, eo, C + 1, scan_state + 1 * scan_words, st));
-    const uint32_t *total_nodes_p = no + C, *total_edges_p = eo + C;
+    const uint32_t *total_edges_p = eo + C;
 
     // ---- launch geometry + workspace offsets ----
     TAKE(es_size, unsigned long long, C + 1); TAKE(es_scan, unsigned long long, C + 1); TAKE(ws_scan, unsigned long long, C + 1);
@@ -735,40 +673,20 @@ int assemble_on_device(const Problem &p, const DevProblem &dp, int shard_rank, i
     hipLaunchKernelGGL(k_offsets, grid_for(C + 1), dim3(kThreads), 0, st, C, class_sorted, es_scan, ws_scan, no, eo, sum, out.d_es_off, out.d_ws_off);
 
     // ---- local node numbering: nodes by (desc, variable first, node id) ----
-    if (node_sort_first) {
-        hipLaunchKernelGGL(k_place_nodes, grid_for(N), dim3(kThreads), 0, st, N, nk1, ni1, di, no, node_begin, out.d_node_ids, local);
-    } else {
-        hipLaunchKernelGGL(k_node_keys, grid_for(N), dim3(kThreads), 0, st, N, comp, di, is_var, (uint32_t)(2 * C), nk0, ni0);
-        if ((rc = sort_pairs(arena, nk0, nk1, ni0, ni1, N, 0, std::min(32, nbits((uint64_t)2 * C)), st)) != LFR_OK) return rc;
-        hipLaunchKernelGGL(k_node_locals, grid_for(N), dim3(kThreads), 0, st, N, total_nodes_p, ni1, comp, di, no, out.d_node_ids, local);
-    }
+    hipLaunchKernelGGL(k_place_nodes, grid_for(N), dim3(kThreads), 0, st, N, nk1, ni1, di, no, node_begin, out.d_node_ids, local);
 
     // ---- edge order: kept edges by (desc, source node, edge id); packed classes by (desc, edge id) ----
-    // Packed classes carry zeros in the source-node bits (their order is component, then edge id - the sort is stable): when the graph
-    // stage's largest component says that no workgroup class can exist, only the component bits are sorted - three radix passes over the
-    // 5 M keys of config 4 instead of five.  A small component with > 320 edges still lands in a workgroup class: the summary below has
-    // the last word and the full sort is redone then.
-    bool words_done = false;                          // the record words came with the match-level order
+    // Packed classes carry zeros in the source-node bits (their order is component, then edge id - the sort is stable).  When the graph
+    // stage's largest component says that no workgroup class can exist, the match-level order above places every match.  A small
+    // component with > 320 edges still lands in a workgroup class: the summary below has the last word and the full sort is redone then.
+    const bool words_done = match_sort_first && fused;      // the record words came with the match-level order
     if (match_sort_first) {                           // (sorted before the counts: every match to its component's place)
         hipLaunchKernelGGL(k_place_matches, grid_for(M), dim3(kThreads), 0, st, M, mkey_sorted, match_sorted, (uint32_t)C, di, eo, run_begin, node1, node2,
                            local, ei1, fused ? out.d_edge_word : nullptr);
-        words_done = fused;
-    } else if (expect_workgroup_classes) {
+    } else {
         hipLaunchKernelGGL(k_edge_keys, grid_for(E2), dim3(kThreads), 0, st, E2, node1, node2, comp, di, class_sorted, kept, node_bits,
                            (uint64_t)C << node_bits, ek0, ei0);
         if ((rc = sort_pairs(arena, ek0, ek1, ei0, ei1, E2, 0, node_bits + comp_bits, st)) != LFR_OK) return rc;
-    } else if (!getenv("LFR_EDGE_SORT_BY_EDGE")) {    // (32-bit keys in the front halves of the 64-bit key buffers; one key per MATCH: k_match_keys_packed)
-        uint32_t *k32a = reinterpret_cast<uint32_t *>(ek0), *k32b = reinterpret_cast<uint32_t *>(ek1);
-        uint32_t *mi0 = ei0, *mi1 = ei0 + M;
-        hipLaunchKernelGGL(k_match_keys_packed, grid_for(M), dim3(kThreads), 0, st, M, node1, comp, di, kept, (uint32_t)C, k32a, mi0);
-        if ((rc = sort_pairs(arena, k32a, k32b, mi0, mi1, M, 0, comp_bits, st)) != LFR_OK) return rc;
-        hipLaunchKernelGGL(k_expand_match_order, grid_for(M), dim3(kThreads), 0, st, M, total_edges_p, mi1, node1, node2, track, local,
-                           ei1, fused ? out.d_edge_word : nullptr);
-        words_done = fused;
-    } else {                                          // (the same per directed edge: rounds 3-4, kept for A/B)
-        uint32_t *k32a = reinterpret_cast<uint32_t *>(ek0), *k32b = reinterpret_cast<uint32_t *>(ek1);
-        hipLaunchKernelGGL(k_edge_keys_packed, grid_for(E2), dim3(kThreads), 0, st, E2, node1, node2, comp, di, kept, (uint32_t)C, k32a, ei0);
-        if ((rc = sort_pairs(arena, k32a, k32b, ei0, ei1, E2, 0, comp_bits, st)) != LFR_OK) return rc;
     }
     // (both directions of a match are kept or dropped together by construction - k_count_edges - and the sort is stable on the edge
     // id, so the pair check only runs on request or on the path that materialises records)

@@ -439,19 +439,7 @@ __device__ __forceinline__ int32_t par_find(int32_t *parent, int32_t x) {
         x = p;
     }
 }
-// append to a list with one atomic per wave
-__device__ __forceinline__ uint32_t wave_append(bool keep, uint32_t *counter) {
-    const unsigned long long mask = __ballot(keep);
-    const int lane = (int)(threadIdx.x & 63);
-    uint32_t base = 0;
-    if (mask) {
-        const int leader = __ffsll((long long)mask) - 1;
-        if (lane == leader) base = atomicAdd(counter, (uint32_t)__popcll(mask));
-        base = __shfl(base, leader, 64);
-    }
-    return base + (uint32_t)__popcll(mask & ((1ull << lane) - 1ull));
-}
-// ... and with one atomic per WORKGROUP, ITEMS candidates per thread: a returning atomic on one address costs ~10 ns at the L2 whoever
+// append to a list with one atomic per WORKGROUP, ITEMS candidates per thread: a returning atomic on one address costs ~10 ns at the L2 whoever
 // sends it, so a list of millions built wave by wave (83 k atomics for config 5's 5.3 M matches) spent 0.25-1 ms per pass on its counter.
 // Every thread of the (kThreads-wide) workgroup must call it.
 template <int ITEMS>
@@ -533,14 +521,6 @@ __device__ __forceinline__ void round_bid(const Pending q, unsigned long long ro
     if (key < __hip_atomic_load(&minpos[q.ra], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMin(&minpos[q.ra], key);
     if (key < __hip_atomic_load(&minpos[q.rb], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMin(&minpos[q.rb], key);
 }
-__device__ __forceinline__ void round_eval_one(bool valid, Pending q, int32_t *parent, const unsigned long long *bits, int W,
-                                               unsigned long long round_hi, unsigned long long *minpos, Pending *out, uint32_t *n_out) {
-    const bool keep = round_evaluate(valid, q, parent, bits, W);
-    const uint32_t at = wave_append(keep, n_out);
-    if (!keep) return;
-    out[at] = q;
-    round_bid(q, round_hi, minpos);
-}
 constexpr int kEvalItems = 4;
 __global__ void k_round_eval(const uint32_t *n_in_p, const Pending *in, int32_t *parent, const unsigned long long *bits, int W,
                              unsigned long long round_hi, unsigned long long *minpos, Pending *out, uint32_t *n_out) {
@@ -584,136 +564,6 @@ __global__ void k_round_accept(const uint32_t *n_p, const Pending *pend, unsigne
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= *n_p) return;
     round_accept_one(pend[i], round_hi, minpos, parent, count, bits, W, n_accepted);
-}
-
-// Every prefix block and every round of the parallel greedy rule in ONE cooperative launch (opt-in, LFR_ROUNDS_COOPERATIVE=1: see the
-// measurements at its launch site): the phases that are kernels in the default path (first pending list of a block, evaluation,
-// acceptance) are separated by grid-wide barriers instead of launches and read-backs.  c[0], c[1]: entries in list A / list B; c[2]: rounds run; c[3]: matches accepted; c[4]: 1 = the round limit was hit.
-// Grid barrier of k_rounds_all (the launch is cooperative, so every workgroup is resident): one monotonic arrival counter per
-// eighth of the grid (one cache line each) and a release word; the last arrival of the last group releases.  Agent-scope fences on both
-// sides: the XCDs' L2 caches are not coherent with each other inside a kernel.  (cooperative_groups' grid.sync() took ~130 us per
-// barrier here - 20 ms for config 5's 76 rounds against 4.4 ms for launch-per-round.)
-__device__ __forceinline__ void rounds_barrier(uint32_t *bar, uint32_t &gen) {
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        ++gen;
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-        const uint32_t grp = blockIdx.x & 7u, in_grp = (gridDim.x - grp + 7u) >> 3;
-        if (__hip_atomic_fetch_add(&bar[16 * (1 + grp)], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + 1u == gen * in_grp) {
-            const uint32_t groups = gridDim.x < 8u ? gridDim.x : 8u;
-            if (__hip_atomic_fetch_add(&bar[16 * 9], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + 1u == gen * groups)
-                __hip_atomic_store(&bar[0], gen, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-        while (__hip_atomic_load(&bar[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < gen) __builtin_amdgcn_s_sleep(2);
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-    }
-    __syncthreads();
-}
-#ifndef LFR_ROUNDS_TAIL_PENDING
-#define LFR_ROUNDS_TAIL_PENDING 0
-#endif
-#ifndef LFR_ROUNDS_TAIL_WGS
-#define LFR_ROUNDS_TAIL_WGS 4
-#endif
-struct RoundsArgs {
-    int64_t M, first_block, serial_limit;
-    const uint32_t *flags, *seg_id, *starts, *order, *n1, *n2;
-    const int32_t *node_image;
-    int W, max_rounds;
-    unsigned long long *bits, *minpos;
-    Pending *pa, *pb;
-    int32_t *parent, *count;
-    uint32_t *c;
-    uint32_t *bar;           // 160 zeroed words
-    int resume, launched0;   // resume = 1: the rounds of ONE prefix block whose pending list (pa, c[0] entries) exists already; launched0 rounds have run
-};
-// Round 5: the same loop on ONE XCD (k_rounds_all<true>, a plain launch).  A round of the greedy rule is a chain of dependent accesses to
-// words everybody shares (parents, bids, image sets); through agent-scope fences every hop leaves the XCD (~2 us) and a barrier writes the
-// whole L2 back, and as separate launches a round costs two kernel boundaries (~43 us for a few thousand pending matches: 76 rounds = 3.3
-// ms of config 5's graph stage).  The workgroups that land on one XCD share its L2: the barrier there is an arrival counter, `s_waitcnt
-// vmcnt(0)` before it (every store has reached L2) and an L1 invalidate behind it - no write-back, nothing leaves the XCD.  The launch
-// is eight times the workgroups that are wanted; every workgroup registers, the ones on other XCDs than the first registrant's leave, the
-// others learn their number and their count when the whole grid has registered.  bar[150]: chosen XCC + 1, [151]: participants,
-// [152]: registered, [153]: arrivals.
-__device__ __forceinline__ void rounds_barrier_xcd(uint32_t *bar, uint32_t &gen, const uint32_t n_blk) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        ++gen;
-        __hip_atomic_fetch_add(&bar[153], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        for (int spins = 0; (int)(__hip_atomic_load(&bar[153], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) - gen * n_blk) < 0 && spins < (1 << 24); ++spins) __builtin_amdgcn_s_sleep(1);   // (bounded: a miscount ends as garbage labels the tests catch, not as a hung GPU)
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");        // (buffer_inv sc1: this CU's L1; the L2 is the XCD's own)
-    }
-    __syncthreads();
-}
-template <bool XCD>
-__global__ void __launch_bounds__(kPipeThreads) k_rounds_all(RoundsArgs a) {
-    uint32_t gen = 0;
-    uint32_t n_blk = gridDim.x, blk = blockIdx.x;
-    if (XCD) {
-        __shared__ uint32_t s_reg[2];
-        if (threadIdx.x == 0) {
-            const uint32_t xcc = (__builtin_amdgcn_s_getreg((20 << 0) | (0 << 6) | (3 << 11)) & 7u) + 1u;
-            uint32_t chosen = atomicCAS(&a.bar[150], 0u, xcc);
-            if (chosen == 0u) chosen = xcc;
-            uint32_t idx = 0xffffffffu;
-            if (chosen == xcc) idx = __hip_atomic_fetch_add(&a.bar[151], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // (the participant count is out before the total says "everyone has registered")
-            __hip_atomic_fetch_add(&a.bar[152], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (idx != 0xffffffffu) for (int spins = 0; __hip_atomic_load(&a.bar[152], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < gridDim.x && spins < (1 << 24); ++spins) __builtin_amdgcn_s_sleep(4);
-            s_reg[0] = idx; s_reg[1] = __hip_atomic_load(&a.bar[151], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-        __syncthreads();
-        blk = s_reg[0]; n_blk = s_reg[1];
-        if (blk == 0xffffffffu) return;
-    }
-    auto barrier = [&]() { if (XCD) rounds_barrier_xcd(a.bar, gen, n_blk); else rounds_barrier(a.bar, gen); };
-    const uint32_t n_thr = n_blk * blockDim.x, tid = blk * blockDim.x + threadIdx.x, lane = threadIdx.x & 63u;
-    Pending *pa = a.pa, *pb = a.pb;
-    int cur = 0;                                                  // c[cur] counts pa; both counters are 0 between blocks
-    int launched = a.launched0;
-    for (int64_t k_lo = 0, size = a.first_block; k_lo < a.M; k_lo += size, size *= 2) {
-        const int64_t k_hi = k_lo + size < a.M ? k_lo + size : a.M;
-        for (int64_t b = k_lo + (tid - lane); !a.resume && b < k_hi; b += n_thr) {          // (wave-uniform trip count: wave_append is a wave operation)
-            const int64_t k = b + lane;
-            bool large = false;
-            uint32_t m = 0;
-            if (k < k_hi) {
-                const uint32_t sg = a.seg_id[k] + a.flags[k] - 1u;
-                large = (int64_t)(a.starts[sg + 1] - a.starts[sg]) > a.serial_limit;
-                m = a.order[k];
-            }
-            const uint32_t at = wave_append(large, &a.c[cur]);
-            if (large) {
-                const uint32_t x = a.n1[m], y = a.n2[m];
-                pa[at] = Pending{(uint32_t)k, (int32_t)x, (int32_t)y};
-                atomicOr(&a.bits[(size_t)x * a.W + (a.node_image[x] >> 6)], 1ull << (a.node_image[x] & 63));
-                atomicOr(&a.bits[(size_t)y * a.W + (a.node_image[y] >> 6)], 1ull << (a.node_image[y] & 63));
-            }
-        }
-        barrier();
-        for (;;) {
-            const uint32_t n_in = __hip_atomic_load(&a.c[cur], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (n_in == 0) break;
-            if (launched >= a.max_rounds) { if (tid == 0) a.c[4] = 1u; return; }        // (uniform: every thread read the same count)
-            const unsigned long long round_hi = (unsigned long long)(kMaxRounds - launched) << 32;
-            for (uint32_t b = tid - lane; b < n_in; b += n_thr) {
-                const uint32_t i = b + lane;
-                const bool valid = i < n_in;
-                round_eval_one(valid, valid ? pa[i] : Pending{0, 0, 0}, a.parent, a.bits, a.W, round_hi, a.minpos, pb, &a.c[cur ^ 1]);
-            }
-            barrier();
-            const uint32_t n_out = __hip_atomic_load(&a.c[cur ^ 1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            for (uint32_t i = tid; i < n_out; i += n_thr) round_accept_one(pb[i], round_hi, a.minpos, a.parent, a.count, a.bits, a.W, &a.c[3]);
-            if (tid == 0) a.c[cur] = 0u;                          // (everybody read n_in before the barrier above)
-            barrier();
-            Pending *t = pa; pa = pb; pb = t;
-            cur ^= 1;
-            ++launched;
-        }
-        if (a.resume) break;                                      // (one block: the host has the next one's pending list made by the whole chip)
-    }
-    if (tid == 0) a.c[2] = (uint32_t)launched;
 }
 
 // ---- size cap (solve.cc:311-364): the cut itself runs on the host, on the handful of inter-track matches it needs ----
@@ -1100,19 +950,6 @@ int warm_graphstage_primitives(DevCtx *ctx) {
         if ((rc = sort_pairs(arena, k64a, k64b, v32a, v32b, n, 0, 52, st)) != LFR_OK) return rc;
         if ((rc = exclusive_sum(arena, v32a, v32b, n, st)) != LFR_OK) return rc;
     }
-    // the two opt-in forms of the union-find rounds (the default is one launch per round and needs no warm-up of its own): an empty list each
-    const char *e_coop = getenv("LFR_ROUNDS_COOPERATIVE"), *e_xcd = getenv("LFR_ROUNDS_XCD");
-    const bool coop = e_coop && e_coop[0] == '1', xcd = e_xcd && e_xcd[0] == '1' && !coop;
-    if (coop || xcd) {
-        uint32_t *c = arena.take_n<uint32_t>(16 + 160);
-        if (c) {
-            LFR_HIP_TRY(hipMemsetAsync(c, 0, 4 * (16 + 160), st));
-            RoundsArgs ra{0, 1024, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 1, kMaxRounds, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, c, c + 16, 0, 0};
-            void *kargs[1] = {&ra};
-            if (coop) { if (hipLaunchCooperativeKernel((const void *)k_rounds_all<false>, dim3(256), dim3(kThreads), kargs, 0, st) != hipSuccess) (void)hipGetLastError(); }
-            else hipLaunchKernelGGL(k_rounds_all<true>, dim3(64), dim3(kThreads), 0, st, ra);      // (LFR_ROUNDS_XCD=1: the rounds on one XCD - measured slower, not the default)
-        }
-    }
     LFR_HIP_TRY(stream_wait(st));
     return rc;
 }
@@ -1358,8 +1195,8 @@ int graph_stage_on_device(const Graph &g, int64_t max_nodes, int device, bool st
     hipLaunchKernelGGL(k_init_nodes, grid_for(N), dim3(kThreads), 0, st, N, dg->node_image, par, next, tail, cnt, sig);
     int64_t serial_limit = kSerialSegmentEdges;
     if (const char *e = getenv("LFR_SERIAL_SEGMENT_EDGES")) serial_limit = std::max<int64_t>(0, atoll(e));
-    // (counting road: the matches as a stream of sorted records - k_kruskal_stream; LFR_KRUSKAL_GLOBAL=1: the gathering kernel, A/B and tests)
-    const bool streamed = counts_on_host && order_done && !getenv("LFR_KRUSKAL_GLOBAL");
+    // (counting road: the matches as a stream of sorted records - k_kruskal_stream)
+    const bool streamed = counts_on_host && order_done;
     if (streamed)
         hipLaunchKernelGGL(k_kruskal_stream, grid_for(seg_cap), dim3(kThreads), 0, st, seg_cap, serial_limit, counts, starts, srec, dg->node_image, par, next, tail, cnt, sig);
     else
@@ -1412,62 +1249,7 @@ int graph_stage_on_device(const Graph &g, int64_t max_nodes, int device, bool st
         int64_t first_block = std::max<int64_t>(2 * N, 1024);
         if (const char *e = getenv("LFR_ROUNDS_FIRST_BLOCK")) first_block = std::max<int64_t>(1, atoll(e));
         int64_t rounds = 0;
-        // LFR_ROUNDS_COOPERATIVE=1: one cooperative launch runs every prefix block and every round (k_rounds_all, grid barriers instead
-        // of launches).  Measured on config 5 (76 rounds, profiles/r03_rounds_cooperative.txt): 4.4 ms with one workgroup per CU, 5.8 / 8.0
-        // with two / four, against 4.3 ms for the launch-per-round loop below - a barrier needs the same agent-scope write-back and
-        // invalidate of the eight L2s as a kernel boundary and costs ~28 us; with cooperative_groups' grid.sync() ~130 us (20 ms).  So
-        // the loop stays the default and this path is kept as the measured alternative.
-        bool done = false;
-        // Round 5, opt-in (LFR_ROUNDS_XCD=1), measured and NOT the default: the first round of a prefix block - every match of the block -
-        // on the whole chip, the block's remaining rounds - a few thousand pending matches each, dozens of rounds - in ONE launch on ONE
-        // XCD (k_rounds_all<true>): three L2-local barriers per round instead of two kernel boundaries.  Config 5's graph stage: 14.4-15.3
-        // ms against 10.9-12.6 for the launch-per-round loop (and 16.4-17.8 with every round on one XCD, the big first rounds included):
-        // 128 workgroups meeting at one L2 word three times per round, and an eighth of the chip's issue slots for the evaluation, cost
-        // more than the kernel boundaries they replace.
-        bool xcd_tail = false;
-        { const char *hx = getenv("LFR_ROUNDS_XCD"); if (hx && hx[0] == '1' && !(getenv("LFR_ROUNDS_COOPERATIVE") && getenv("LFR_ROUNDS_COOPERATIVE")[0] == '1')) xcd_tail = true; }
-        // Round 6: the one-XCD loop for SHORT lists only.  Below a few thousand pending matches a round is two kernel
-        // boundaries around a chain of ~10 dependent accesses (~26 us whatever the count, 40 of config 5's 76 rounds), and a batch of
-        // eight rounds is launched whole even when the list empties in its second; a handful of workgroups on one XCD then runs the
-        // rest of the block's rounds in ONE launch (L2-local barriers, no read-back in between).  LFR_ROUNDS_TAIL="pending,workgroups"
-        // (0 = off): the list length below which the block is finished that way, and how many workgroups take part.
-        const std::pair<uint32_t, int> tail_cfg = [] {
-            unsigned t = LFR_ROUNDS_TAIL_PENDING, w = LFR_ROUNDS_TAIL_WGS;
-            if (const char *e = getenv("LFR_ROUNDS_TAIL")) { unsigned a = 0, b = 0; const int got = sscanf(e, "%u,%u", &a, &b); if (got >= 1) t = a; if (got >= 2 && b >= 1 && b <= 32) w = b; }
-            return std::make_pair((uint32_t)t, (int)w);
-        }();
-        uint32_t *xbar = rounds_arena.take_n<uint32_t>(160);
-        if (!xbar) { set_error("graph stage: rounds arena exhausted"); return LFR_ERR_NOMEM; }
-        const char *hl = getenv("LFR_ROUNDS_COOPERATIVE");
-        if (hl && hl[0] == '1') {
-            static int blocks_per_cu = -1, n_cu = 0;
-            if (blocks_per_cu < 0) {
-                int nb = 0;
-                hipDeviceProp_t prop;
-                if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_rounds_all<false>, kThreads, 0) == hipSuccess && nb > 0 &&
-                    hipGetDeviceProperties(&prop, device) == hipSuccess && prop.cooperativeLaunch) { const char *eb = getenv("LFR_ROUNDS_BLOCKS_PER_CU"); blocks_per_cu = std::max(1, std::min(nb, eb ? atoi(eb) : 1)); n_cu = prop.multiProcessorCount; }
-                else blocks_per_cu = 0;
-            }
-            if (blocks_per_cu > 0) {
-                uint32_t *bar = rounds_arena.take_n<uint32_t>(160);
-                if (!bar) { set_error("graph stage: rounds arena exhausted"); return LFR_ERR_NOMEM; }
-                LFR_HIP_TRY(hipMemsetAsync(bar, 0, 4 * 160, st));
-                RoundsArgs ra{M, first_block, serial_limit, flags, segid, starts, order, n1, n2, dg->node_image, W, kMaxRounds, bits, minpos, pa, pb, par, cnt, ctr + 8, bar, 0, 0};
-                void *kargs[1] = {&ra};
-                const hipError_t e = hipLaunchCooperativeKernel((const void *)k_rounds_all<false>, dim3((unsigned)(blocks_per_cu * n_cu)), dim3(kThreads), kargs, 0, st);
-                if (e == hipSuccess) {
-                    LFR_HIP_TRY(hipMemcpyAsync(h_ctr, ctr + 8, 4 * 5, hipMemcpyDeviceToHost, st));
-                    LFR_HIP_TRY(stream_wait(st));
-                    if (h_ctr[4]) return use_host("a path-shaped dependency chain");                      // a path-shaped dependency chain: sequential anyway
-                    rounds = h_ctr[2];
-                    if (trace > 2) fprintf(stderr, "lfr graph stage:   %u rounds in one cooperative launch, %u matches accepted\n", h_ctr[2], h_ctr[3]);
-                    done = true;
-                } else {
-                    (void)hipGetLastError();
-                    blocks_per_cu = 0;
-                }
-            }
-        }
+        // (one launch per round: grid-barrier and one-XCD forms measured slower - profiles/r03_rounds_cooperative.txt, r06_ab/rounds_tail.txt)
         // Rounds run in batches of kRoundBatch without a host round trip: every round takes its input count from the device
         // (the launches are sized by the count of the last read-back: counts only shrink), a round with nothing pending is two
         // empty launches.  Round 2 read the count back after every round: 76 synchronisations for config 5's giant component.
@@ -1475,8 +1257,8 @@ int graph_stage_on_device(const Graph &g, int64_t max_nodes, int device, bool st
         uint32_t *rc_ = rounds_arena.take_n<uint32_t>(kRoundBatch + 2);
         if (!rc_) { set_error("graph stage: rounds arena exhausted"); return LFR_ERR_NOMEM; }
         int64_t launched = 0;
-        if (!done) LFR_HIP_TRY(hipMemsetAsync(rc_, 0, 4 * (kRoundBatch + 2), st));
-        for (int64_t k_lo = 0, size = first_block; !done && k_lo < M; k_lo += size, size *= 2) {
+        LFR_HIP_TRY(hipMemsetAsync(rc_, 0, 4 * (kRoundBatch + 2), st));
+        for (int64_t k_lo = 0, size = first_block; k_lo < M; k_lo += size, size *= 2) {
             const int64_t k_hi = std::min(M, k_lo + size);
             LFR_HIP_TRY(hipMemsetAsync(rc_ + kRoundBatch, 0, 4, st));
             hipLaunchKernelGGL(k_large_pending, grid_for_items(k_hi - k_lo, kAppendItems), dim3(kThreads), 0, st, k_lo, k_hi, serial_limit, flags, segid, starts, order, n1, n2,
@@ -1484,58 +1266,7 @@ int graph_stage_on_device(const Graph &g, int64_t max_nodes, int device, bool st
             LFR_HIP_TRY(hipMemcpyAsync(h_ctr, rc_ + kRoundBatch, 4, hipMemcpyDeviceToHost, st));
             LFR_HIP_TRY(stream_wait(st));
             uint32_t bound = h_ctr[0];
-            if (xcd_tail && bound > 0) {
-                if (launched + 1 > kMaxRounds) return use_host("round limit");
-                hipLaunchKernelGGL(k_round_counters_shift, dim3(1), dim3(64), 0, st, rc_, kRoundBatch);         // rc_[0] = pending, rc_[1..] = 0
-                const unsigned long long round_hi = (unsigned long long)(kMaxRounds - launched) << 32;
-                hipLaunchKernelGGL(k_round_eval, grid_for_items(bound, kEvalItems), dim3(kThreads), 0, st, rc_, pa, par, bits, W, round_hi, minpos, pb, rc_ + 1);
-                hipLaunchKernelGGL(k_round_accept, grid_for(bound), dim3(kThreads), 0, st, rc_ + 1, pb, round_hi, minpos, par, cnt, bits, W, ctr + 3);
-                std::swap(pa, pb);
-                ++launched;
-                // the survivors (pa, rc_[1] entries) finish their rounds on one XCD
-                LFR_HIP_TRY(hipMemsetAsync(xbar, 0, 4 * 160, st));
-                LFR_HIP_TRY(hipMemsetAsync(ctr + 8, 0, 4 * 8, st));
-                LFR_HIP_TRY(hipMemcpyAsync(ctr + 8, rc_ + 1, 4, hipMemcpyDeviceToDevice, st));
-                RoundsArgs ra{M, first_block, serial_limit, flags, segid, starts, order, n1, n2, dg->node_image, W, kMaxRounds, bits, minpos, pa, pb, par, cnt, ctr + 8, xbar, 1, (int)launched};
-                // (every participant must be resident at once - they meet at barriers: never more workgroups per CU than half of what the
-                // occupancy query admits; a larger request hung the launch until its timeout)
-                static int occ = -1;
-                if (occ < 0) { int nb = 0; occ = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_rounds_all<true>, kThreads, 0) == hipSuccess ? nb : 2; }
-                int per_cu = std::max(1, std::min(4, occ / 2));
-                if (const char *eb = getenv("LFR_ROUNDS_BLOCKS_PER_CU")) per_cu = std::max(1, std::min(per_cu, atoi(eb)));
-                hipLaunchKernelGGL(k_rounds_all<true>, dim3((unsigned)(per_cu * ctx->n_cu)), dim3(kThreads), 0, st, ra);
-                LFR_HIP_TRY(hipGetLastError());
-                LFR_HIP_TRY(hipMemcpyAsync(h_ctr, ctr + 8, 4 * 5, hipMemcpyDeviceToHost, st));
-                LFR_HIP_TRY(hipMemsetAsync(rc_, 0, 4 * (kRoundBatch + 2), st));
-                LFR_HIP_TRY(stream_wait(st));
-                if (h_ctr[4]) return use_host("a path-shaped dependency chain");                          // a path-shaped dependency chain: sequential anyway
-                if (((int64_t)h_ctr[2] - launched) & 1) std::swap(pa, pb);              // (the kernel swapped its lists once per round)
-                rounds += 1 + ((int64_t)h_ctr[2] - launched);
-                launched = h_ctr[2];
-                if (trace > 2) fprintf(stderr, "lfr graph stage:   block [%lld, %lld): %lld rounds so far\n", (long long)k_lo, (long long)k_hi, (long long)rounds);
-                bound = 0;
-            }
             while (bound > 0) {
-                if (tail_cfg.first && bound <= tail_cfg.first && !xcd_tail) {
-                    // the rest of this block's rounds on one XCD: pa holds `bound` entries (rc_[0] after the shift below), launched rounds have run
-                    hipLaunchKernelGGL(k_round_counters_shift, dim3(1), dim3(64), 0, st, rc_, kRoundBatch);
-                    LFR_HIP_TRY(hipMemsetAsync(xbar, 0, 4 * 160, st));
-                    LFR_HIP_TRY(hipMemsetAsync(ctr + 8, 0, 4 * 8, st));
-                    LFR_HIP_TRY(hipMemcpyAsync(ctr + 8, rc_, 4, hipMemcpyDeviceToDevice, st));
-                    RoundsArgs ra{M, first_block, serial_limit, flags, segid, starts, order, n1, n2, dg->node_image, W, kMaxRounds, bits, minpos, pa, pb, par, cnt, ctr + 8, xbar, 1, (int)launched};
-                    hipLaunchKernelGGL(k_rounds_all<true>, dim3((unsigned)(8 * tail_cfg.second)), dim3(kThreads), 0, st, ra);
-                    LFR_HIP_TRY(hipGetLastError());
-                    LFR_HIP_TRY(hipMemcpyAsync(h_ctr, ctr + 8, 4 * 5, hipMemcpyDeviceToHost, st));
-                    LFR_HIP_TRY(hipMemsetAsync(rc_, 0, 4 * (kRoundBatch + 2), st));
-                    LFR_HIP_TRY(stream_wait(st));
-                    if (h_ctr[4]) return use_host("a path-shaped dependency chain");
-                    if (((int64_t)h_ctr[2] - launched) & 1) std::swap(pa, pb);              // (the kernel swapped its lists once per round)
-                    rounds += (int64_t)h_ctr[2] - launched;
-                    launched = h_ctr[2];
-                    if (trace > 2) fprintf(stderr, "lfr graph stage:   block [%lld, %lld): pending %u finished on one XCD, %lld rounds so far\n", (long long)k_lo, (long long)k_hi, bound, (long long)rounds);
-                    bound = 0;
-                    break;
-                }
                 if (launched + kRoundBatch > kMaxRounds) return use_host("round limit");   // a path-shaped dependency chain: sequential anyway
                 hipLaunchKernelGGL(k_round_counters_shift, dim3(1), dim3(64), 0, st, rc_, kRoundBatch);
                 for (int j = 0; j < kRoundBatch; ++j, ++launched) {

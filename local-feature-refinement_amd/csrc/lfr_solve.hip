@@ -124,17 +124,9 @@ struct KernelArgs {
 #define PROF_SWEEP_MARK(i)
 #define PROF_FACTOR_MARK(i) PROF_MARK(i)
 #endif
-// Experiments (scripts/ab_packed.py builds them as variants): what a phase of the packed kernel costs, measured by running it TWICE
+// Experiments (-DLFR_ABL_*: scripts/ab_packed.py builds them as variants): what a phase of the packed kernel costs, measured by running it TWICE
 // with unchanged results (round 6, config 4, 0.45 ms: atomics +15 %, evaluation +21 %, matrix build + elimination +16 %,
 // reductions +2 %, zeroing +2 % - profiles/r06_ablation_packed_kernel.txt)
-#ifdef LFR_DOUBLE_ATOMICS          // every term of the assembly added as two halves
-#define LFR_ASM_ADD(p, v) do { const double v_ = 0.5 * (v); atomicAdd(p, v_); atomicAdd(p, v_); } while (0)
-#else
-#define LFR_ASM_ADD(p, v) atomicAdd(p, v)
-#endif
-#ifndef LFR_LOG_REGS
-#define LFR_LOG_REGS 1             // 8- / 16-row classes: the logarithm's series coefficients live in VGPRs (0: literals moved into SGPRs at every use)
-#endif
 #ifndef LFR_GJ_DPP
 #define LFR_GJ_DPP 2               // elimination of the 16-row (1) and also the 8-row (2) packed class with DPP row broadcasts; 0: ds_swizzle
 #endif
@@ -389,7 +381,7 @@ __device__ __forceinline__ void solve_group_body(const KernelArgs &a, const int 
 
     bool at_zero = true;                              // wave-uniform: the first sweep evaluates every edge at the origin (PH_EVAL_INIT)
     // the logarithm's series coefficients in 22 VGPRs for the whole solve where the class has them to spare (8- and 16-row classes)
-    constexpr bool kLogRegs = NV <= 16 && LPR == 1 && LFR_LOG_REGS;
+    constexpr bool kLogRegs = NV <= 16 && LPR == 1;
     LogCoef logc;
     if constexpr (kLogRegs) logc.load();
     const LogCoef *lcp = kLogRegs ? &logc : nullptr;
@@ -526,16 +518,16 @@ __device__ __forceinline__ void solve_group_body(const KernelArgs &a, const int 
                 const double c1 = c_own1 + dpp_f64<kDppQuadXor1>(c_send1);
                 const double c2 = c_own2 + dpp_f64<kDppQuadXor1>(c_send2);
                 if (ra >= 0) {
-                    LFR_ASM_ADD(&A[ra * LD + ra], o.j00 * o.j00 + o.j10 * o.j10 + p_w);
-                    LFR_ASM_ADD(&A[(ra + 1) * LD + ra], o.j01 * o.j00 + o.j11 * o.j10);
-                    LFR_ASM_ADD(&A[(ra + 1) * LD + ra + 1], o.j01 * o.j01 + o.j11 * o.j11 + p_w);
-                    LFR_ASM_ADD(&g[ra], o.j00 * o.r0 + o.j10 * o.r1 + p_g0);
-                    LFR_ASM_ADD(&g[ra + 1], o.j01 * o.r0 + o.j11 * o.r1 + p_g1);
+                    atomicAdd(&A[ra * LD + ra], o.j00 * o.j00 + o.j10 * o.j10 + p_w);
+                    atomicAdd(&A[(ra + 1) * LD + ra], o.j01 * o.j00 + o.j11 * o.j10);
+                    atomicAdd(&A[(ra + 1) * LD + ra + 1], o.j01 * o.j01 + o.j11 * o.j11 + p_w);
+                    atomicAdd(&g[ra], o.j00 * o.r0 + o.j10 * o.r1 + p_g0);
+                    atomicAdd(&g[ra + 1], o.j01 * o.r0 + o.j11 * o.r1 + p_g1);
                 }
                 if (ra >= 0 && rb >= 0) {
                     const int r1 = rb + q, k1 = ra, r2 = rb + 1 - q, k2 = ra + 1;
-                    LFR_ASM_ADD(&A[rb > ra ? r1 * LD + k1 : k1 * LD + r1], c1);
-                    LFR_ASM_ADD(&A[rb > ra ? r2 * LD + k2 : k2 * LD + r2], c2);
+                    atomicAdd(&A[rb > ra ? r1 * LD + k1 : k1 * LD + r1], c1);
+                    atomicAdd(&A[rb > ra ? r2 * LD + k2 : k2 * LD + r2], c2);
                 }
             }
         } else {
@@ -1281,19 +1273,13 @@ __device__ __forceinline__ void solve_component(const KernelArgs &a, const int m
     // off-diagonal entry gets ONE term from each of them, i.e. while no node pair is matched twice inside the component (the
     // reference keeps duplicated matches, solve.cc:476-478; they are rare).  Duplicates sit next to each other in a node's in-edge
     // list (sorted by record index = by source node): one scan per solve decides, components with duplicates take the one-thread walk.
-#ifndef LFR_SPLIT_WALK
-#define LFR_SPLIT_WALK 1
-#endif
-    bool split_walk = LFR_SPLIT_WALK != 0;
-    if (split_walk) {
-        int dup = 0;
-        for (int i = tid; i + 1 < E; i += kBlockThreads) {
-            const uint32_t e0 = in_idx[i], e1 = in_idx[i + 1];
-            const uint32_t k0 = *reinterpret_cast<const uint32_t *>(&edges[e0].src), k1 = *reinterpret_cast<const uint32_t *>(&edges[e1].src);
-            dup |= ((k0 ^ k1) & 0x7fffffffu) == 0u;                 // same source, same destination (the kind bit aside)
-        }
-        split_walk = block_max<kBlockThreads>((double)dup, sh) == 0.0;
+    int dup = 0;
+    for (int i = tid; i + 1 < E; i += kBlockThreads) {
+        const uint32_t e0 = in_idx[i], e1 = in_idx[i + 1];
+        const uint32_t k0 = *reinterpret_cast<const uint32_t *>(&edges[e0].src), k1 = *reinterpret_cast<const uint32_t *>(&edges[e1].src);
+        dup |= ((k0 ^ k1) & 0x7fffffffu) == 0u;                     // same source, same destination (the kind bit aside)
     }
+    const bool split_walk = block_max<kBlockThreads>((double)dup, sh) == 0.0;
     PROF_DECL
     auto sweep_scratch = [&](const double *xv, double *gout, bool want_matrix) -> double {
         double cost = 0.0;
@@ -1466,10 +1452,7 @@ __device__ __forceinline__ void solve_component(const KernelArgs &a, const int m
     // in any order - as 64-bit FIXED-POINT integers (2^-40 units, |term| < 128, so 2^15 in-edges cannot overflow): integer
     // addition is associative, the sums are bitwise reproducible whatever the order.  Resolution 9e-13 on entries of O(1-100).
     // Components with duplicated matches (three or more terms on a cross entry) or a term outside the range take the scratch sweep.
-#ifndef LFR_FUSED_SWEEP
-#define LFR_FUSED_SWEEP 1
-#endif
-    bool fused_sweep = LFR_FUSED_SWEEP != 0 && split_walk && !a.scratch_sweep;
+    bool fused_sweep = split_walk && !a.scratch_sweep;
     auto sweep_fused = [&](const double *xv, double *gout, bool want_matrix, bool &overflow) -> double {
         constexpr double kFx = 0x1p40, kFxInv = 0x1p-40;
         unsigned long long *fx_g = reinterpret_cast<unsigned long long *>(vstep), *fx_d = reinterpret_cast<unsigned long long *>(vD);
@@ -2142,46 +2125,23 @@ __device__ __forceinline__ void solve_tree_component(const KernelArgs &a, const 
             }
             return q;
         };
-#ifndef LFR_T_SWEEP_MERGE
-#define LFR_T_SWEEP_MERGE 1
-#endif
-#if LFR_T_SWEEP_MERGE
         NodePre np = node_pre(gt);
         tsync();                                                            // cross blocks and partial sums are out
-#else
-        { double z1 = 0.0, z2 = 0.0, z3 = 0.0, z4 = 0.0; treduce5(cost, z1, z2, z3, z4); }
-        const double cost_total = cost;
-        cost = 0.0;
-        NodePre np = node_pre(gt);
-#endif
         TR(21, 0);
         double sn = 0.0, xn = 0.0, gd = 0.0, gm = 0.0;
         for (int p = gt; p < 8 * NB; p += GT) {
-#if LFR_T_SWEEP_MERGE
             const NodePre nq = np;
             if (p + GT < 8 * NB) np = node_pre(p + GT);
-#else
-            const NodePre nq = p == gt ? np : node_pre(p);
-#endif
             if (nq.ip == kNone) continue;
             const uint32_t i0 = nq.i0, i1 = nq.i1;
             const double xo0 = nq.xo0, xo1 = nq.xo1, dl0 = nq.dl0, dl1 = nq.dl1;
             double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0, s4 = 0.0;
-#ifndef LFR_T_NODE_BATCH
-#define LFR_T_NODE_BATCH 1
-#endif
-            for (uint32_t ib0 = i0; ib0 < i1; ib0 += (uint32_t)LFR_T_NODE_BATCH) {
-                double u[LFR_T_NODE_BATCH][5];
+            for (uint32_t ib = i0; ib < i1; ++ib) {
+                const double *pp = part + 6 * (size_t)ib;
+                double u[5];
 #pragma unroll
-                for (int k = 0; k < LFR_T_NODE_BATCH; ++k) {
-                    const double *pp = part + 6 * (size_t)min(ib0 + (uint32_t)k, i1 - 1u);
-#pragma unroll
-                    for (int c = 0; c < 5; ++c) u[k][c] = ldd(pp + c);
-                }
-#pragma unroll
-                for (int k = 0; k < LFR_T_NODE_BATCH; ++k) {
-                    if (ib0 + (uint32_t)k < i1) { s0 += u[k][0]; s1 += u[k][1]; s2 += u[k][2]; s3 += u[k][3]; s4 += u[k][4]; }
-                }
+                for (int c = 0; c < 5; ++c) u[c] = ldd(pp + c);
+                s0 += u[0]; s1 += u[1]; s2 += u[2]; s3 += u[3]; s4 += u[4];
             }
             double *T = atiles + ((size_t)nq.dt << 8) + 34 * (p & 7);  // entry (2 slot, 2 slot) of the diagonal tile
             T[0] = s0; T[16] = s1; T[17] = s2;
@@ -2197,9 +2157,6 @@ __device__ __forceinline__ void solve_tree_component(const KernelArgs &a, const 
         TR(22, 0);
         treduce5(cost, sn, xn, gd, gm);                                     // (its barrier also publishes the node pass)
         TR(23, 0);
-#if !LFR_T_SWEEP_MERGE
-        cost = cost_total;
-#endif
         so.cost = cost; so.sn = sn; so.xn = xn; so.gd = gd; so.gm = gm;
         return so;
     };
@@ -2389,10 +2346,6 @@ __device__ __forceinline__ void solve_tree_component(const KernelArgs &a, const 
 #pragma unroll
             for (int r = 0; r < 4; ++r) acc.cD[r] += (r16 >> 2) == r ? dd2 : 0.0;
         }
-#ifndef LFR_T_PINGPONG
-#define LFR_T_PINGPONG 1
-#endif
-#if LFR_T_PINGPONG
         // Further entries (a column near the root of the tree has 5-20 of them: one per descendant that touches it).  Their operands are
         // all there once the children are done, and a load from the workspace is 1-2 us: with one entry at a time the root chain of a
         // 2.4 k-row component spent half of the factorization's critical path waiting for operands.  Two operand sets alternate - the
@@ -2431,18 +2384,6 @@ __device__ __forceinline__ void solve_tree_component(const KernelArgs &a, const 
                 ++e; ++ei;
             }
         }
-#else
-        if (dc.ne > 0u) apply_ops(dc.a00, dc.a01, dc.a02, pn.o0, pn.y0, acc);
-        for (uint32_t e = dc.e_rest - 1u; e < dc.e_rest - 2u + dc.ne && dc.ne > 1u; ++e) {    // further entries (a separator's column has one per child)
-            if (gated) gate_wait(gate, e - (dc.e_rest - 2u));
-            const uint32_t k = col_upd[5 * e], tb = col_upd[5 * e + 1], a0 = col_upd[5 * e + 2], a1 = col_upd[5 * e + 3], a2 = col_upd[5 * e + 4];
-            UpdB o;
-            UpdY y;
-            load_b(k, tb, o);
-            load_y(a0, a1, a2, y);
-            apply_ops(a0, a1, a2, o, y, acc);
-        }
-#endif
         double wacc = acc.wacc;
         wacc += __shfl_xor(wacc, 16, 64);
         wacc += __shfl_xor(wacc, 32, 64);
@@ -2573,10 +2514,7 @@ __device__ __forceinline__ void solve_tree_component(const KernelArgs &a, const 
     // this wave's next column after position q of level l (levels ascending / descending); false: none left
     // (the first column of level l goes to wave l mod GW: a chain of single-column levels - the blocks of a top separator - then
     // alternates between waves, and the parent's wave streams through its finished entries while the child is being eliminated)
-#ifndef LFR_T_ROTATE
-#define LFR_T_ROTATE 1
-#endif
-    auto first_of = [&](const int l) -> int { return LFR_T_ROTATE ? (gw - l % GW + GW) % GW : gw; };
+    auto first_of = [&](const int l) -> int { return (gw - l % GW + GW) % GW; };
     auto next_up = [&](int &l, int &q) -> bool {
         q += GW;
         while (q >= (int)level_ptr[l + 1]) { if (++l >= n_levels) return false; q = (int)level_ptr[l] + first_of(l); }
@@ -2600,18 +2538,12 @@ __device__ __forceinline__ void solve_tree_component(const KernelArgs &a, const 
         if (have) dn = load_desc(q);
         while (have) {
             const ColDesc dc = dn;
-#ifndef LFR_T_SPLIT_PREFETCH
-#define LFR_T_SPLIT_PREFETCH 2      // 0: a column's loads go out together once its children are done (round 4); 1: the half that does not depend
-                                    // on the children goes out early, for the wave's next column inside the current one; 2: ... AFTER the current
-                                    // column has been published when the next one is not ready yet (the publishing `s_waitcnt vmcnt(0)` waits for
-                                    // every load in flight: a prefetch in front of it delayed the hand-off along the critical path)
-#endif
+            // (loads that do not wait for the children go out early, for a next column not ready yet only after the publication: docs/history/DESIGN_rounds1-5.md)
             EntryGate gate = gate_open(dc);
             TR(1, dc.J | (pre ? 0x10000u : 0u) | (dc.ne << 20));
             if (!pre) {                                   // not prefetched: wait for the column of the first entry, then load its rows
-                if (LFR_T_SPLIT_PREFETCH && !pre_static) issue_static(dc, pn);
+                if (!pre_static) issue_static(dc, pn);
                 if (dc.ne > 0u) gate_wait(gate, 0u);
-                if (!LFR_T_SPLIT_PREFETCH) issue_static(dc, pn);
                 issue_ops(dc, pn);
             }
             TR(2, dc.J);
@@ -2623,12 +2555,12 @@ __device__ __forceinline__ void solve_tree_component(const KernelArgs &a, const 
                 next_ready = dn.ne == 0u || pend_load(dn.k0) != 0;          // (its first entry's column is factored: that entry's rows can be requested)
                 if (next_ready) observe_fence();
             }
-            run_column(dc, pn, gate, true, LFR_T_SPLIT_PREFETCH == 1 ? have : next_ready, next_ready, dn, true, xd, fprof, ft_, ft0_);
-            pre = next_ready; pre_static = LFR_T_SPLIT_PREFETCH == 1 ? have : next_ready;
+            run_column(dc, pn, gate, true, next_ready, next_ready, dn, true, xd, fprof, ft_, ft0_);
+            pre = next_ready; pre_static = next_ready;
             publish_fence();                                               // the column's rows are out before anyone hears of it
             if (lane == 0) state_store(dc.J, 1);
             TR(5, dc.J);
-            if (LFR_T_SPLIT_PREFETCH == 2 && have && !next_ready) { issue_static(dn, pn); pre_static = true; }
+            if (have && !next_ready) { issue_static(dn, pn); pre_static = true; }
         }
         tsync();
         if constexpr (TEAM) {                             // a bad pivot anywhere in the team rejects the step for everyone
@@ -2802,10 +2734,9 @@ __device__ __forceinline__ void solve_tree_component(const KernelArgs &a, const 
                 const ColDesc dc = dn;
                 TR(6, dc.J | (pre ? 0x10000u : 0u));
                 if (!pre) {
-                    if (LFR_T_SPLIT_PREFETCH && !pre_static) issue_back_static(dc, pn);
+                    if (!pre_static) issue_back_static(dc, pn);
                     pend_wait([&]() { return dc.parent == kNone || pend_load(dc.parent) == 2; });
                     observe_fence();
-                    if (!LFR_T_SPLIT_PREFETCH) issue_back_static(dc, pn);
                     issue_back_y(dc, pn);
                 }
                 TR(7, dc.J);
@@ -2816,12 +2747,12 @@ __device__ __forceinline__ void solve_tree_component(const KernelArgs &a, const 
                     next_ready = dn.parent == kNone || pend_load(dn.parent) == 2;
                     if (next_ready) observe_fence();
                 }
-                run_back(dc, pn, LFR_T_SPLIT_PREFETCH == 1 ? have : next_ready, next_ready, dn);
-                pre = next_ready; pre_static = LFR_T_SPLIT_PREFETCH == 1 ? have : next_ready;
+                run_back(dc, pn, next_ready, next_ready, dn);
+                pre = next_ready; pre_static = next_ready;
                 publish_fence();
                 if (lane == 0) state_store(dc.J, 2);
                 TR(8, dc.J);
-                if (LFR_T_SPLIT_PREFETCH == 2 && have && !next_ready) { issue_back_static(dn, pn); pre_static = true; }
+                if (have && !next_ready) { issue_back_static(dn, pn); pre_static = true; }
             }
             tsync();
             return;
@@ -3293,14 +3224,9 @@ __device__ __forceinline__ void block_kernel_body(const KernelArgs &a, int max_r
         __syncthreads();                              // the component's last LDS reads are done
     }
 }
-// (LFR_BLOCK_WPE_256=1 with LFR_THREADS_L=256: the experiment of round 6 - the 192-row class on 256 threads with 512 registers and no
-// spill at all ran 5.92 ms per config-5 solve against 5.80 with the spills and 4.55 for 512 threads: the kernel lives on its threads, the
-// spills are not what holds it; profiles/r06_ab/block_kernel_spills.txt)
-#ifndef LFR_BLOCK_WPE_256
-#define LFR_BLOCK_WPE_256 2
-#endif
+// (two waves per SIMD at every size: without the spills at one wave the kernel was slower - profiles/r06_ab/block_kernel_spills.txt)
 template <int kBlockThreads>
-__global__ __launch_bounds__(kBlockThreads) __attribute__((amdgpu_waves_per_eu(kBlockThreads == 256 ? LFR_BLOCK_WPE_256 : 2, kBlockThreads == 256 ? LFR_BLOCK_WPE_256 : 2))) void solve_block_kernel(const KernelArgs a, int max_rows) {
+__global__ __launch_bounds__(kBlockThreads) __attribute__((amdgpu_waves_per_eu(2, 2))) void solve_block_kernel(const KernelArgs a, int max_rows) {
     block_kernel_body<kBlockThreads>(a, max_rows);
 }
 
@@ -4060,7 +3986,7 @@ __global__ __launch_bounds__(64) void debug_solve_packed_kernel(int64_t n_sys, c
 // Workgroup classes: one workgroup per system, the dynamic LDS of a class whose largest component has max_rows rows carved as
 // solve_component carves it (what is not the system reads as NaN), then factor_lds and the back substitution.
 template <int kBlockThreads>
-__global__ __launch_bounds__(kBlockThreads) __attribute__((amdgpu_waves_per_eu(kBlockThreads == 256 ? LFR_BLOCK_WPE_256 : 2, kBlockThreads == 256 ? LFR_BLOCK_WPE_256 : 2)))
+__global__ __launch_bounds__(kBlockThreads) __attribute__((amdgpu_waves_per_eu(2, 2)))
 void debug_solve_block_kernel(int max_rows, int64_t lds_doubles, const int32_t *n_rows, const int64_t *tri_off, const int64_t *vec_off, const double *A,
                               const double *damp, const double *g, double *y, int32_t *status, unsigned int *spin_timeouts) {
     extern __shared__ double dyn[];
