@@ -302,6 +302,53 @@ int lfr_batch_positions_view_f32(lfr_batch *b, const float **positions);
 int64_t lfr_batch_component_info(lfr_batch *b, int64_t *component, int32_t *iterations, int32_t *termination,
                                  double *final_cost, int32_t *n_var_nodes, int32_t *n_edges);
 
+/* ---------------------------------------------------------------------------------------------
+ * Implicit-gradient backward pass through lfr_batch_solve (no counterpart in the reference: the
+ * in-process PyTorch interface, lfr_amd/autograd.py, trains the two-view network through it).
+ *
+ * Contract.  Take the batch after its latest lfr_batch_solve; x^ = the fp64 positions it produced.  Per solved component, with the
+ * component structure of that solve held fixed:
+ *   - F(x; theta) = sum_e 1/2 w_e rho_kind(e)(|r_e|^2) over the component's kept directed edges (exactly those the solve uses:
+ *     intra-track edges Cauchy(0.25), inter-track edges Tukey(0.0625) in the batch's variant), r_e = x_dst - x_src - f(x_src; phi_e),
+ *     phi_e the edge's 18 flow values, w_e its similarity (cost.cc:78-94, solve.cc:98-143);
+ *   - usable components: termination CONVERGENCE or NO_CONVERGENCE.  FAILURE components get a zero gradient;
+ *   - free coordinates: those of the variable nodes of usable components with |x^| < 1.  Coordinates at the +-1 box bound, roots and
+ *     other constant nodes are constant;
+ *   - H = the EXACT Hessian of F over the free coordinates at x^ (not Gauss-Newton): per edge w [J^T (rho' I + 2 rho'' r r^T) J +
+ *     rho' sum_k r_k d2 r_k], the second term in the src-src block from the biquadratic's second derivatives, taken where a
+ *     coordinate is in [-0.5, 0.5] and zero where cost.cc:38-43 zeroes the first derivative;
+ *   - v = H^-1 ubar (ubar = the caller's dL/dx^ on the free coordinates); per kept edge
+ *     (dL/dphi_e, dL/dw_e) = -d/dtheta_e [v . grad F_e(x^; theta_e)];
+ *   - scattered to the MATCH layout of the graph - the input order of lfr_graph_from_arrays* with the matches of banned pairs removed:
+ *     edge node1 -> node2 of match m goes to grad_disp2[m], edge node2 -> node1 to grad_disp1[m] (solve.cc:477-478), grad_sim[m] is
+ *     the sum over both directions.  Every other entry is 0: dropped edges, edges with two constant ends, matches outside this shard;
+ *   - a factorization of H that meets a pivot that is not positive gives that component a zero gradient and reports it indefinite.
+ * The tracks, roots, components, edge kinds and the active set of the box are piecewise constant in theta: the gradient treats them
+ * as fixed.  It is taken at x^, where LM stopped by its tolerances, not at an exact stationary point of F.
+ * Kernels: one workgroup per component over the batch's kernel classes; H in LDS up to 192 rows, in an HBM workspace above; a dense
+ * LDL^T that skips the zeros of each column.  Components above 6144 rows: LFR_ERR_UNSUPPORTED. */
+typedef struct lfr_backward_stats {
+    int64_t n_differentiated;      /* components whose gradient was computed */
+    int64_t n_not_usable;          /* FAILURE components (zero gradient) */
+    int64_t n_indefinite;          /* components whose H met a pivot that is not positive (zero gradient) */
+    int64_t n_bound_coordinates;   /* coordinates of usable components held at the +-1 bound */
+    double kernel_ms;              /* HIP-event time of the backward's kernels (and its clearing of the outputs) */
+} lfr_backward_stats;
+
+#define LFR_BACKWARD_F64 1         /* outputs are double instead of float32 */
+
+/* Stream-ordered device copy of the latest solve's positions (2 * n_nodes doubles of the whole graph; nodes outside the shard: 0). */
+int lfr_batch_positions_to_device(lfr_batch *b, double *dst_device, void *hip_stream);
+/* The gradient above.  grad_positions_device: 2 * n_nodes doubles (dL/dx of the whole graph); grad_disp1/2_device: n_matches x 18,
+ * grad_sim_device: n_matches, float32 (double with LFR_BACKWARD_F64); whole arrays are overwritten.  Runs on `hip_stream` after the
+ * latest solve; asynchronous unless stats != NULL.  LFR_ERR_ARG before the first solve.  The first call sets up its workspace and,
+ * for batches whose records do not carry their directed-edge ids, maps records to edges from the graph (which must still be alive). */
+int lfr_batch_backward(lfr_batch *b, const double *grad_positions_device, void *grad_disp1_device, void *grad_disp2_device,
+                       void *grad_sim_device, int flags, void *hip_stream, lfr_backward_stats *stats);
+/* Per component (order of lfr_batch_component_info) of the latest backward: 0 differentiated, 1 not usable, 2 indefinite.
+ * Waits for that backward.  Returns the count (< 0: error, LFR_ERR_ARG before the first backward). */
+int64_t lfr_batch_backward_status(lfr_batch *b, int32_t *status);
+
 /* Unit-level probe of the device arithmetic (cost.cc:13-48,78-90 + the loss / corrector of solve.cc:111,120): for
  * each of n edges (flows n x 18 float32, sim, kind 0 = intra-track/Cauchy 1 = inter-track/Tukey, x1 = source and
  * x2 = destination position) the kernels' eval_edge on the GPU: out8[8i..] = 0.5*rho, corrected residual r0 r1,

@@ -1,0 +1,508 @@
+// Implicit-gradient backward pass through the batched LM solve (lfr_batch_backward, include/lfr.h).
+// Included at the end of lfr_solve.hip: it reads the batch layout (lfr_batch, CompInfoDev, ensure_mirrors) that lives there and
+// changes nothing the forward kernels read.
+//
+// Per solved component, one workgroup:
+//   1. the EXACT Hessian H of F = sum_e 1/2 w_e rho(|r_e|^2) over the free coordinates at the solve's x (owner computes: the thread of a
+//      variable node sums the rows of its two coordinates over the node's out- and in-edges in record order - deterministic), the
+//      caller's dL/dx as right-hand side, bound coordinates (|x| >= 1) replaced by identity rows / columns and a zero right-hand side;
+//   2. LDL^T of H (right-looking; the update of column k touches only the pairs of NONZERO entries of column k, so the tree-plus-cycles
+//      systems of the size cap cost what their fill costs, not n^3) and v = H^-1 ubar.  A pivot that is not positive (or not finite)
+//      marks the component indefinite: its gradient stays zero;
+//   3. the vector-Jacobian sweep: one thread per record writes -d/dtheta_e [v . grad F_e] into the match layout of the graph.
+// The packed lower triangle of H lives in LDS for the classes of up to 192 rows (<= 148 KB) and in an HBM workspace above.
+
+namespace {
+
+constexpr int kBwdThreadsSmall = 64;         // packed classes (<= 32 rows): one wave per component
+constexpr int kBwdThreads = 256;             // workgroup classes
+constexpr int kBwdMaxRows = 6144;            // largest system of the HBM variant: its vectors fill the LDS (lfr.h: LFR_ERR_UNSUPPORTED above)
+
+// Derivatives of the biquadratic interpolant (cost.cc:13-48) at the source point, with the reference's zeroing of the first derivative
+// outside [-0.5, 0.5] (cost.cc:38-43) carried over to the second derivatives.
+struct BwdEdge {
+    double lr[3], dlr[3], d2lr[3], lc[3], dlc[3], d2lc[3];
+    double f[2], fr[2], fc[2], frr[2], frc[2], fcc[2];
+    double r[2], w, rho1, rho2;
+};
+
+__device__ __forceinline__ void bwd_basis(double x, double (&l)[3], double (&dl)[3], double (&d2l)[3]) {
+    const double t = fmax(fmin(x, 0.5), -0.5);
+    const bool in = (t == x);
+    l[0] = 2. * t * (t - .5); l[1] = (-4.) * (t - .5) * (t + .5); l[2] = 2. * t * (t + .5);
+    dl[0] = in ? 2. * t + 2. * (t - .5) : 0.; dl[1] = in ? (-4.) * (t - .5) + (-4.) * (t + .5) : 0.; dl[2] = in ? 2. * t + 2. * (t + .5) : 0.;
+    d2l[0] = in ? 4. : 0.; d2l[1] = in ? -8. : 0.; d2l[2] = in ? 4. : 0.;
+}
+
+__device__ __forceinline__ void bwd_eval(const EdgeRec &e, int kind, int tukey_variant, double x1r, double x1c, double x2r, double x2c,
+                                         BwdEdge &o) {
+    bwd_basis(x1r, o.lr, o.dlr, o.d2lr);
+    bwd_basis(x1c, o.lc, o.dlc, o.d2lc);
+#pragma unroll
+    for (int k = 0; k < 2; ++k) { o.f[k] = o.fr[k] = o.fc[k] = o.frr[k] = o.frc[k] = o.fcc[k] = 0.; }
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int j = 0; j < 3; ++j)
+#pragma unroll
+            for (int k = 0; k < 2; ++k) {
+                const double d = (double)e.flow[2 * (3 * i + j) + k];
+                o.f[k] += o.lr[i] * o.lc[j] * d;
+                o.fr[k] += o.dlr[i] * o.lc[j] * d;
+                o.fc[k] += o.lr[i] * o.dlc[j] * d;
+                o.frr[k] += o.d2lr[i] * o.lc[j] * d;
+                o.frc[k] += o.dlr[i] * o.dlc[j] * d;
+                o.fcc[k] += o.lr[i] * o.d2lc[j] * d;
+            }
+    o.r[0] = x2r - x1r - o.f[0];
+    o.r[1] = x2c - x1c - o.f[1];
+    const double s = o.r[0] * o.r[0] + o.r[1] * o.r[1];
+    o.w = (double)e.sim;
+    if (kind == 0) {                                   // CauchyLoss(0.25)
+        const double inv = 1.0 / (1.0 + s * kCauchyC);
+        o.rho1 = fmax(DBL_MIN, inv);
+        o.rho2 = -kCauchyC * inv * inv;
+    } else if (s <= kTukeyA2) {                        // TukeyLoss(0.0625), Ceres 1.x (1) or 2.x (2)
+        const double v = 1.0 - s / kTukeyA2;
+        o.rho1 = tukey_variant == 1 ? 0.5 * v * v : v * v;
+        o.rho2 = tukey_variant == 1 ? -v / kTukeyA2 : -2.0 * v / kTukeyA2;
+    } else {
+        o.rho1 = 0.; o.rho2 = 0.;
+    }
+}
+
+// M = w (rho' I + 2 rho'' r r^T), P = I + df/dx_src: the edge's Hessian over (x_src, x_dst) is [[P^T M P - w rho' sum_k r_k d2f_k, -P^T M],
+// [-M P, M]].
+__device__ __forceinline__ void bwd_blocks(const BwdEdge &o, double (&M)[2][2], double (&P)[2][2]) {
+    const double a = o.w * o.rho1, b = 2.0 * o.w * o.rho2;
+    M[0][0] = a + b * o.r[0] * o.r[0]; M[0][1] = b * o.r[0] * o.r[1]; M[1][0] = M[0][1]; M[1][1] = a + b * o.r[1] * o.r[1];
+    P[0][0] = 1.0 + o.fr[0]; P[0][1] = o.fc[0]; P[1][0] = o.fr[1]; P[1][1] = 1.0 + o.fc[1];
+}
+
+struct BwdArgs {
+    const CompDesc *descs;
+    const EdgeRec *edges;
+    const uint32_t *node_ids;
+    const lfr::NodeInc *node_inc;
+    const uint32_t *in_idx;
+    const double *positions;
+    const CompInfoDev *infos;
+    const double *grad_pos;       // dL/dx of the whole graph (2 per node)
+    const uint32_t *eid;          // per record: directed edge id of the graph (2m: node1 -> node2, 2m+1: node2 -> node1)
+    double *hws;                  // HBM variant: packed lower triangles
+    const uint64_t *hws_off;      // per descriptor (doubles)
+    void *g_disp1, *g_disp2;      // n_matches x 18, float or double
+    double *g_sim_dir;            // per directed edge
+    int32_t *status;              // per descriptor
+    unsigned long long *counters; // [0] coordinates held at a bound
+    uint32_t n_matches;
+    int desc_begin, tukey_variant, f64;
+    int scan_all;                 // records in edge-id order (packed classes): no out-edge runs
+};
+
+__host__ __device__ __forceinline__ size_t bwd_tri(int i, int j) { return (size_t)i * (i + 1) / 2 + j; }     // j <= i
+
+template <int T, bool LDS_MATRIX>
+__global__ __launch_bounds__(T) void backward_kernel(const BwdArgs a) {
+    extern __shared__ double bsh[];
+    const int di = a.desc_begin + blockIdx.x, tid = threadIdx.x;
+    const CompDesc d = a.descs[di];
+    const int nv = d.n_var, n = 2 * nv;
+    if (a.infos[di].termination == LFR_TERM_FAILURE) {       // not usable: zero gradient (the outputs were cleared)
+        if (tid == 0) a.status[di] = 1;
+        return;
+    }
+    double *H = LDS_MATRIX ? bsh : a.hws + a.hws_off[di];
+    double *v = LDS_MATRIX ? bsh + bwd_tri(n, 0) : bsh;           // rhs, then the solution
+    double *lval = v + n;                                     // column k's nonzeros: values and rows
+    int *lidx = reinterpret_cast<int *>(lval + n);
+    uint8_t *fr = reinterpret_cast<uint8_t *>(lidx + n);
+    __shared__ int cnt[2];
+    const EdgeRec *E = a.edges + d.edge_off;
+    const uint32_t *ids = a.node_ids + d.node_off;
+
+    // 1. free coordinates, right-hand side, zero matrix
+    unsigned long long n_bound = 0;
+    for (int i = tid; i < n; i += T) {
+        const size_t g = 2 * (size_t)ids[i >> 1] + (i & 1);
+        const bool f = fabs(a.positions[g]) < kBound;
+        fr[i] = f;
+        v[i] = f ? a.grad_pos[g] : 0.0;
+        n_bound += !f;
+    }
+    if (n_bound) atomicAdd(a.counters, n_bound);
+    const size_t nt = bwd_tri(n, 0);
+    for (size_t t = tid; t < nt; t += T) H[t] = 0.0;
+    if (tid == 0) { cnt[0] = 0; cnt[1] = 0; }
+    __syncthreads();
+
+    // 2. assembly: the thread of node l owns rows 2l, 2l+1 (lower triangle: columns of nodes <= l).  The workgroup classes' records
+    // come by source node (out-edges contiguous, NodeInc); the packed classes' in edge-id order: a thread scans them all (<= 320)
+    auto xof = [&](int m, int c) -> double { return m < nv ? a.positions[2 * (size_t)ids[m] + c] : 0.0; };
+    for (int l = tid; l < nv; l += T) {
+        lfr::NodeInc ni = a.node_inc[d.node_off + l];
+        if (a.scan_all) { ni.out_begin = 0; ni.out_count = d.n_edges; ni.in_count = 0; }
+        const double xr = xof(l, 0), xc = xof(l, 1);
+        double hd[3] = {0., 0., 0.};                          // (2l,2l) (2l+1,2l) (2l+1,2l+1)
+        for (uint32_t k = 0; k < ni.out_count; ++k) {         // l -> m (packed classes: and m -> l)
+            const EdgeRec e = E[ni.out_begin + k];
+            const int m = e.dst_kind & 0x7fff, kind = e.dst_kind >> 15;
+            if (a.scan_all && e.src != l) {
+                if (m != l) continue;
+                const int sm = e.src;                         // in-edge sm -> l
+                BwdEdge o;
+                bwd_eval(e, kind, a.tukey_variant, xof(sm, 0), xof(sm, 1), xr, xc, o);
+                double M[2][2], P[2][2];
+                bwd_blocks(o, M, P);
+                hd[0] += M[0][0]; hd[1] += M[1][0]; hd[2] += M[1][1];
+                if (sm < l) {
+#pragma unroll
+                    for (int p = 0; p < 2; ++p)
+#pragma unroll
+                        for (int q = 0; q < 2; ++q) H[bwd_tri(2 * l + p, 2 * sm + q)] -= M[p][0] * P[0][q] + M[p][1] * P[1][q];
+                }
+                continue;
+            }
+            BwdEdge o;
+            bwd_eval(e, kind, a.tukey_variant, xr, xc, xof(m, 0), xof(m, 1), o);
+            double M[2][2], P[2][2];
+            bwd_blocks(o, M, P);
+            double PM[2][2], S[2][2];                         // P^T M, P^T M P - w rho' sum_k r_k d2f_k
+#pragma unroll
+            for (int p = 0; p < 2; ++p)
+#pragma unroll
+                for (int q = 0; q < 2; ++q) PM[p][q] = P[0][p] * M[0][q] + P[1][p] * M[1][q];
+            const double c = o.w * o.rho1;
+#pragma unroll
+            for (int p = 0; p < 2; ++p)
+#pragma unroll
+                for (int q = 0; q < 2; ++q) S[p][q] = PM[p][0] * P[0][q] + PM[p][1] * P[1][q];
+            S[0][0] -= c * (o.r[0] * o.frr[0] + o.r[1] * o.frr[1]);
+            S[1][0] -= c * (o.r[0] * o.frc[0] + o.r[1] * o.frc[1]);
+            S[1][1] -= c * (o.r[0] * o.fcc[0] + o.r[1] * o.fcc[1]);
+            hd[0] += S[0][0]; hd[1] += S[1][0]; hd[2] += S[1][1];
+            if (m < l) {                                      // src-dst block: -P^T M
+#pragma unroll
+                for (int p = 0; p < 2; ++p)
+#pragma unroll
+                    for (int q = 0; q < 2; ++q) H[bwd_tri(2 * l + p, 2 * m + q)] -= PM[p][q];
+            }
+        }
+        for (uint32_t k = 0; k < ni.in_count; ++k) {          // m -> l
+            const EdgeRec e = E[a.in_idx[d.edge_off + ni.in_begin + k]];
+            const int m = e.src, kind = e.dst_kind >> 15;
+            BwdEdge o;
+            bwd_eval(e, kind, a.tukey_variant, xof(m, 0), xof(m, 1), xr, xc, o);
+            double M[2][2], P[2][2];
+            bwd_blocks(o, M, P);
+            hd[0] += M[0][0]; hd[1] += M[1][0]; hd[2] += M[1][1];
+            if (m < l) {                                      // dst-src block: -M P
+#pragma unroll
+                for (int p = 0; p < 2; ++p)
+#pragma unroll
+                    for (int q = 0; q < 2; ++q) H[bwd_tri(2 * l + p, 2 * m + q)] -= M[p][0] * P[0][q] + M[p][1] * P[1][q];
+            }
+        }
+        H[bwd_tri(2 * l, 2 * l)] += hd[0]; H[bwd_tri(2 * l + 1, 2 * l)] += hd[1]; H[bwd_tri(2 * l + 1, 2 * l + 1)] += hd[2];
+        for (int p = 0; p < 2; ++p) {                         // bound coordinates: identity rows and columns
+            const int i = 2 * l + p;
+            for (int j = 0; j <= i; ++j)
+                if (!fr[i] || !fr[j]) H[bwd_tri(i, j)] = (i == j) ? 1.0 : 0.0;
+        }
+    }
+    __syncthreads();
+
+    // 3. LDL^T, right-looking over the nonzeros of each column (D on the diagonal, L below it)
+    bool indefinite = false;
+    for (int k = 0; k < n; ++k) {
+        const double dk = H[bwd_tri(k, k)];
+        if (!(dk > 0.0) || !isfinite(dk)) { indefinite = true; break; }       // (uniform: every thread read the same pivot)
+        const double dinv = 1.0 / dk;
+        int *c = &cnt[k & 1];
+        for (int i = k + 1 + tid; i < n; i += T) {
+            const double x = H[bwd_tri(i, k)];
+            if (x != 0.0) { const int p = atomicAdd(c, 1); lidx[p] = i; lval[p] = x; }
+        }
+        __syncthreads();
+        const int nc = *c;
+        if (tid == 0) cnt[(k + 1) & 1] = 0;
+        for (int t = tid; t < nc * nc; t += T) {
+            const int p = t / nc, q = t - p * nc, i = lidx[p], j = lidx[q];
+            if (j <= i) H[bwd_tri(i, j)] -= lval[p] * (lval[q] * dinv);
+        }
+        for (int p = tid; p < nc; p += T) H[bwd_tri(lidx[p], k)] = lval[p] * dinv;
+        __syncthreads();
+    }
+    if (indefinite) {                                         // zero gradient
+        if (tid == 0) a.status[di] = 2;
+        return;
+    }
+    // 4. v = L^-T D^-1 L^-1 ubar
+    for (int k = 0; k < n; ++k) {
+        const double vk = v[k];
+        for (int i = k + 1 + tid; i < n; i += T) v[i] -= H[bwd_tri(i, k)] * vk;
+        __syncthreads();
+    }
+    for (int i = tid; i < n; i += T) v[i] /= H[bwd_tri(i, i)];
+    __syncthreads();
+    for (int i = n - 1; i > 0; --i) {
+        const double vi = v[i];
+        for (int k = tid; k < i; k += T) v[k] -= H[bwd_tri(i, k)] * vi;
+        __syncthreads();
+    }
+
+    // 5. vector-Jacobian sweep: per record, -d/dtheta [v . grad F_e] scattered to the edge's match row
+    for (uint32_t p = tid; p < d.n_edges; p += T) {
+        const EdgeRec e = E[p];
+        const int s = e.src, m = e.dst_kind & 0x7fff, kind = e.dst_kind >> 15;
+        const double vs0 = s < nv ? v[2 * s] : 0., vs1 = s < nv ? v[2 * s + 1] : 0.;
+        const double vd0 = m < nv ? v[2 * m] : 0., vd1 = m < nv ? v[2 * m + 1] : 0.;
+        BwdEdge o;
+        bwd_eval(e, kind, a.tukey_variant, xof(s, 0), xof(s, 1), xof(m, 0), xof(m, 1), o);
+        const double a0 = vd0 - (1.0 + o.fr[0]) * vs0 - o.fc[0] * vs1;      // a = J v = v_dst - P v_src
+        const double a1 = vd1 - o.fr[1] * vs0 - (1.0 + o.fc[1]) * vs1;
+        const double ra = o.r[0] * a0 + o.r[1] * a1;
+        const uint32_t id = a.eid[d.edge_off + p];
+        if ((id >> 1) >= a.n_matches) continue;               // (cannot happen: every record maps to an edge of the graph)
+        const size_t row = 18 * (size_t)(id >> 1);
+        void *out = (id & 1u) ? a.g_disp1 : a.g_disp2;
+        a.g_sim_dir[id] = -o.rho1 * ra;
+        const double q2 = 2.0 * o.w * o.rho2 * ra, q1 = o.w * o.rho1;
+#pragma unroll
+        for (int i = 0; i < 3; ++i)
+#pragma unroll
+            for (int j = 0; j < 3; ++j) {
+                const double A = o.lr[i] * o.lc[j], B = o.dlr[i] * o.lc[j] * vs0 + o.lr[i] * o.dlc[j] * vs1;
+                const double g0 = q2 * o.r[0] * A + q1 * (A * a0 + o.r[0] * B);
+                const double g1 = q2 * o.r[1] * A + q1 * (A * a1 + o.r[1] * B);
+                const size_t at = row + 2 * (3 * i + j);
+                if (a.f64) { static_cast<double *>(out)[at] = g0; static_cast<double *>(out)[at + 1] = g1; }
+                else { static_cast<float *>(out)[at] = (float)g0; static_cast<float *>(out)[at + 1] = (float)g1; }
+            }
+    }
+    if (tid == 0) a.status[di] = 0;
+}
+
+__global__ void k_bwd_sim(int64_t n_matches, const double *dir, void *out, int f64) {
+    const int64_t m = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (m >= n_matches) return;
+    const double g = dir[2 * m] + dir[2 * m + 1];
+    if (f64) static_cast<double *>(out)[m] = g; else static_cast<float *>(out)[m] = (float)g;
+}
+
+__global__ void k_bwd_words(uint32_t n, const EdgeRec *edges, uint32_t *words) {
+    const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
+    if (p < n) words[p] = (uint32_t)edges[p].src | ((uint32_t)edges[p].dst_kind << 16);
+}
+
+size_t bwd_lds_bytes(int rows, bool lds_matrix) {
+    return (lds_matrix ? bwd_tri(rows, 0) * 8 : 0) + (size_t)rows * (8 + 8 + 4 + 1) + 16;
+}
+
+}  // namespace
+
+struct BwdState {
+    lfr::DevArena slab;
+    uint32_t *d_eid = nullptr;                 // nullptr: the batch's edge_ref
+    double *d_gsim = nullptr, *d_hws = nullptr;
+    uint64_t *d_hws_off = nullptr;
+    int32_t *d_status = nullptr;
+    unsigned long long *d_counters = nullptr;
+    int rows_max[lfr::KC_COUNT] = {0};
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    hipStream_t last_stream = nullptr;
+    int64_t n_calls = 0;
+};
+
+void bwd_free(BwdState *s) {
+    if (!s) return;
+    if (s->last_stream || s->n_calls) (void)hipStreamSynchronize(s->last_stream);
+    if (s->ev0) (void)hipEventDestroy(s->ev0);
+    if (s->ev1) (void)hipEventDestroy(s->ev1);
+    delete s;
+}
+
+namespace {
+
+// record -> directed edge of the graph for batches without edge_ref: the records of a component come in the reference's residual-block
+// order (solve.cc:98-102: by source node, a node's out-edges in insertion order = ascending directed-edge id) or, in the packed
+// classes, in edge-id order - either way the records of one source node ascend in edge id - and a kept edge is kept for its two end
+// points' labels alone, so the k-th record from s to t is the k-th out-edge of s that ends at t.
+int bwd_edge_map(lfr_batch *b, std::vector<uint32_t> &eid) {
+    const lfr::Graph *g = b->graph;
+    const size_t ne = (size_t)b->n_edges;
+    std::vector<uint32_t> words(ne);
+    hipStream_t st = b->ctx->s_main;
+    if (b->n_solves > 0) HIP_TRY(hipStreamWaitEvent(st, b->ev[1], 0));
+    if (ne) {
+        uint32_t *d_words = static_cast<uint32_t *>(b->bwd->slab.take(4 * ne));
+        if (!d_words) { lfr::set_error("backward slab exhausted"); return LFR_ERR_NOMEM; }
+        hipLaunchKernelGGL(k_bwd_words, dim3((unsigned)((ne + 255) / 256)), dim3(256), 0, st, (uint32_t)ne, b->d_edges, d_words);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(words.data(), d_words, 4 * ne, hipMemcpyDeviceToHost, st));
+        HIP_TRY(lfr::stream_wait(st));
+    }
+    std::vector<int64_t> out_off, out_eid;
+    lfr::build_out_csr(*g, out_off, out_eid);
+    std::vector<int64_t> cursor(out_off.begin(), out_off.end() - 1);
+    eid.assign(ne, 0);
+    auto dst_of = [&](int64_t e) -> uint32_t { return (e & 1) ? g->m_node1[e >> 1] : g->m_node2[e >> 1]; };
+    for (const CompDesc &dsc : b->descs) {
+        for (uint32_t p = dsc.edge_off; p < dsc.edge_off + dsc.n_edges; ++p) {
+            const uint32_t sl = words[p] & 0xffffu, tl = (words[p] >> 16) & 0x7fffu;
+            const uint32_t s = b->node_ids[dsc.node_off + sl], t = b->node_ids[dsc.node_off + tl];
+            int64_t &c = cursor[s];
+            while (c < out_off[s + 1] && dst_of(out_eid[c]) != t) ++c;
+            if (c >= out_off[s + 1]) { lfr::set_error("backward: record %u has no edge in the graph", p); return LFR_ERR_ARG; }
+            eid[p] = (uint32_t)out_eid[c++];
+        }
+    }
+    return LFR_OK;
+}
+
+int bwd_setup(lfr_batch *b) {
+    int rc = ensure_mirrors(b);
+    if (rc != LFR_OK) return rc;
+    std::unique_ptr<BwdState> s(new BwdState());
+    const size_t nd = std::max<size_t>(b->descs.size(), 1), ne = std::max<int64_t>(b->n_edges, 1);
+    const size_t M = (size_t)std::max<int64_t>(b->n_graph_matches, 1);
+    std::vector<uint64_t> off(nd, 0);
+    uint64_t hws = 0;
+    for (size_t i = 0; i < b->descs.size(); ++i) {
+        const int cls = b->desc_class[i], rows = 2 * b->descs[i].n_var;
+        s->rows_max[cls] = std::max(s->rows_max[cls], rows);
+        if (cls == lfr::KC_GLOBAL) {
+            if (rows > kBwdMaxRows) { lfr::set_error("backward: a component of %d rows exceeds the dense backward's %d", rows, kBwdMaxRows); return LFR_ERR_UNSUPPORTED; }
+            off[i] = hws; hws += bwd_tri(rows, 0);
+        }
+    }
+    const bool map_on_host = b->d_edge_ref == nullptr;
+    const size_t bytes = (map_on_host ? 8 * ne : 0) + 16 * M + 8 * hws + 8 * nd + 4 * nd + 64 + ((size_t)1 << 16);
+    if (!s->slab.init(b->ctx, bytes)) return LFR_ERR_NOMEM;
+    s->d_gsim = s->slab.take_n<double>(2 * M);
+    s->d_hws = s->slab.take_n<double>(std::max<uint64_t>(hws, 1));
+    s->d_hws_off = s->slab.take_n<uint64_t>(nd);
+    s->d_status = s->slab.take_n<int32_t>(nd);
+    s->d_counters = s->slab.take_n<unsigned long long>(8);
+    if (!s->d_gsim || !s->d_hws || !s->d_hws_off || !s->d_status || !s->d_counters) { lfr::set_error("backward slab exhausted"); return LFR_ERR_NOMEM; }
+    HIP_TRY(hipEventCreate(&s->ev0)); HIP_TRY(hipEventCreate(&s->ev1));
+    hipStream_t st = b->ctx->s_main;
+    HIP_TRY(hipMemcpyAsync(s->d_hws_off, off.data(), 8 * nd, hipMemcpyHostToDevice, st));
+    b->bwd = s.release();
+    if (map_on_host) {
+        std::vector<uint32_t> eid;
+        if (!b->graph) { lfr::set_error("backward: the batch has no graph"); return LFR_ERR_ARG; }
+        if ((rc = bwd_edge_map(b, eid)) != LFR_OK) { bwd_free(b->bwd); b->bwd = nullptr; return rc; }
+        b->bwd->d_eid = b->bwd->slab.take_n<uint32_t>(ne);
+        if (!b->bwd->d_eid) { bwd_free(b->bwd); b->bwd = nullptr; lfr::set_error("backward slab exhausted"); return LFR_ERR_NOMEM; }
+        if (!eid.empty()) HIP_TRY(hipMemcpyAsync(b->bwd->d_eid, eid.data(), 4 * eid.size(), hipMemcpyHostToDevice, st));
+    }
+    HIP_TRY(lfr::stream_wait(st));
+    HIP_TRY(hipFuncSetAttribute((const void *)backward_kernel<kBwdThreads, true>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                (int)bwd_lds_bytes(lfr::kBlockMaxRows, true)));
+    HIP_TRY(hipFuncSetAttribute((const void *)backward_kernel<kBwdThreads, false>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                (int)bwd_lds_bytes(kBwdMaxRows, false)));
+    return LFR_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int lfr_batch_positions_to_device(lfr_batch *b, double *dst_device, void *hip_stream) {
+    if (!b || !dst_device) { lfr::set_error("bad argument"); return LFR_ERR_ARG; }
+    HIP_TRY(hipSetDevice(b->device));
+    hipStream_t st = (hipStream_t)hip_stream;
+    if (b->n_solves > 0) HIP_TRY(hipStreamWaitEvent(st, b->ev[1], 0));        // end of the latest solve, whatever stream it ran on
+    HIP_TRY(hipMemcpyAsync(dst_device, b->d_positions, sizeof(double) * 2 * (size_t)b->n_graph_nodes, hipMemcpyDeviceToDevice, st));
+    return LFR_OK;
+}
+
+int lfr_batch_backward(lfr_batch *b, const double *grad_positions_device, void *grad_disp1_device, void *grad_disp2_device,
+                       void *grad_sim_device, int flags, void *hip_stream, lfr_backward_stats *stats) {
+    if (!b || !grad_positions_device || !grad_disp1_device || !grad_disp2_device || !grad_sim_device || (flags & ~LFR_BACKWARD_F64)) {
+        lfr::set_error("bad argument"); return LFR_ERR_ARG;
+    }
+    if (b->n_solves == 0) { lfr::set_error("lfr_batch_backward: the batch has not been solved"); return LFR_ERR_ARG; }
+    HIP_TRY(hipSetDevice(b->device));
+    if (!b->bwd) { const int rc = bwd_setup(b); if (rc != LFR_OK) return rc; }
+    BwdState &s = *b->bwd;
+    hipStream_t st = (hipStream_t)hip_stream;
+    const int f64 = (flags & LFR_BACKWARD_F64) ? 1 : 0;
+    const size_t M = (size_t)b->n_graph_matches, elt = f64 ? 8 : 4;
+    HIP_TRY(hipStreamWaitEvent(st, b->ev[1], 0));                               // the latest solve's positions and termination codes
+    HIP_TRY(hipEventRecord(s.ev0, st));
+    if (b->fused && b->packed_edges)         // the packed records have not been written yet: write them (the next solve would write the same bytes)
+        hipLaunchKernelGGL(k_materialize_records, dim3((unsigned)(((uint64_t)5 * b->packed_edges + 255) / 256)), dim3(256), 0, st, b->packed_edges,
+                           b->d_edge_ref, b->d_edge_word, b->dev_hold->graph->flow_row, b->dev_hold->graph->disp1, b->dev_hold->graph->disp2,
+                           b->dev_hold->graph->sim, reinterpret_cast<uint4 *>(b->d_edges));
+    if (M) {
+        HIP_TRY(hipMemsetAsync(grad_disp1_device, 0, 18 * M * elt, st));
+        HIP_TRY(hipMemsetAsync(grad_disp2_device, 0, 18 * M * elt, st));
+        HIP_TRY(hipMemsetAsync(s.d_gsim, 0, 16 * M, st));
+    }
+    HIP_TRY(hipMemsetAsync(s.d_counters, 0, 64, st));
+    BwdArgs a;
+    a.descs = b->d_descs; a.edges = b->d_edges; a.node_ids = b->d_node_ids; a.node_inc = b->d_node_inc; a.in_idx = b->d_in_idx;
+    a.positions = b->d_positions; a.infos = b->d_infos; a.grad_pos = grad_positions_device;
+    a.eid = s.d_eid ? s.d_eid : b->d_edge_ref;
+    a.hws = s.d_hws; a.hws_off = s.d_hws_off; a.g_disp1 = grad_disp1_device; a.g_disp2 = grad_disp2_device; a.g_sim_dir = s.d_gsim;
+    a.status = s.d_status; a.counters = s.d_counters; a.tukey_variant = b->tukey_variant; a.f64 = f64;
+    a.n_matches = (uint32_t)M;
+    // packed classes (<= 32 rows): one wave each; LDS classes: 256 threads, matrix in LDS; above 192 rows: matrix in HBM
+    {
+        a.desc_begin = b->class_begin[0];
+        const int n = b->class_begin[lfr::KC_BLOCK] - a.desc_begin;
+        a.scan_all = 1;
+        if (n > 0)
+            hipLaunchKernelGGL((backward_kernel<kBwdThreadsSmall, true>), dim3(n), dim3(kBwdThreadsSmall), bwd_lds_bytes(32, true), st, a);
+    }
+    a.scan_all = 0;
+    for (int cls = lfr::KC_BLOCK; cls < lfr::KC_COUNT; ++cls) {
+        a.desc_begin = b->class_begin[cls];
+        const int n = b->class_begin[cls + 1] - a.desc_begin, rows = std::max(s.rows_max[cls], 2);
+        if (n <= 0) continue;
+        if (cls == lfr::KC_GLOBAL)
+            hipLaunchKernelGGL((backward_kernel<kBwdThreads, false>), dim3(n), dim3(kBwdThreads), bwd_lds_bytes(rows, false), st, a);
+        else
+            hipLaunchKernelGGL((backward_kernel<kBwdThreads, true>), dim3(n), dim3(kBwdThreads), bwd_lds_bytes(rows, true), st, a);
+    }
+    if (M) hipLaunchKernelGGL(k_bwd_sim, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, st, (int64_t)M, s.d_gsim, grad_sim_device, f64);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(s.ev1, st));
+    s.last_stream = st;
+    ++s.n_calls;
+    if (stats) {
+        HIP_TRY(hipEventSynchronize(s.ev1));
+        std::vector<int32_t> status(b->descs.size());
+        unsigned long long cnt[8];
+        if (!status.empty()) HIP_TRY(hipMemcpyAsync(status.data(), s.d_status, 4 * status.size(), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(cnt, s.d_counters, sizeof(cnt), hipMemcpyDeviceToHost, st));
+        HIP_TRY(lfr::stream_wait(st));
+        memset(stats, 0, sizeof(*stats));
+        for (int32_t v : status) {
+            if (v == 0) ++stats->n_differentiated;
+            else if (v == 1) ++stats->n_not_usable;
+            else ++stats->n_indefinite;
+        }
+        stats->n_bound_coordinates = (int64_t)cnt[0];
+        float ms = 0.f;
+        HIP_TRY(hipEventElapsedTime(&ms, s.ev0, s.ev1));
+        stats->kernel_ms = ms;
+    }
+    return LFR_OK;
+}
+
+int64_t lfr_batch_backward_status(lfr_batch *b, int32_t *status) {
+    if (!b || !b->bwd || !b->bwd->n_calls) { lfr::set_error("lfr_batch_backward_status: no backward has run on this batch"); return LFR_ERR_ARG; }
+    HIP_TRY(hipSetDevice(b->device));
+    HIP_TRY(hipEventSynchronize(b->bwd->ev1));
+    const size_t n = b->descs.size();
+    if (status && n) {
+        HIP_TRY(hipMemcpyAsync(status, b->bwd->d_status, 4 * n, hipMemcpyDeviceToHost, b->bwd->last_stream));
+        HIP_TRY(lfr::stream_wait(b->bwd->last_stream));
+    }
+    return (int64_t)n;
+}
+
+}  // extern "C"

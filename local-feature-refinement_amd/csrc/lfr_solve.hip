@@ -3273,6 +3273,8 @@ static inline void host_trace(const char *what) {
 constexpr size_t kProfWords = 8 * lfr::KC_COUNT + 8 + 64;  // phase counters of -DLFR_PROFILE_PHASES + 16 32-bit class queues + -DLFR_PROFILE_FACTOR (16 per workgroup class)
 
 constexpr uint32_t kPackedEventsAliased = 1u << 31;     // ev_recorded: the packed launch is timed by the solve's own pair of events
+struct BwdState;                                        // lfr_backward_impl.hpp
+void bwd_free(BwdState *s);
 struct lfr_batch {
     int device = 0;
     lfr::DevCtx *ctx = nullptr;
@@ -3346,9 +3348,14 @@ struct lfr_batch {
     double h2d_ms = 0.0;             // upload (host-assembled) or device assembly incl. waiting for the flows
     std::vector<CompInfoDev> infos;      // last downloaded
     bool infos_valid = false;
+    // implicit-gradient backward (lfr_backward_impl.hpp): everything is set up on the first lfr_batch_backward
+    const lfr::Graph *graph = nullptr;   // for the record -> directed-edge map of batches without edge_ref
+    int64_t n_graph_matches = 0;
+    BwdState *bwd = nullptr;
 
     lfr_batch() { for (auto &e : ev_ring) e = nullptr; }
     ~lfr_batch() {
+        bwd_free(bwd);
         if (ctx) {
             (void)hipSetDevice(device);
             if (n_solves > 0) (void)hipStreamSynchronize(last_stream);      // nothing may still use the slab
@@ -4125,6 +4132,7 @@ int lfr_batch_create(const lfr_problem *ph, int device, int shard_rank, int shar
     b->device = device; b->ctx = ctx; b->tukey_variant = tukey_variant; b->shard_world = shard_world;
     { const char *e = getenv("LFR_SERIAL_CLASSES"); b->serial = e && e[0] == '1'; }
     b->n_graph_nodes = p.g->n_nodes();
+    b->graph = p.g; b->n_graph_matches = p.g->n_matches();
     int rc = p.host_batch ? create_from_host(b.get(), p, shard_rank, shard_world) : create_on_device(b.get(), p, shard_rank, shard_world);
     if (rc != LFR_OK) return rc;
     if ((rc = finish_workspace(b.get(), p)) != LFR_OK) return rc;
@@ -4844,3 +4852,6 @@ int lfr_solve_graph_hip_multi(const lfr_graph *g, const int *devices, int n_devi
 }
 
 }  // extern "C"
+
+// implicit-gradient backward pass (lfr_batch_backward)
+#include "lfr_backward_impl.hpp"

@@ -1,0 +1,96 @@
+"""PyTorch autograd through the batched LM solve: the two-view network's flows (and the similarities) in, refined positions out, and
+the implicit-function-theorem gradient back (lfr_batch_backward, include/lfr.h).
+
+    pos, node_image, node_feature = refine(disp1, disp2, sim, image_names=..., pair_img1=..., pair_img2=..., pair_off=...,
+                                           feat1=..., feat2=...)
+    loss(pos).backward()        # fills disp1.grad, disp2.grad, sim.grad
+
+One device, first-order only (the backward is not itself differentiable).  The graph stage (tracks, roots, components, the cut) is
+discrete and the box's active set piecewise constant: the gradient holds them fixed.
+"""
+import numpy as np
+import torch
+from torch.autograd.function import once_differentiable
+
+from . import capi
+from .synthetic import MatchArrays
+
+
+def _kept_rows(pair_img1, pair_img2, pair_off, image_names, banned):
+    """Input rows of the matches the graph keeps (pairs touching a banned image are skipped, solve.cc:444-446), in graph order."""
+    if not banned:
+        return None
+    bad = np.array([n in set(banned) for n in image_names], bool)
+    keep = ~(bad[pair_img1] | bad[pair_img2])
+    rows = [np.arange(pair_off[p], pair_off[p + 1], dtype=np.int64) for p in np.nonzero(keep)[0]]
+    return np.concatenate(rows) if rows else np.zeros(0, np.int64)
+
+
+class _Refine(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, disp1, disp2, sim, meta):
+        device = disp1.device
+        d1 = disp1.detach().to(torch.float32).reshape(-1, 18).contiguous()
+        d2 = disp2.detach().to(torch.float32).reshape(-1, 18).contiguous()
+        ma = MatchArrays(image_names=list(meta["image_names"]), facts=meta["facts"], pair_img1=meta["pair_img1"],
+                         pair_img2=meta["pair_img2"], pair_off=meta["pair_off"], feat1=meta["feat1"], feat2=meta["feat2"],
+                         sim=sim.detach().to(torch.float32).cpu().numpy(), disp1=None, disp2=None)
+        dev = device.index if device.index is not None else torch.cuda.current_device()
+        with torch.cuda.device(dev):
+            stream = torch.cuda.current_stream(device).cuda_stream
+            # the library reads the flows on its own streams: they must be complete before the graph takes them
+            torch.cuda.current_stream(device).synchronize()
+            g = capi.Graph.from_device_flows(ma, d1.data_ptr(), d2.data_ptr(), device=dev, banned=tuple(meta["banned"]))
+            p = capi.Problem(g, device_graph_stage=dev)
+            b = capi.Batch(p, dev, tukey_variant=meta["tukey_variant"])      # (gathers its records: d1 / d2 may go after this)
+            b.solve(stream=stream, want_stats=False)
+            pos = torch.empty((g.n_nodes, 2), dtype=torch.float64, device=device)
+            b.positions_to(pos, stream=stream)
+        node_image, node_feature = g.nodes()
+        ctx.batch = b
+        ctx.meta = meta
+        ctx.n_in = (disp1.shape, disp2.shape, sim.shape, disp1.dtype, disp2.dtype, sim.dtype)
+        return pos, node_image, node_feature
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_pos, *_):
+        b, meta = ctx.batch, ctx.meta
+        s1, s2, ss, t1, t2, ts = ctx.n_in
+        if grad_pos is None:
+            return None, None, None, None
+        g1, g2, gs = b.backward(grad_pos, f64=False)
+        rows = meta["kept_rows"]
+        if rows is not None:        # back to the caller's rows (matches of banned pairs get 0)
+            idx = torch.as_tensor(rows, device=g1.device)
+            f1 = torch.zeros((ss[0], 18), dtype=g1.dtype, device=g1.device)
+            f2 = torch.zeros_like(f1)
+            fs = torch.zeros((ss[0],), dtype=gs.dtype, device=gs.device)
+            f1[idx], f2[idx], fs[idx] = g1, g2, gs
+            g1, g2, gs = f1, f2, fs
+        return (g1.reshape(s1).to(t1) if ctx.needs_input_grad[0] else None,
+                g2.reshape(s2).to(t2) if ctx.needs_input_grad[1] else None,
+                gs.reshape(ss).to(device=gs.device, dtype=ts) if ctx.needs_input_grad[2] else None, None)
+
+
+def refine(disp1, disp2, sim, *, image_names, pair_img1, pair_img2, pair_off, feat1, feat2, image_facts=None, banned=(),
+           tukey_variant="ceres1"):
+    """Multi-view refinement of the matches as a differentiable function of the flows and similarities.
+
+    disp1, disp2: [n_matches, 18] (or [n_matches, 9, 2]) float32 tensors on one HIP device - disp2 = flow image1 -> image2, disp1 =
+    flow image2 -> image1 (lfr_graph_from_arrays); sim: [n_matches] similarities (any device); the rest as lfr_graph_from_arrays.
+    Returns (positions, node_image, node_feature): [n_nodes, 2] float64 device positions (di, dj per node, the solver's unit) and the
+    node -> (image index, feature index) map as numpy arrays.  Gradients reach disp1, disp2 and sim; the matches of banned pairs
+    get 0."""
+    pair_img1 = np.ascontiguousarray(pair_img1, np.int32)
+    pair_img2 = np.ascontiguousarray(pair_img2, np.int32)
+    pair_off = np.ascontiguousarray(pair_off, np.int64)
+    facts = np.ones(len(image_names), np.float32) if image_facts is None else np.ascontiguousarray(image_facts, np.float32)
+    if not disp1.is_cuda or disp2.device != disp1.device:
+        raise ValueError("refine: disp1 and disp2 must be on the same HIP device")
+    meta = {"image_names": list(image_names), "facts": facts, "pair_img1": pair_img1, "pair_img2": pair_img2, "pair_off": pair_off,
+            "feat1": np.ascontiguousarray(feat1, np.uint32), "feat2": np.ascontiguousarray(feat2, np.uint32),
+            "banned": tuple(banned), "tukey_variant": tukey_variant,
+            "kept_rows": _kept_rows(pair_img1, pair_img2, pair_off, list(image_names), tuple(banned))}
+    pos, node_image, node_feature = _Refine.apply(disp1, disp2, sim, meta)
+    return pos, node_image, node_feature

@@ -49,6 +49,18 @@ class SolveStats(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+class BackwardStats(C.Structure):
+    _fields_ = [(n, C.c_int64) for n in ("n_differentiated", "n_not_usable", "n_indefinite", "n_bound_coordinates")] + \
+        [("kernel_ms", C.c_double)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+BACKWARD_F64 = 1                # LFR_BACKWARD_F64
+BACKWARD_OK, BACKWARD_NOT_USABLE, BACKWARD_INDEFINITE = 0, 1, 2      # lfr_batch_backward_status
+
+
 _lib = None
 
 
@@ -106,6 +118,9 @@ def lib():
         "lfr_batch_positions_view_f32": (C.c_int, [vp, pp]),
         "lfr_batch_timing": (C.c_int, [vp, C.c_int, C.POINTER(C.c_double), vp, vp]),
         "lfr_batch_component_info": (i64, [vp, vp, vp, vp, vp, vp, vp]),
+        "lfr_batch_positions_to_device": (C.c_int, [vp, vp, vp]),
+        "lfr_batch_backward": (C.c_int, [vp, vp, vp, vp, vp, C.c_int, vp, C.POINTER(BackwardStats)]),
+        "lfr_batch_backward_status": (i64, [vp, vp]),
         "lfr_batch_spin_timeouts": (i64, [vp]),
         "lfr_batch_team_runs": (i64, [vp]),
         "lfr_batch_team_fallbacks": (i64, [vp]),
@@ -138,7 +153,7 @@ EXPORTS = ["lfr_version", "lfr_last_error", "lfr_graph_from_files", "lfr_graph_f
            "lfr_graph_num_images", "lfr_graph_get_nodes", "lfr_graph_image_name", "lfr_graph_image_fact",
            "lfr_write_matching_file", "lfr_problem_build", "lfr_problem_build_labels", "lfr_problem_build_hip", "lfr_problem_free", "lfr_problem_get_stats",
            "lfr_problem_get_labels", "lfr_problem_shard_components", "lfr_hip_warmup", "lfr_batch_create", "lfr_batch_free", "lfr_batch_solve",
-           "lfr_batch_download", "lfr_batch_timing", "lfr_batch_spin_timeouts", "lfr_batch_team_runs", "lfr_batch_team_fallbacks", "lfr_debug_occupy", "lfr_batch_tree_stats", "lfr_batch_component_info", "lfr_solve_hip", "lfr_solve_hip_multi", "lfr_solve_graph_hip_multi", "lfr_write_solution", "lfr_apply_displacements"]
+           "lfr_batch_download", "lfr_batch_timing", "lfr_batch_spin_timeouts", "lfr_batch_team_runs", "lfr_batch_team_fallbacks", "lfr_debug_occupy", "lfr_batch_tree_stats", "lfr_batch_component_info", "lfr_batch_positions_to_device", "lfr_batch_backward", "lfr_batch_backward_status", "lfr_solve_hip", "lfr_solve_hip_multi", "lfr_solve_graph_hip_multi", "lfr_write_solution", "lfr_apply_displacements"]
 
 
 def _check(rc):
@@ -555,6 +570,52 @@ class Batch:
             return np.zeros((0, 2), np.float32)
         buf = (C.c_float * (2 * n)).from_address(p.value)
         return np.frombuffer(buf, dtype=np.float32).reshape(n, 2)
+
+    def positions_to(self, tensor, stream=None):
+        """Stream-ordered device copy of the latest solve's positions into `tensor` ([n_nodes, 2] float64, contiguous, on the batch's
+        device); stream: a hipStream_t as int, None = torch's current stream.  Returns `tensor`."""
+        import torch
+        n = self.problem.graph.n_nodes
+        if tensor.dtype != torch.float64 or not tensor.is_cuda or not tensor.is_contiguous() or tensor.numel() != 2 * n:
+            raise ValueError("positions_to: need a contiguous [%d, 2] float64 device tensor" % n)
+        if stream is None:
+            stream = torch.cuda.current_stream(tensor.device).cuda_stream
+        if n:
+            _check(lib().lfr_batch_positions_to_device(self._h, C.c_void_p(tensor.data_ptr()), C.c_void_p(stream) if stream else None))
+        return tensor
+
+    def backward(self, grad_positions, f64=False, stream=None, want_stats=False):
+        """Implicit gradient of the latest solve (lfr_batch_backward, include/lfr.h): grad_positions = dL/dx, [n_nodes, 2] float64 on
+        the batch's device.  Returns (grad_disp1, grad_disp2, grad_sim) as device tensors in the graph's match layout ([n_matches, 18],
+        [n_matches, 18], [n_matches]; float32, or float64 with f64=True), and the stats dict when want_stats (that waits)."""
+        import torch
+        n = self.problem.graph.n_nodes
+        m = self.problem.graph.n_edges // 2
+        g = grad_positions.detach().to(dtype=torch.float64).contiguous()
+        if not g.is_cuda or g.numel() != 2 * n:
+            raise ValueError("backward: need a [%d, 2] float64 device tensor" % n)
+        dt = torch.float64 if f64 else torch.float32
+        g1 = torch.empty((m, 18), dtype=dt, device=g.device)
+        g2 = torch.empty((m, 18), dtype=dt, device=g.device)
+        gs = torch.empty((m,), dtype=dt, device=g.device)
+        if stream is None:
+            stream = torch.cuda.current_stream(g.device).cuda_stream
+        st = BackwardStats()
+        _check(lib().lfr_batch_backward(self._h, C.c_void_p(g.data_ptr() or 1), C.c_void_p(g1.data_ptr() or 1), C.c_void_p(g2.data_ptr() or 1), C.c_void_p(gs.data_ptr() or 1),
+                                        BACKWARD_F64 if f64 else 0, C.c_void_p(stream) if stream else None,
+                                        C.byref(st) if want_stats else None))
+        if want_stats:
+            return g1, g2, gs, st.as_dict()
+        return g1, g2, gs
+
+    def backward_status(self):
+        """Per component (order of component_info) of the latest backward: BACKWARD_OK / _NOT_USABLE / _INDEFINITE."""
+        n = lib().lfr_batch_component_info(self._h, None, None, None, None, None, None)
+        out = np.zeros(max(n, 0), np.int32)
+        rc = lib().lfr_batch_backward_status(self._h, _ptr(out))
+        if rc < 0:
+            _check(rc)
+        return out
 
     def tree_stats(self):
         """Per component (order of component_info): columns / tiles / 16x16x16 updates per factorization / levels / sweep items of the
