@@ -759,6 +759,86 @@ using f64x4 = __attribute__((ext_vector_type(4))) double;
 __device__ __forceinline__ double uni(double v) {
     return __hiloint2double(__builtin_amdgcn_readfirstlane(__double2hiint(v)), __builtin_amdgcn_readfirstlane(__double2loint(v)));
 }
+
+// The samples of one line search: ls_next_step_* take them by reference, so they live in scratch, apart from LmControl's SGPRs.
+struct LmSearch {
+    LsSample initial, previous, current;
+    __device__ __forceinline__ void set_gradient(double g) { current.gradient = g; current.gradient_valid = isfinite(g); }
+};
+
+// Ceres' trust-region control flow, decision for decision, stated once for solve_component and solve_tree_component.  The kernels
+// keep the vector work (sweeps, damping, factorization, reductions) and feed the scalars in; every member is wave-uniform.
+struct LmControl {
+    enum Verdict { STOP, ACCEPT, REJECT };
+    double cost, gmax, x_norm = 0.0, radius = kInitialRadius, decrease_factor = 2.0;
+    bool reuse_diagonal = false, step_successful = true, matrix_valid = true;
+    int n_invalid = 0, iteration = 0, term = LFR_TERM_CONVERGENCE;
+    int n_successful = 0, n_ls_evals = 0, n_cand = 0, exec_passes = 1;
+
+    // the tests at the top of an iteration; false: the solve is over (term says how)
+    __device__ __forceinline__ bool begin_iteration() {
+        if (iteration >= kMaxIterations) { term = LFR_TERM_NO_CONVERGENCE; return false; }
+        if (step_successful && gmax <= kGradientTol) return false;
+        if (radius <= kMinRadius) return false;
+        ++iteration;
+        step_successful = false;
+        return true;
+    }
+    // the LM diagonal from the Jacobi scaling s and the diagonal of J^T J, and the damping D / s of the unscaled system
+    __device__ __forceinline__ static double lm_diag(double scale, double adiag) { return fmin(fmax(scale * scale * adiag, kMinLmDiag), kMaxLmDiag); }
+    __device__ __forceinline__ double lm_d(double diag, double scale) const { return sqrt(diag / radius) / scale; }
+    __device__ __forceinline__ void shrink_radius() {
+        radius = uni(radius / decrease_factor);
+        decrease_factor = uni(decrease_factor * 2.0);
+    }
+    // a step that is not finite or does not decrease the model; true: the component FAILS
+    __device__ __forceinline__ bool invalid_step() {
+        if (++n_invalid >= kMaxInvalid) { term = LFR_TERM_FAILURE; return true; }
+        shrink_radius();
+        return false;
+    }
+    // a valid step: the projected Armijo search along it starts at alpha = 0
+    __device__ __forceinline__ LmSearch start_search(double g_dot_delta) {
+        n_invalid = 0;
+        LmSearch ls;
+        ls.initial = LsSample{0.0, cost, g_dot_delta, true, true};
+        ls.previous = LsSample{0, 0, 0, false, false};
+        return ls;
+    }
+    // the cost at alpha into ls.current; true: sufficient decrease.  Else the kernel may set_gradient, then ls_next_step, previous = current
+    __device__ __forceinline__ bool sample(LmSearch &ls, double alpha, double cost_c) {
+        ++exec_passes; ++n_ls_evals;
+        ls.current = LsSample{alpha, cost_c, 0.0, isfinite(cost_c), false};
+        return ls.current.value_valid && !(cost_c > cost + kLsSufficientDecrease * ls.initial.gradient * alpha);
+    }
+    // the candidate (the search's point, else the full step): tolerances, then step quality.  ACCEPT: the kernel makes it x, sets x_norm, gmax
+    __device__ __forceinline__ Verdict judge(double step_norm, double cost_c, double model_cost_change) {
+        ++n_cand;
+        const double cost_cand = uni(isfinite(cost_c) ? cost_c : DBL_MAX);
+        if (step_norm <= kParameterTol * (x_norm + kParameterTol)) return STOP;
+        const double cost_change = cost - cost_cand;
+        if (fabs(cost_change) <= kFunctionTol * cost) return STOP;
+        const double rel = cost_change / model_cost_change;
+        if (!(rel > kMinRelDecrease)) { shrink_radius(); return REJECT; }
+        cost = cost_cand;
+        matrix_valid = true;
+        step_successful = true;
+        ++n_successful;
+        const double t = 2.0 * rel - 1.0;
+        radius = uni(fmin(kMaxRadius, radius / fmax(1.0 / 3.0, 1.0 - t * t * t)));
+        decrease_factor = 2.0;
+        reuse_diagonal = false;
+        return ACCEPT;
+    }
+    __device__ __forceinline__ CompInfoDev info() const {
+        CompInfoDev inf;
+        inf.iterations = iteration; inf.termination = term; inf.n_successful = n_successful;
+        inf.n_ls_evals = n_ls_evals; inf.n_cand_evals = n_cand; inf.exec_passes = exec_passes;
+        inf.final_cost = cost;
+        return inf;
+    }
+};
+
 template <int kBlockThreads>
 __device__ __forceinline__ double block_sum(double v, BlockShared &sh) {
     v = wave_sum(v);
@@ -1222,7 +1302,7 @@ __device__ __forceinline__ void back_substitute_lds(const double *Mat, const dou
     }
 }
 
-// vectors live in LDS for both variants: 8 vectors of n doubles
+// vectors and the packed matrix live in dynamic LDS
 // (two waves per SIMD = 256 registers each, VGPRs + the MFMA accumulators: what the 4 / 2 workgroups per CU of the two smaller
 // LDS classes need; without the attribute the allocator takes 264)
 template <int kBlockThreads>
@@ -1237,9 +1317,6 @@ __device__ __forceinline__ void solve_component(const KernelArgs &a, const int m
     const int tv = a.tukey_variant;
     const EdgeRec *edges = a.edges + d.edge_off;
 
-    // LDS variant: vectors + packed matrix in dynamic LDS.  HBM variant: packed matrix, then the
-    // vectors, in this component's workspace (L2-resident); no dynamic LDS at all, so the row count
-    // is only bounded by the 32767-node limit of the batch format.
     double *Mat = dyn + 2 * (size_t)(max_rows + 2) + 7 * (size_t)max_rows;
     double *vx = dyn;                 // x (n + 2, zero slot at n)
     double *vxc = vx + max_rows + 2;  // trial point
@@ -1247,7 +1324,7 @@ __device__ __forceinline__ void solve_component(const KernelArgs &a, const int m
     double *vgn = vg + max_rows;      // gradient at trial point
     double *vscale = vgn + max_rows;
     double *vdiag = vscale + max_rows;
-    // rhs -> step.  LDS variant: row n of the matrix - the right-hand side rides through the factorization as one more row
+    // rhs -> step: row n of the matrix - the right-hand side rides through the factorization as one more row
     // (LDL^T of [[A, g], [g^T, .]]: the unscaled entries of that row come out as L^-1 g), so the forward substitution, n
     // dependent steps per solve, is gone; the (n, n) entry is never used.
     double *vstep = Mat + tri(n, 0);
@@ -1581,8 +1658,7 @@ __device__ __forceinline__ void solve_component(const KernelArgs &a, const int m
         return sweep_scratch(xv, gout, want_matrix);
     };
 
-    int exec_passes = 1;
-    double cost = uni(sweep(vx, vg, true));          // (uni: the scalars of this loop are wave-uniform - SGPRs, not spilled VGPRs)
+    const double cost0 = uni(sweep(vx, vg, true));   // (uni: the scalars of this loop are wave-uniform - SGPRs, not spilled VGPRs)
     PROF_MARK(0);                                     // 0: sweeps (evaluate + owner-computes assembly)
     for (int i = tid; i < n; i += kBlockThreads) vscale[i] = 1.0 / (1.0 + sqrt(vadiag[i]));
     __syncthreads();
@@ -1591,24 +1667,14 @@ __device__ __forceinline__ void solve_component(const KernelArgs &a, const int m
         for (int i = tid; i < n; i += kBlockThreads) m = fmax(m, fabs(xv[i] - clampb(xv[i] - gv[i])));
         return block_max<kBlockThreads>(m, sh);
     };
-    double gmax = grad_max(vx, vg);
-    double x_norm = 0.0, radius = kInitialRadius, decrease_factor = 2.0;
-    bool reuse_diagonal = false, step_successful = true, matrix_valid = true;
-    int n_invalid = 0, iteration = 0, term = LFR_TERM_CONVERGENCE;
-    int n_successful = 0, n_ls_evals = 0, n_cand = 0;
+    LmControl lm{cost0, grad_max(vx, vg)};
 
-    for (;;) {
-        if (iteration >= kMaxIterations) { term = LFR_TERM_NO_CONVERGENCE; break; }
-        if (step_successful && gmax <= kGradientTol) break;
-        if (radius <= kMinRadius) break;
-        ++iteration;
-        step_successful = false;
-
+    while (lm.begin_iteration()) {
         PROF_MARK(4);                                 // 4: bookkeeping
-        if (!matrix_valid) {           // the factorization of a rejected step overwrote J^T J: re-assemble
+        if (!lm.matrix_valid) {        // the factorization of a rejected step overwrote J^T J: re-assemble
             sweep(vx, vg, true);
-            ++exec_passes;
-            matrix_valid = true;
+            ++lm.exec_passes;
+            lm.matrix_valid = true;
             PROF_MARK(0);
         }
         // ---- the damped system.  Ceres solves (S A S + D^2) y = S g with the Jacobi scaling S; that is (A + S^-1 D^2 S^-1) (S y) = g: the
@@ -1616,14 +1682,14 @@ __device__ __forceinline__ void solve_component(const KernelArgs &a, const int m
         // (the packed kernel has always done this; rounds 1-2 scaled every entry here: 3 % of a 190-row component, 19 % of a sparse
         // 1000-row one whose tiles live in HBM) ----
         for (int i = tid; i < n; i += kBlockThreads) {
-            if (!reuse_diagonal) vdiag[i] = fmin(fmax(vscale[i] * vscale[i] * vadiag[i], kMinLmDiag), kMaxLmDiag);
-            const double di = sqrt(vdiag[i] / radius) / vscale[i];           // D / s
+            if (!lm.reuse_diagonal) vdiag[i] = LmControl::lm_diag(vscale[i], vadiag[i]);
+            const double di = lm.lm_d(vdiag[i], vscale[i]);
             vD[i] = di;
             vstep[i] = vg[i];
             Mat[tri(i, i)] += di * di;
         }
-        reuse_diagonal = true;
-        matrix_valid = false;
+        lm.reuse_diagonal = true;
+        lm.matrix_valid = false;
         __syncthreads();
         PROF_MARK(5);                                 // 5: damping
         double *vinv = vgn;            // free until the line search
@@ -1652,12 +1718,9 @@ __device__ __forceinline__ void solve_component(const KernelArgs &a, const int m
             valid = bad == 0.0 && model_cost_change > 0.0;
         }
         if (!valid) {
-            if (++n_invalid >= kMaxInvalid) { term = LFR_TERM_FAILURE; break; }
-            radius = uni(radius / decrease_factor);
-            decrease_factor = uni(decrease_factor * 2.0);
+            if (lm.invalid_step()) break;
             continue;
         }
-        n_invalid = 0;
         double gd_part = 0.0, dm_part = 0.0;
         for (int i = tid; i < n; i += kBlockThreads) {
             const double dl = -vstep[i];
@@ -1672,27 +1735,22 @@ __device__ __forceinline__ void solve_component(const KernelArgs &a, const int m
         double alpha = 1.0, cost_c = 0.0;
         bool ls_ok = false;
         {
-            LsSample initial{0.0, cost, g_dot_delta, true, true}, previous{0, 0, 0, false, false}, current;
-            int n_iter = 0;
-            for (;;) {
+            LmSearch ls = lm.start_search(g_dot_delta);
+            for (int n_iter = 0;;) {
                 for (int i = tid; i < n; i += kBlockThreads) vxc[i] = clampb(__dadd_rn(vx[i], __dmul_rn(alpha, vdelta[i])));
                 __syncthreads();
                 PROF_MARK(4);
-                cost_c = uni(sweep(vxc, vgn, true));  // also assembles J^T J at the trial point into Mat
-                PROF_MARK(2);                         // 2: line-search sweeps
-                ++exec_passes; ++n_ls_evals;
-                current.x = alpha; current.value = cost_c; current.value_valid = isfinite(cost_c);
-                current.gradient = 0.0; current.gradient_valid = false;
-                if (current.value_valid && !(cost_c > cost + kLsSufficientDecrease * g_dot_delta * alpha)) { ls_ok = true; break; }
-                if (current.value_valid) {
+                cost_c = uni(sweep(vxc, vgn, true));      // also assembles J^T J at the trial point into Mat
+                PROF_MARK(2);                             // 2: line-search sweeps
+                if (lm.sample(ls, alpha, cost_c)) { ls_ok = true; break; }
+                if (ls.current.value_valid) {
                     double p = 0.0;
                     for (int i = tid; i < n; i += kBlockThreads) p += vdelta[i] * vgn[i];
-                    current.gradient = block_sum<kBlockThreads>(p, sh);
-                    current.gradient_valid = isfinite(current.gradient);
+                    ls.set_gradient(block_sum<kBlockThreads>(p, sh));
                 }
-                const double nstep = ls_next_step_regs(initial, previous, current, dir_max, n_iter);
+                const double nstep = ls_next_step_regs(ls.initial, ls.previous, ls.current, dir_max, n_iter);
                 if (nstep < 0.0) break;
-                previous = current;
+                ls.previous = ls.current;
                 alpha = uni(nstep);
             }
         }
@@ -1700,56 +1758,37 @@ __device__ __forceinline__ void solve_component(const KernelArgs &a, const int m
             for (int i = tid; i < n; i += kBlockThreads) vxc[i] = clampb(__dadd_rn(vx[i], vdelta[i]));
             __syncthreads();
             cost_c = uni(sweep(vxc, vgn, true));
-            ++exec_passes;
+            ++lm.exec_passes;
         }
-        ++n_cand;
-        const double cost_cand = uni(isfinite(cost_c) ? cost_c : DBL_MAX);
         double sn = 0.0;
         for (int i = tid; i < n; i += kBlockThreads) sn += (vx[i] - vxc[i]) * (vx[i] - vxc[i]);
-        const double step_norm = sqrt(block_sum<kBlockThreads>(sn, sh));
-        if (step_norm <= kParameterTol * (x_norm + kParameterTol)) break;
-        const double cost_change = cost - cost_cand;
-        if (fabs(cost_change) <= kFunctionTol * cost) break;
-        const double rel = cost_change / model_cost_change;
-        if (rel > kMinRelDecrease) {
+        const LmControl::Verdict v = lm.judge(sqrt(block_sum<kBlockThreads>(sn, sh)), cost_c, model_cost_change);
+        if (v == LmControl::STOP) break;
+        if (v == LmControl::ACCEPT) {
             double xn = 0.0;
             __syncthreads();
             for (int i = tid; i < n; i += kBlockThreads) { vx[i] = vxc[i]; xn += vxc[i] * vxc[i]; }
-            x_norm = uni(sqrt(block_sum<kBlockThreads>(xn, sh)));
+            lm.x_norm = uni(sqrt(block_sum<kBlockThreads>(xn, sh)));
             // the accepted candidate is the last evaluated point: its cost, gradient and J^T J (in Mat,
             // the factorization was no longer needed) are already there - no extra sweep
             for (int i = tid; i < n; i += kBlockThreads) vg[i] = vgn[i];
             __syncthreads();
-            cost = cost_cand;
-            matrix_valid = true;
-            gmax = grad_max(vx, vg);
-            step_successful = true;
-            ++n_successful;
-            const double t = 2.0 * rel - 1.0;
-            radius = uni(fmin(kMaxRadius, radius / fmax(1.0 / 3.0, 1.0 - t * t * t)));
-            decrease_factor = 2.0;
-            reuse_diagonal = false;
-        } else {
-            radius = uni(radius / decrease_factor);
-            decrease_factor = uni(decrease_factor * 2.0);
+            lm.gmax = grad_max(vx, vg);
         }
     }
     __syncthreads();
     PROF_MARK(4);
 #ifdef LFR_PROFILE_ONLY_ITER       // diagnostic builds: phase profile of the slow components only
-    if (iteration >= LFR_PROFILE_ONLY_ITER)
+    if (lm.iteration >= LFR_PROFILE_ONLY_ITER)
 #endif
     PROF_FLUSH();
     for (int i = tid; i < n; i += kBlockThreads)
-        a.positions[2 * (size_t)a.node_ids[d.node_off + (i >> 1)] + (i & 1)] = term != LFR_TERM_FAILURE ? vx[i] : 0.0;
+        a.positions[2 * (size_t)a.node_ids[d.node_off + (i >> 1)] + (i & 1)] = lm.term != LFR_TERM_FAILURE ? vx[i] : 0.0;
     if (tid == 0) {
-        CompInfoDev inf;
-        inf.iterations = iteration; inf.termination = term; inf.n_successful = n_successful;
-        inf.n_ls_evals = n_ls_evals; inf.n_cand_evals = n_cand; inf.exec_passes = exec_passes;
-        inf.final_cost = cost;
+        CompInfoDev inf = lm.info();
 #ifdef LFR_PROFILE_WGTIME          // diagnostic builds: the workgroup's lifetime in s_memtime ticks instead of the cost
         inf.final_cost = (double)(__builtin_amdgcn_s_memtime() - wg_t0_);
-        if (LFR_PROFILE_WGTIME == 2) inf.final_cost = exec_passes + 1e3 * n_ls_evals + 1e6 * n_cand + 1e9 * n_successful + 1e12 * n_invalid;
+        if (LFR_PROFILE_WGTIME == 2) inf.final_cost = lm.exec_passes + 1e3 * lm.n_ls_evals + 1e6 * lm.n_cand + 1e9 * lm.n_successful + 1e12 * lm.n_invalid;
         if (LFR_PROFILE_WGTIME == 3) {           // start time, lifetime in kiloticks, hardware id (XCC, SE, CU)
             inf.final_cost = (double)wg_r0_;
             inf.iterations = (int)(wall_clock64() - wg_r0_);
@@ -2781,28 +2820,18 @@ __device__ __forceinline__ void solve_tree_component(const KernelArgs &a, const 
     //      the LM diagonal.  Per iteration: that pass, the factorization, the back substitution, one pass + reduction for the
     //      model's cost change, and two reductions per sweep. ----
     // (-DLFR_PROFILE_PHASES: 0 sweeps, 1 factorization, 5 scaling, 6 back substitution, 4 everything else - the slots of the LDS kernels)
-    int exec_passes = 1;
     SweepOut sw = sweep(vx, vdelta, 0.0, false, vxc, vg);
-    double cost = uni(sw.cost);                       // (uni: the loop's scalars are replicated - SGPRs, like the LDS kernel's)
+    const double cost0 = uni(sw.cost);                // (uni: the loop's scalars are replicated - SGPRs, like the LDS kernel's)
     PROF_MARK(0);
-    double gmax = uni(sw.gm);
-    double x_norm = 0.0, radius = kInitialRadius, decrease_factor = 2.0;
-    bool reuse_diagonal = false, step_successful = true, matrix_valid = true;
-    int n_invalid = 0, iteration = 0, term = LFR_TERM_CONVERGENCE;
-    int n_successful = 0, n_ls_evals = 0, n_cand = 0;
-    for (;;) {
-        if (iteration >= kMaxIterations) { term = LFR_TERM_NO_CONVERGENCE; break; }
-        if (step_successful && gmax <= kGradientTol) break;
-        if (radius <= kMinRadius) break;
-        ++iteration;
-        TR_IT(iteration);
+    LmControl lm{cost0, uni(sw.gm)};
+    while (lm.begin_iteration()) {
+        TR_IT(lm.iteration);
         TR(10, 0);
-        step_successful = false;
         PROF_MARK(4);
-        if (!matrix_valid) {           // A holds J^T J of a rejected trial point: re-assemble at x
+        if (!lm.matrix_valid) {        // A holds J^T J of a rejected trial point: re-assemble at x
             sweep(vx, vdelta, 0.0, false, vxc, vg);
-            ++exec_passes;
-            matrix_valid = true;
+            ++lm.exec_passes;
+            lm.matrix_valid = true;
             PROF_MARK(0);
         }
         // the damped system (A + S^-1 D^2 S^-1) (S y) = g: the scaled LM diagonal onto the diagonal tiles, g into w.
@@ -2817,13 +2846,13 @@ __device__ __forceinline__ void solve_tree_component(const KernelArgs &a, const 
             for (int u = 0; u < 4; ++u) {
                 const int i = i0 + u * GT;
                 if (i >= n) break;
-                if (iteration == 1) { sc[u] = 1.0 / (1.0 + sqrt(ad[u])); vscale[i] = sc[u]; }       // the Jacobi scaling: fixed at the initial point
-                if (!reuse_diagonal) { dg[u] = fmin(fmax(sc[u] * sc[u] * ad[u], kMinLmDiag), kMaxLmDiag); vdiag[i] = dg[u]; }
-                vD[i] = sqrt(dg[u] / radius) / sc[u];                        // D / s (the column tasks add D^2 to their diagonal tiles)
+                if (lm.iteration == 1) { sc[u] = 1.0 / (1.0 + sqrt(ad[u])); vscale[i] = sc[u]; }    // the Jacobi scaling: fixed at the initial point
+                if (!lm.reuse_diagonal) { dg[u] = LmControl::lm_diag(sc[u], ad[u]); vdiag[i] = dg[u]; }
+                vD[i] = lm.lm_d(dg[u], sc[u]);                               // (the column tasks add D^2 to their diagonal tiles)
                 vw[i] = gg[u];
             }
         }
-        reuse_diagonal = true;
+        lm.reuse_diagonal = true;
         if (thin || TEAM) {            // the columns' state words of the barrier-free schedule: nothing factored yet
             if constexpr (TEAM) {
                 for (int q = gt; q < NB; q += GT) team_st(gteam + 16 + q, 0u);
@@ -2868,32 +2897,22 @@ __device__ __forceinline__ void solve_tree_component(const KernelArgs &a, const 
             // (a team's bad-pivot word is reset by the leader at the top of the next iteration; every member must have
             // read it first - no sweep or reduction, hence no team barrier, lies on this path otherwise)
             if constexpr (TEAM) tsync();
-            if (++n_invalid >= kMaxInvalid) { term = LFR_TERM_FAILURE; break; }
-            radius = uni(radius / decrease_factor);
-            decrease_factor = uni(decrease_factor * 2.0);
+            if (lm.invalid_step()) break;
             continue;
         }
-        n_invalid = 0;
         // ---- projected Armijo line search ----
         double alpha = 1.0, cost_c = 0.0;
         bool ls_ok = false;
         {
-            LsSample initial{0.0, cost, g_dot_delta, true, true}, previous{0, 0, 0, false, false}, current;
-            int n_iter = 0;
-            for (;;) {
+            LmSearch ls = lm.start_search(g_dot_delta);
+            for (int n_iter = 0;;) {
                 PROF_MARK(4);
-                sw = sweep(vx, vdelta, alpha, true, vxc, vgn);             // also assembles J^T J at the trial point
+                sw = sweep(vx, vdelta, alpha, true, vxc, vgn);                 // also assembles J^T J at the trial point
                 cost_c = uni(sw.cost);
-                matrix_valid = false;
+                lm.matrix_valid = false;
                 PROF_MARK(0);
-                ++exec_passes; ++n_ls_evals;
-                current.x = alpha; current.value = cost_c; current.value_valid = isfinite(cost_c);
-                current.gradient = 0.0; current.gradient_valid = false;
-                if (current.value_valid && !(cost_c > cost + kLsSufficientDecrease * g_dot_delta * alpha)) { ls_ok = true; break; }
-                if (current.value_valid) {
-                    current.gradient = uni(sw.gd);                 // delta . g(trial point), summed by the sweep's node pass
-                    current.gradient_valid = isfinite(current.gradient);
-                }
+                if (lm.sample(ls, alpha, cost_c)) { ls_ok = true; break; }
+                if (ls.current.value_valid) ls.set_gradient(uni(sw.gd));      // delta . g(trial point), summed by the sweep's node pass
                 TR(15, 0);
                 // The next trial step is a pure function of replicated scalars - 10-40 k cycles of polynomial fitting and root
                 // isolation (9-18 us when all eight waves of the CU run it side by side: two waves per SIMD share the issue port).
@@ -2902,71 +2921,52 @@ __device__ __forceinline__ void solve_tree_component(const KernelArgs &a, const 
                 {
                     int n_iter_w0 = n_iter;
                     if (wave == 0) {
-                        const double v = ls_next_step_wave(initial, previous, current, dir_max, n_iter_w0);
+                        const double v = ls_next_step_wave(ls.initial, ls.previous, ls.current, dir_max, n_iter_w0);
                         if (lane == 0) sh.bcast[0] = v;
                     }
                     __syncthreads();
                     nstep = uni(sh.bcast[0]);
-                    ++n_iter;                                    // (= what ls_next_step_regs did to wave 0's copy)
+                    ++n_iter;                                        // (= what ls_next_step_regs did to wave 0's copy)
                     __syncthreads();
                 }
                 TR(16, 0);
                 if (nstep < 0.0) break;
-                previous = current;
+                ls.previous = ls.current;
                 alpha = nstep;
             }
         }
         if (!ls_ok) {
             sw = sweep(vx, vdelta, 1.0, true, vxc, vgn);
             cost_c = uni(sw.cost);
-            matrix_valid = false;
-            ++exec_passes;
+            lm.matrix_valid = false;
+            ++lm.exec_passes;
         }
-        ++n_cand;
-        const double cost_cand = uni(isfinite(cost_c) ? cost_c : DBL_MAX);
         // step norm, and - should the candidate be accepted - its norm and projected gradient: from the sweep
-        const double step_norm = sqrt(sw.sn);
-        if (step_norm <= kParameterTol * (x_norm + kParameterTol)) break;
-        const double cost_change = cost - cost_cand;
-        if (fabs(cost_change) <= kFunctionTol * cost) break;
-        const double rel = cost_change / model_cost_change;
-        if (rel > kMinRelDecrease) {
+        const LmControl::Verdict v = lm.judge(sqrt(sw.sn), cost_c, model_cost_change);
+        if (v == LmControl::STOP) break;
+        if (v == LmControl::ACCEPT) {
             { double *t = vx; vx = vxc; vxc = t; t = vg; vg = vgn; vgn = t; }      // the candidate becomes x, its gradient g
-            x_norm = uni(sqrt(sw.xn));
-            cost = cost_cand;
-            matrix_valid = true;              // the accepted candidate is the last evaluated point: its J^T J is in the tiles
-            gmax = uni(sw.gm);
-            step_successful = true;
-            ++n_successful;
-            const double t = 2.0 * rel - 1.0;
-            radius = uni(fmin(kMaxRadius, radius / fmax(1.0 / 3.0, 1.0 - t * t * t)));
-            decrease_factor = 2.0;
-            reuse_diagonal = false;
-        } else {
-            radius = uni(radius / decrease_factor);
-            decrease_factor = uni(decrease_factor * 2.0);
+            lm.x_norm = uni(sqrt(sw.xn));
+            lm.gmax = uni(sw.gm);
         }
     }
     PROF_MARK(4);
     PROF_FLUSH();
     tsync();
-    if constexpr (TEAM) { if (team_ld(tm.ctl + 9) != 0u) term = LFR_TERM_FAILURE; }      // a wait of this launch's teams gave up: nothing computed since can be trusted
+    if constexpr (TEAM) { if (team_ld(tm.ctl + 9) != 0u) lm.term = LFR_TERM_FAILURE; }   // a wait of this launch's teams gave up: nothing computed since can be trusted
     for (int p = gt; p < 8 * NB; p += GT) {
         const uint32_t v = ipos[p];
         if (v == kNone) continue;
         double *out = a.positions + 2 * (size_t)a.node_ids[d.node_off + v];
-        out[0] = term != LFR_TERM_FAILURE ? ldd(vx + 2 * p) : 0.0;
-        out[1] = term != LFR_TERM_FAILURE ? ldd(vx + 2 * p + 1) : 0.0;
+        out[0] = lm.term != LFR_TERM_FAILURE ? ldd(vx + 2 * p) : 0.0;
+        out[1] = lm.term != LFR_TERM_FAILURE ? ldd(vx + 2 * p + 1) : 0.0;
     }
     if (tid == 0 && (!TEAM || tm.r == 0)) {
-        CompInfoDev inf;
-        inf.iterations = iteration; inf.termination = term; inf.n_successful = n_successful;
-        inf.n_ls_evals = n_ls_evals; inf.n_cand_evals = n_cand; inf.exec_passes = exec_passes;
-        inf.final_cost = cost;
+        CompInfoDev inf = lm.info();
 #if defined(LFR_PROFILE_WGTIME) && LFR_PROFILE_WGTIME == 3      // diagnostic builds (scripts/sparse_timeline.py): start (100 MHz ticks) in the cost, lifetime << 4 | team size in the termination
         inf.final_cost = (double)tree_r0_;
         inf.termination = (int)(((wall_clock64() - tree_r0_) << 4) | (unsigned long long)tS);
-        inf.iterations = iteration | (min(exec_passes, 1023) << 8) | (min(n_successful, 255) << 18);
+        inf.iterations = lm.iteration | (min(lm.exec_passes, 1023) << 8) | (min(lm.n_successful, 255) << 18);
 #endif
         a.infos[ci] = inf;
     }
@@ -3242,8 +3242,7 @@ __global__ __launch_bounds__(kBlockThreads) __attribute__((amdgpu_waves_per_eu(2
 constexpr int kThreadsS = LFR_THREADS_S, kThreadsM = LFR_THREADS_M, kThreadsL = LFR_THREADS_L, kThreadsG = LFR_THREADS_G;
 
 size_t block_vector_doubles(int max_rows) { return 2 * (size_t)(max_rows + 2) + 8 * (size_t)max_rows; }
-size_t block_lds_bytes(int max_rows, bool global_matrix) {
-    if (global_matrix) return 0;                       // matrix and vectors live in the HBM workspace
+size_t block_lds_bytes(int max_rows) {
     // nine vectors (the step is row max_rows of the matrix) + the packed triangle of max_rows + 1 rows
     return (block_vector_doubles(max_rows) - (size_t)max_rows + (size_t)(max_rows + 1) * (max_rows + 2) / 2) * sizeof(double);
 }
@@ -4077,7 +4076,7 @@ int lfr_debug_solve_damped(int device, int solver, int64_t n_sys, const int32_t 
         }
     } else {
         const int max_rows = kLimit[solver];
-        const size_t lds = block_lds_bytes(max_rows, false);
+        const size_t lds = block_lds_bytes(max_rows);
         const void *fn = solver == 4 ? (const void *)debug_solve_block_kernel<kThreadsS> : solver == 5 ? (const void *)debug_solve_block_kernel<kThreadsM>
                                                                                                        : (const void *)debug_solve_block_kernel<kThreadsL>;
         HIP_TRY(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
@@ -4162,9 +4161,9 @@ int lfr_batch_create(const lfr_problem *ph, int device, int shard_rank, int shar
             HIP_TRY(hipEventRecord(b->ev_order, so));
         }
         host_trace("lfr_batch_create: hand-out order enqueued");
-        const int lds_s = (int)block_lds_bytes(std::max(b->class_max_rows[lfr::KC_BLOCK], 2), false);
-        const int lds_m = (int)block_lds_bytes(std::max(b->class_max_rows[lfr::KC_BLOCK_M], 2), false);
-        const int lds_l = (int)block_lds_bytes(std::max(b->class_max_rows[lfr::KC_BLOCK_L], 2), false);
+        const int lds_s = (int)block_lds_bytes(std::max(b->class_max_rows[lfr::KC_BLOCK], 2));
+        const int lds_m = (int)block_lds_bytes(std::max(b->class_max_rows[lfr::KC_BLOCK_M], 2));
+        const int lds_l = (int)block_lds_bytes(std::max(b->class_max_rows[lfr::KC_BLOCK_L], 2));
         HIP_TRY(hipFuncSetAttribute((const void *)solve_block_kernel<kThreadsS>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_s));
         HIP_TRY(hipFuncSetAttribute((const void *)solve_block_kernel<kThreadsM>, hipFuncAttributeMaxDynamicSharedMemorySize, std::max(lds_m, kThreadsM == kThreadsS ? lds_s : 0)));
         HIP_TRY(hipFuncSetAttribute((const void *)solve_block_kernel<kThreadsL>, hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -4240,23 +4239,23 @@ int lfr_batch_solve(lfr_batch *b, void *hip_stream, lfr_solve_stats *stats) {
         a.desc_begin = b->class_begin[cls]; a.desc_end = b->class_begin[cls + 1]; a.cls = cls;
         const int n = a.desc_end - a.desc_begin;
         if (n <= 0) return LFR_OK;
-        const int rows = b->class_max_rows[cls];
-        const size_t lds = block_lds_bytes(rows, cls == lfr::KC_GLOBAL);
-        // persistent workgroups: what the chip keeps resident for the class (by LDS, and 8 waves of 256 registers per CU)
-        const int threads = cls == lfr::KC_BLOCK ? kThreadsS : cls == lfr::KC_BLOCK_M ? kThreadsM : cls == lfr::KC_BLOCK_L ? kThreadsL : kThreadsG;
-        const int by_waves = std::max(1, 512 / threads), by_lds = lds ? std::max(1, (int)((size_t)160 * 1024 / (lds + 256))) : by_waves;
-        const int wgs = std::min(n, b->ctx->n_cu * std::min(by_waves, by_lds));
-        switch (cls) {
-            case lfr::KC_BLOCK:   hipLaunchKernelGGL((solve_block_kernel<kThreadsS>), dim3(wgs), dim3(kThreadsS), lds, cs, a, rows); break;
-            case lfr::KC_BLOCK_M: hipLaunchKernelGGL((solve_block_kernel<kThreadsM>), dim3(wgs), dim3(kThreadsM), lds, cs, a, rows); break;
-            case lfr::KC_BLOCK_L: hipLaunchKernelGGL((solve_block_kernel<kThreadsL>), dim3(wgs), dim3(kThreadsL), lds, cs, a, rows); break;
-            default: {
-                if (const char *e = getenv("LFR_DEBUG_TREE_FIRST")) a.desc_end = std::min(a.desc_end, a.desc_begin + std::max(1, atoi(e)));   // (experiments: only the first k of the hand-out order)
-                // elimination-tree kernel: one 512-thread workgroup per CU (two waves per SIMD), static LDS only
-                // (at least 8 kTeamMax workgroups: whatever the placement, one of the eight XCDs then holds a complete unit)
-                if (b->d_team_ctl) hipLaunchKernelGGL((solve_tree_team_kernel<kThreadsG>), dim3(std::max(8 * kTeamMax, std::min(b->team_wgs, b->ctx->n_cu / 32 * 32))), dim3(kThreadsG), 0, cs, a);
-                else hipLaunchKernelGGL((solve_tree_kernel<kThreadsG>), dim3(std::min(n, b->ctx->n_cu)), dim3(kThreadsG), 0, cs, a);
-                break;
+        if (cls == lfr::KC_GLOBAL) {
+            if (const char *e = getenv("LFR_DEBUG_TREE_FIRST")) a.desc_end = std::min(a.desc_end, a.desc_begin + std::max(1, atoi(e)));   // (experiments: only the first k of the hand-out order)
+            // elimination-tree kernel: one 512-thread workgroup per CU (two waves per SIMD), static LDS only
+            // (at least 8 kTeamMax workgroups: whatever the placement, one of the eight XCDs then holds a complete unit)
+            if (b->d_team_ctl) hipLaunchKernelGGL((solve_tree_team_kernel<kThreadsG>), dim3(std::max(8 * kTeamMax, std::min(b->team_wgs, b->ctx->n_cu / 32 * 32))), dim3(kThreadsG), 0, cs, a);
+            else hipLaunchKernelGGL((solve_tree_kernel<kThreadsG>), dim3(std::min(n, b->ctx->n_cu)), dim3(kThreadsG), 0, cs, a);
+        } else {
+            const int rows = b->class_max_rows[cls];
+            const size_t lds = block_lds_bytes(rows);
+            // persistent workgroups: what the chip keeps resident for the class (by LDS, and 8 waves of 256 registers per CU)
+            const int threads = cls == lfr::KC_BLOCK ? kThreadsS : cls == lfr::KC_BLOCK_M ? kThreadsM : kThreadsL;
+            const int by_waves = std::max(1, 512 / threads), by_lds = std::max(1, (int)((size_t)160 * 1024 / (lds + 256)));
+            const int wgs = std::min(n, b->ctx->n_cu * std::min(by_waves, by_lds));
+            switch (cls) {
+                case lfr::KC_BLOCK:   hipLaunchKernelGGL((solve_block_kernel<kThreadsS>), dim3(wgs), dim3(kThreadsS), lds, cs, a, rows); break;
+                case lfr::KC_BLOCK_M: hipLaunchKernelGGL((solve_block_kernel<kThreadsM>), dim3(wgs), dim3(kThreadsM), lds, cs, a, rows); break;
+                case lfr::KC_BLOCK_L: hipLaunchKernelGGL((solve_block_kernel<kThreadsL>), dim3(wgs), dim3(kThreadsL), lds, cs, a, rows); break;
             }
         }
         HIP_TRY(hipGetLastError());
