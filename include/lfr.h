@@ -349,6 +349,54 @@ int lfr_batch_backward(lfr_batch *b, const double *grad_positions_device, void *
  * Waits for that backward.  Returns the count (< 0: error, LFR_ERR_ARG before the first backward). */
 int64_t lfr_batch_backward_status(lfr_batch *b, int32_t *status);
 
+/* ---------------------------------------------------------------------------------------------
+ * Per-keypoint covariance of the refined positions (the counterpart of ceres::Covariance with apply_loss_function = true; the
+ * reference's `solve` never asks Ceres for it).
+ *
+ * Contract.  Take the batch after its latest lfr_batch_solve; x^ = the fp64 positions it produced.  Per solved component, with the
+ * component structure of that solve held fixed:
+ *   - A = J^T J over ALL coordinates of the component's variable nodes, J the loss-corrected Jacobian at x^ of the component's kept
+ *     directed edges: corrector sqrt(rho') (both losses have rho'' <= 0), the similarity as the loss scale, the interpolant's
+ *     derivative zeroed outside [-0.5, 0.5] (cost.cc:38-43) - the Gauss-Newton matrix of the LM loop, without damping and without
+ *     Jacobi scaling.  Like Ceres it ignores the +-1 box bounds;
+ *   - C = A^-1.  Per node n three numbers cov[3n + 0..2] = C(di,di), C(di,dj), C(dj,dj) of the node's own 2x2 diagonal block, in the
+ *     axis order of `positions` and in the solver's unit squared;
+ *   - roots, other constant nodes, nodes outside solved components and nodes outside this shard: 0;
+ *   - usable components: termination CONVERGENCE or NO_CONVERGENCE.  FAILURE components: all zeros, status "not usable";
+ *   - an elimination that meets a pivot that is not positive (a node tied in only by edges of weight 0 or by saturated Tukey edges):
+ *     all zeros for that component, status "singular".  A zero diagonal can never be the covariance of a variable node, so a 0 is
+ *     unambiguous: "no covariance for this node".  Every other component - also one in the same wavefront - is unaffected, bit for bit;
+ *   - results are bitwise repeatable from call to call, and identical for the host-assembled and the device-assembled batch.
+ * Kernels: components of up to 32 rows in ONE launch in the solve's packed layout (64/S components per wavefront, one lane per row,
+ * one evaluation sweep at x^ and an in-register Gauss-Jordan inversion); above, one workgroup per component: A in LDS up to 192
+ * rows, in an HBM workspace above; the backward's LDL^T and, per node, two forward substitutions.  Components above 6144 rows:
+ * LFR_ERR_UNSUPPORTED. */
+typedef struct lfr_covariance_stats {
+    int64_t n_computed;            /* components whose covariance was computed */
+    int64_t n_not_usable;          /* FAILURE components (zeros) */
+    int64_t n_singular;            /* components whose A met a pivot that is not positive (zeros) */
+    double kernel_ms;              /* HIP-event time of the covariance's kernels (and its clearing of the output) */
+} lfr_covariance_stats;
+
+#define LFR_COVARIANCE_F64 1       /* the output is double instead of float32 (the float32 output is the fp64 result rounded once) */
+
+/* cov_device: 3 * n_nodes float32 (double with LFR_COVARIANCE_F64) of the whole graph; the whole array is overwritten.  Runs on
+ * `hip_stream` after the latest solve; asynchronous unless stats != NULL.  LFR_ERR_ARG before the first solve.  Changes nothing the
+ * solve or the backward read. */
+int lfr_batch_covariance(lfr_batch *b, void *cov_device, int flags, void *hip_stream, lfr_covariance_stats *stats);
+/* Per component (order of lfr_batch_component_info) of the latest covariance: 0 computed, 1 not usable, 2 singular.  Waits for that
+ * call.  Returns the count (< 0: error, LFR_ERR_ARG before the first lfr_batch_covariance). */
+int64_t lfr_batch_covariance_status(lfr_batch *b, int32_t *status);
+/* Consumer side, the counterpart of lfr_apply_displacements (colmap_utils.py:126-137): per feature of `image_name` the 2x2 covariance
+ * in PIXELS and in keypoint (x, y) order, (16 * fact)^2 * [[C(dj,dj), C(di,dj)], [C(di,dj), C(di,di)]], as out[3f + 0..2] = xx, xy,
+ * yy.  cov: 3 * n_nodes doubles on the host.  Features the graph does not know, roots and unsolved nodes get 0.  Host code. */
+int lfr_keypoint_covariances(const lfr_graph *g, const double *cov, const char *image_name, float *out, int64_t num_features);
+/* Unit-level probe of the packed classes' in-register inversion: n_sys symmetric matrices placed in waves exactly as
+ * lfr_debug_solve_damped places systems (solver 0-3: n_rows <= 8, 16, 24, 32, even; 0 = an empty group).  A: the lower triangles,
+ * packed row by row; Cinv: the inverses' full lower triangles in the same layout (row i as lane i holds it); status[s] = 0, or 2 when
+ * a pivot was not positive (Cinv of that system is then zero).  Test infrastructure, not part of the covariance path. */
+int lfr_debug_invert_spd(int device, int solver, int64_t n_sys, const int32_t *n_rows, const double *A, double *Cinv, int32_t *status);
+
 /* Unit-level probe of the device arithmetic (cost.cc:13-48,78-90 + the loss / corrector of solve.cc:111,120): for
  * each of n edges (flows n x 18 float32, sim, kind 0 = intra-track/Cauchy 1 = inter-track/Tukey, x1 = source and
  * x2 = destination position) the kernels' eval_edge on the GPU: out8[8i..] = 0.5*rho, corrected residual r0 r1,

@@ -1,0 +1,521 @@
+// Per-keypoint covariance of the refined positions (lfr_batch_covariance, include/lfr.h).
+// Included at the end of lfr_solve.hip behind lfr_backward_impl.hpp: it reads the batch layout and the packed kernel's pieces that live
+// there (load_packed_edge, PackedRanges, eval_edge) and the backward's assembly and LDL^T, and changes nothing the solve or the backward read.
+//
+// Per solved component C = (J^T J)^-1 at the solve's x, J the loss-corrected Jacobian - the undamped, unscaled matrix of the LM loop:
+//   packed classes (<= 32 rows)   ONE launch in the forward's layout: a wave64 hosts 64/S components, one-wave workgroups, no barriers.
+//                                 One sweep with the forward's eval_edge and the matrix part of its LDS adds (five per edge), then an in-place Gauss-Jordan
+//                                 INVERSION with one row per lane and all n columns of the row in registers; the pivot row travels as
+//                                 the DPP operand of v_fmac_f64 (8- and 16-row classes) or through ds_swizzle (32-row classes).
+//   workgroup classes (33..6144)  one workgroup per component: the backward's owner-computes assembly without rho'' and the second
+//                                 derivatives, its zero-skipping LDL^T, then per node two forward substitutions with unit right-hand
+//                                 sides and C(i,j) = sum_k W(k,i) W(k,j) / d_k, W = L^-1; nodes dealt to waves, fixed summation order.
+
+namespace {
+
+constexpr int kCovThreads = 256;              // workgroup classes
+constexpr size_t kCovLdsMax = 160 * 1024 - 256;
+
+// ---- in-register Gauss-Jordan inversion, lane = row ----
+// Step K: every lane takes pivot row K (before the step), p = its pivot; rows i != K: h_ij -= (h_iK / p) h_Kj for j != K and
+// h_iK = -h_iK / p; row K: h_Kj /= p and h_KK = 1 / p.  After n steps h is the inverse.  No pivoting (SPD); padded rows are identity.
+// Column K rides through the rank-1 update with the others (one wasted multiply-add) and is then overwritten.
+template <int K, int BANK, int C0, int CL>
+__device__ __forceinline__ void cov_fmac_cols(double nf, double (&h)[CL]) {
+    constexpr int n = CL - C0;
+    if constexpr (n >= 4) {
+        fmac_bcast<K, BANK>(nf, h[C0], h[C0 + 1], h[C0 + 2], h[C0 + 3]);
+        cov_fmac_cols<K, BANK, C0 + 4, CL>(nf, h);
+    } else if constexpr (n == 3) fmac_bcast<K, BANK>(nf, h[C0], h[C0 + 1], h[C0 + 2]);
+    else if constexpr (n == 2) fmac_bcast<K, BANK>(nf, h[C0], h[C0 + 1]);
+    else if constexpr (n == 1) fmac_bcast<K, BANK>(nf, h[C0]);
+}
+
+template <int NV, int K, int CL>
+struct CovGaussJordan {
+    static __device__ __forceinline__ void run(double (&h)[CL], double &minpiv, const int row, const int n_steps) {
+        const bool is_k = row == K;
+        double rp, nf;
+        if constexpr (NV <= 16) {
+            // the group sits inside one 16-lane DPP row: row_newbcast:K inside the v_fmac_f64 (NV == 8: two groups per DPP row, the
+            // update is issued per half with a bank mask).  Every asm statement of these helpers opens with s_nop 1 (lfr_device.hpp).
+            const double piv = (NV == 16) ? bcast16_f64<K>(h[K]) : bcast8_f64<K>(h[K]);
+            minpiv = fmin(minpiv, piv);
+            rp = 1.0 / piv;
+            nf = is_k ? 0.0 : -(h[K] * rp);                            // (the pivot lane's own row stays: h += 0 * h)
+            if constexpr (NV == 16) cov_fmac_cols<K, 0xf, 0, CL>(nf, h);
+            else { cov_fmac_cols<K, 0x3, 0, CL>(nf, h); cov_fmac_cols<K + 8, 0xc, 0, CL>(nf, h); }
+        } else {
+            // one burst of ds_swizzle broadcasts inside the 32-lane half (the <32,2> class holds its rows twice, once per half)
+            double pr[CL];
+#pragma unroll
+            for (int c = 0; c < CL; ++c) pr[c] = swz_bcast<0x00, K>(h[c]);
+            const double piv = pr[K];
+            minpiv = fmin(minpiv, piv);
+            rp = 1.0 / piv;
+            nf = is_k ? 0.0 : -(h[K] * rp);
+#pragma unroll
+            for (int c = 0; c < CL; ++c) h[c] = fma(nf, pr[c], h[c]);
+        }
+        const double sc = is_k ? rp : 1.0;                             // the pivot row is scaled, the others multiply by an exact 1
+#pragma unroll
+        for (int c = 0; c < CL; ++c) h[c] *= sc;
+        h[K] = is_k ? rp : nf;
+        if constexpr (K + 1 < CL) {
+            if (K + 1 < n_steps) CovGaussJordan<NV, K + 1, CL>::run(h, minpiv, row, n_steps);
+        }
+    }
+};
+
+// The inversion of a packed class (CLS 0-3 = <8,1>, <16,1>, <32,1>, <32,2>) in the instantiation sized for the largest system of the
+// wave (n_max, wave-uniform): build(c) = the lane's entry of column c, sink(h, ok) takes the lane's row of the inverse; ok = false: a
+// pivot of the lane's group was not positive.  Every lane of the wave must be active.
+template <int CLS, class Build, class Sink>
+__device__ __forceinline__ void cov_invert(const int row, const int n_max, Build &&build, Sink &&sink) {
+    constexpr int NV = CLS == 0 ? 8 : CLS == 1 ? 16 : 32;
+    auto run = [&](auto cl_tag) {
+        constexpr int CL = decltype(cl_tag)::value;
+        double h[CL];
+#pragma unroll
+        for (int c = 0; c < CL; ++c) h[c] = build(c);
+        double minpiv = 1.0;
+        CovGaussJordan<NV, 0, CL>::run(h, minpiv, row, n_max);
+        sink(h, minpiv > 0.0);
+    };
+#define LFR_COV_CL(n) run(std::integral_constant<int, n>{})
+    if constexpr (CLS == 0) {
+        if (n_max <= 2) LFR_COV_CL(2); else if (n_max <= 4) LFR_COV_CL(4); else if (n_max <= 6) LFR_COV_CL(6); else LFR_COV_CL(8);
+    } else if constexpr (CLS == 1) {
+        if (n_max <= 10) LFR_COV_CL(10); else if (n_max <= 12) LFR_COV_CL(12); else if (n_max <= 14) LFR_COV_CL(14); else LFR_COV_CL(16);
+    } else if constexpr (CLS == 2) {                   // the class holds <= 24 rows (classify())
+        if (n_max <= 18) LFR_COV_CL(18); else if (n_max <= 20) LFR_COV_CL(20); else if (n_max <= 22) LFR_COV_CL(22); else LFR_COV_CL(24);
+    } else {
+        if (n_max <= 20) LFR_COV_CL(20); else if (n_max <= 26) LFR_COV_CL(26); else if (n_max <= 28) LFR_COV_CL(28);
+        else if (n_max <= 30) LFR_COV_CL(30); else LFR_COV_CL(32);
+    }
+#undef LFR_COV_CL
+}
+
+__device__ __forceinline__ int cov_wave_max(int v) {
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) v = max(v, __shfl_xor(v, m, 64));
+    return __builtin_amdgcn_readfirstlane(v);
+}
+
+// ---- packed classes ----
+template <int NV>
+struct alignas(16) CovLds {
+    static constexpr int LD = NV + 1;
+    double A[NV * LD];         // J^T J (lower triangle)
+    double x[NV + 2];          // x^; slots 2*n_var, 2*n_var+1 stay 0 (constants)
+};
+
+struct CovArgs {
+    KernelArgs k;              // descs, edges, node_ids, positions, infos, the fused gather's arrays, tukey_variant
+    void *cov;                 // 3 per node of the whole graph, float or double (cleared before the launch)
+    int32_t *status;           // per descriptor
+    int f64;
+};
+
+__device__ __forceinline__ void cov_store(const CovArgs &a, const uint32_t node, const double c00, const double c01, const double c11) {
+    if (a.f64) { double *o = static_cast<double *>(a.cov) + 3 * (size_t)node; o[0] = c00; o[1] = c01; o[2] = c11; }
+    else { float *o = static_cast<float *>(a.cov) + 3 * (size_t)node; o[0] = (float)c00; o[1] = (float)c01; o[2] = (float)c11; }
+}
+
+template <int CLS, int EPL, bool FUSED>
+__device__ __forceinline__ void cov_group_body(const CovArgs &ca, const int desc_begin, const int desc_end, const int block_in_class,
+                                               unsigned char *lds_raw) {
+    constexpr int NV = CLS == 0 ? 8 : CLS == 1 ? 16 : 32, LPR = CLS == 3 ? 2 : 1;
+    constexpr int S = NV * LPR, G = 64 / S, LD = NV + 1;
+    const KernelArgs &a = ca.k;
+    const int lane = threadIdx.x & 63;
+    const int gid = lane / S, sl = lane % S;
+    const int row = sl % NV, part = sl / NV;
+    const int ci0 = desc_begin + block_in_class * G;
+    if (ci0 >= desc_end) return;                      // wave-uniform
+    const int ci = ci0 + gid;
+    const bool have = ci < desc_end;
+    CovLds<NV> &L = reinterpret_cast<CovLds<NV> *>(lds_raw)[gid];
+
+    CompDesc d;
+    d.edge_off = 0; d.n_edges = 0; d.node_off = 0; d.n_nodes = 0; d.n_var = 0;
+    if (have) d = a.descs[ci];
+    const bool usable = have && a.infos[ci].termination != LFR_TERM_FAILURE;
+    const int n_var = usable ? d.n_var : 0, nv2 = 2 * n_var, E = usable ? (int)d.n_edges : 0;     // a group without a usable component inverts the identity
+    const bool is_row = row < nv2;
+    const int nv2_max = cov_wave_max(nv2);
+    const uint32_t node = is_row ? a.node_ids[d.node_off + (row >> 1)] : 0u;
+
+    for (int i = sl; i < NV * LD; i += S) L.A[i] = 0.0;
+    for (int i = sl; i < NV + 2; i += S) L.x[i] = (i < nv2) ? a.positions[2 * (size_t)a.node_ids[d.node_off + (i >> 1)] + (i & 1)] : 0.0;
+    wave_lds_sync();
+
+    // ---- one sweep at x^: the forward's evaluation and its assembly (solve_group_body) ----
+#pragma unroll
+    for (int k = 0; k < EPL; ++k) {
+        if (!(sl + S * k < E)) continue;
+        float flow_k[18]; float sim_k; uint32_t pk;
+        load_packed_edge<FUSED>(a, d.edge_off + (sl + S * k), flow_k, sim_k, pk);
+        const int es = (int)(pk & 0xffffu), ed = (int)((pk >> 16) & 0x7fffu), ekind = (int)(pk >> 31);
+        const int xa = 2 * min(es, n_var), xb = 2 * min(ed, n_var);      // constants read the zero slot
+        const int ra = es < n_var ? 2 * es : -1, rb = ed < n_var ? 2 * ed : -1;
+        EdgeOut o;
+        eval_edge<true>(flow_k, sim_k, ekind, a.tukey_variant, L.x[xa], L.x[xa + 1], L.x[xb], L.x[xb + 1], o);
+        double *A = L.A;
+        // lane ^ 1 holds the opposite direction of the same match (records 2m, 2m+1): its d r / d x_dst = sq' * I terms land on THIS
+        // lane's source block and the two cross blocks coincide - exchanged through DPP, five LDS adds per edge
+        const int q = sl & 1;
+        const double p_w = dpp_f64<kDppQuadXor1>(o.sq * o.sq);
+        const double c_send1 = o.sq * (q ? o.j00 : o.j01), c_send2 = o.sq * (q ? o.j11 : o.j10);
+        const double c_own1 = o.sq * (q ? o.j10 : o.j00), c_own2 = o.sq * (q ? o.j01 : o.j11);
+        const double c1 = c_own1 + dpp_f64<kDppQuadXor1>(c_send1);
+        const double c2 = c_own2 + dpp_f64<kDppQuadXor1>(c_send2);
+        if (ra >= 0) {
+            atomicAdd(&A[ra * LD + ra], o.j00 * o.j00 + o.j10 * o.j10 + p_w);
+            atomicAdd(&A[(ra + 1) * LD + ra], o.j01 * o.j00 + o.j11 * o.j10);
+            atomicAdd(&A[(ra + 1) * LD + ra + 1], o.j01 * o.j01 + o.j11 * o.j11 + p_w);
+        }
+        if (ra >= 0 && rb >= 0) {
+            const int r1 = rb + q, k1 = ra, r2 = rb + 1 - q, k2 = ra + 1;
+            atomicAdd(&A[rb > ra ? r1 * LD + k1 : k1 * LD + r1], c1);
+            atomicAdd(&A[rb > ra ? r2 * LD + k2 : k2 * LD + r2], c2);
+        }
+    }
+    wave_lds_sync();
+
+    // ---- inversion, lane = row ----
+    const double *A = L.A;
+    cov_invert<CLS>(row, nv2_max,
+        [&](int c) -> double {
+            double v = 0.0;
+            if (is_row && c < nv2) v = (c <= row ? A[row * LD + c] : A[c * LD + row]);
+            return (!is_row && c == row) ? 1.0 : v;                  // padded rows are identity
+        },
+        [&](auto &h, const bool ok) {
+            constexpr int CL = sizeof(h) / sizeof(double);
+            double dg = 0.0, off = 0.0;                              // C(row,row), C(row,row+1)
+#pragma unroll
+            for (int c = 0; c < CL; ++c) { dg = (c == row) ? h[c] : dg; off = (c == row + 1) ? h[c] : off; }
+            const double dg_next = dpp_f64<kDppQuadXor1>(dg);       // the odd lane's diagonal, to the even lane of the node
+            if (is_row && part == 0 && !(row & 1) && ok) cov_store(ca, node, dg, off, dg_next);
+            if (have && sl == 0) ca.status[ci] = !usable ? 1 : ok ? 0 : 2;
+        });
+}
+
+constexpr size_t kCovPackedLdsBytes = 4 * sizeof(CovLds<16>) > 2 * sizeof(CovLds<32>) ? 4 * sizeof(CovLds<16>) : 2 * sizeof(CovLds<32>);
+static_assert(kCovPackedLdsBytes >= 8 * sizeof(CovLds<8>), "LDS budget");
+
+// all packed classes in ONE launch, the blocks dealt to the classes as in solve_packed_kernel
+template <bool FUSED>
+__global__ __launch_bounds__(64, 2) void covariance_packed_kernel(const CovArgs a, const PackedRanges r) {
+    __shared__ __attribute__((aligned(16))) unsigned char lds_raw[kCovPackedLdsBytes];
+    const int b = (int)blockIdx.x;
+    if (b < r.blk_begin[1]) cov_group_body<3, 5, FUSED>(a, r.desc_begin[0], r.desc_end[0], b - r.blk_begin[0], lds_raw);
+    else if (b < r.blk_begin[2]) cov_group_body<2, 6, FUSED>(a, r.desc_begin[1], r.desc_end[1], b - r.blk_begin[1], lds_raw);
+    else if (b < r.blk_begin[3]) { /* retired class, never assigned */ }
+    else if (b < r.blk_begin[4]) cov_group_body<1, 6, FUSED>(a, r.desc_begin[3], r.desc_end[3], b - r.blk_begin[3], lds_raw);
+    else cov_group_body<0, 3, FUSED>(a, r.desc_begin[4], r.desc_end[4], b - r.blk_begin[4], lds_raw);
+}
+
+// lfr_debug_invert_spd: the inversion alone, systems placed as the groups of a wave
+template <int CLS>
+__global__ __launch_bounds__(64) void debug_invert_kernel(int64_t n_sys, const int32_t *n_rows, const int64_t *tri_off, const double *A,
+                                                          double *Cinv, int32_t *status) {
+    constexpr int NV = CLS == 0 ? 8 : CLS == 1 ? 16 : 32, LPR = CLS == 3 ? 2 : 1;
+    constexpr int S = NV * LPR, G = 64 / S;
+    const int lane = threadIdx.x & 63;
+    const int gid = lane / S, sl = lane % S;
+    const int row = sl % NV, part = sl / NV;
+    const int64_t sys = (int64_t)blockIdx.x * G + gid;
+    const bool have = sys < n_sys;
+    const int n = have ? n_rows[sys] : 0;
+    const int64_t to = have ? tri_off[sys] : 0;
+    const bool is_row = row < n;
+    const int n_max = cov_wave_max(n);
+    cov_invert<CLS>(row, n_max,
+        [&](int c) -> double {
+            double v = 0.0;
+            if (is_row && c < n) v = A[to + (int64_t)bwd_tri(max(row, c), min(row, c))];
+            return (!is_row && c == row) ? 1.0 : v;
+        },
+        [&](auto &h, const bool ok) {
+            constexpr int CL = sizeof(h) / sizeof(double);
+#pragma unroll
+            for (int c = 0; c < CL; ++c)
+                if (is_row && part == 0 && c <= row) Cinv[to + (int64_t)bwd_tri(row, c)] = ok ? h[c] : 0.0;
+            if (have && sl == 0) status[sys] = ok ? 0 : 2;
+        });
+}
+
+// ---- workgroup classes ----
+struct CovBlockArgs {
+    BwdArgs b;                 // descs, edges, node_ids, node_inc, in_idx, positions, infos, hws, hws_off, status, desc_begin, tukey_variant
+    void *cov;
+    int f64;
+    int scratch_doubles;       // dynamic LDS behind the matrix (LDS variant) or all of it (HBM variant)
+};
+
+template <int T, bool LDS_MATRIX>
+__global__ __launch_bounds__(T) void covariance_block_kernel(const CovBlockArgs ca) {
+    extern __shared__ double bsh[];
+    const BwdArgs &a = ca.b;
+    const int di = a.desc_begin + blockIdx.x, tid = threadIdx.x;
+    const CompDesc d = a.descs[di];
+    const int nv = d.n_var, n = 2 * nv;
+    if (a.infos[di].termination == LFR_TERM_FAILURE) {       // not usable: zeros (the output was cleared)
+        if (tid == 0) a.status[di] = 1;
+        return;
+    }
+    double *H = LDS_MATRIX ? bsh : a.hws + a.hws_off[di];
+    double *scratch = LDS_MATRIX ? bsh + bwd_tri(n, 0) : bsh;
+    double *lval = scratch;                                   // the factorization's column buffer; afterwards the waves' vectors
+    int *lidx = reinterpret_cast<int *>(lval + n);
+    __shared__ int cnt[2];
+    const EdgeRec *E = a.edges + d.edge_off;
+    const uint32_t *ids = a.node_ids + d.node_off;
+
+    const size_t nt = bwd_tri(n, 0);
+    for (size_t t = tid; t < nt; t += T) H[t] = 0.0;
+    if (tid == 0) { cnt[0] = 0; cnt[1] = 0; }
+    __syncthreads();
+    bwd_assemble<T, false>(a, d, nv, E, ids, H, nullptr, tid);
+    __syncthreads();
+    if (bwd_ldlt<T>(H, n, lval, lidx, cnt, tid)) {             // singular: zeros
+        if (tid == 0) a.status[di] = 2;
+        return;
+    }
+    __syncthreads();
+
+    // diagonal blocks of C = L^-T D^-1 L^-1: node l's two columns of W = L^-1 by forward substitution (rows >= 2l only; a column of L is
+    // visited only where W is not zero), the three sums accumulated as the entries of W become final - in row order, by one wave
+    const int lane = tid & 63, wv = tid >> 6;
+    const int ww = min(T / 64, ca.scratch_doubles / (2 * n));  // waves that have room for their two vectors (>= 1: the launch sizes the LDS)
+    if (wv < ww) {
+        double *w0 = scratch + (size_t)wv * 2 * n, *w1 = w0 + n;
+        for (int l = wv; l < nv; l += ww) {
+            const int i0 = 2 * l;
+            for (int r = i0 + lane; r < n; r += 64) { w0[r] = (r == i0) ? 1.0 : 0.0; w1[r] = (r == i0 + 1) ? 1.0 : 0.0; }
+            wave_lds_sync();
+            double c00 = 0.0, c01 = 0.0, c11 = 0.0;
+            for (int k = i0; k < n; ++k) {
+                const double u = w0[k], v = w1[k];             // (wave-uniform)
+                if (u == 0.0 && v == 0.0) continue;
+                const double dinv = 1.0 / H[bwd_tri(k, k)];
+                c00 += u * u * dinv; c01 += u * v * dinv; c11 += v * v * dinv;
+                for (int r = k + 1 + lane; r < n; r += 64) {
+                    const double lrk = H[bwd_tri(r, k)];
+                    if (lrk != 0.0) { w0[r] -= lrk * u; w1[r] -= lrk * v; }
+                }
+                wave_lds_sync();
+            }
+            if (lane == 0) {
+                if (ca.f64) { double *o = static_cast<double *>(ca.cov) + 3 * (size_t)ids[l]; o[0] = c00; o[1] = c01; o[2] = c11; }
+                else { float *o = static_cast<float *>(ca.cov) + 3 * (size_t)ids[l]; o[0] = (float)c00; o[1] = (float)c01; o[2] = (float)c11; }
+            }
+            wave_lds_sync();
+        }
+    }
+    if (tid == 0) a.status[di] = 0;
+}
+
+size_t cov_scratch_bytes(int rows) { return std::max<size_t>((size_t)rows * 12, (size_t)rows * 16 * (kCovThreads / 64)) + 16; }
+// dynamic LDS of a launch whose largest component has `rows` rows; scratch_doubles: what lies behind the matrix
+size_t cov_lds_bytes(int rows, bool lds_matrix, int &scratch_doubles) {
+    const size_t mat = lds_matrix ? bwd_tri(rows, 0) * 8 : 0;
+    const size_t scratch = std::min(cov_scratch_bytes(rows), kCovLdsMax - mat);
+    scratch_doubles = (int)(scratch / 8);
+    return mat + scratch;
+}
+
+}  // namespace
+
+struct CovState {
+    lfr::DevArena slab;
+    double *d_hws = nullptr;
+    uint64_t *d_hws_off = nullptr;
+    int32_t *d_status = nullptr;
+    int rows_max[lfr::KC_COUNT] = {0};
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    hipStream_t last_stream = nullptr;
+    int64_t n_calls = 0;
+};
+
+void cov_free(CovState *s) {
+    if (!s) return;
+    if (s->last_stream || s->n_calls) (void)hipStreamSynchronize(s->last_stream);
+    if (s->ev0) (void)hipEventDestroy(s->ev0);
+    if (s->ev1) (void)hipEventDestroy(s->ev1);
+    delete s;
+}
+
+namespace {
+
+int cov_setup(lfr_batch *b) {
+    int rc = ensure_mirrors(b);
+    if (rc != LFR_OK) return rc;
+    std::unique_ptr<CovState, void (*)(CovState *)> s(new CovState(), cov_free);
+    const size_t nd = std::max<size_t>(b->descs.size(), 1);
+    std::vector<uint64_t> off(nd, 0);
+    uint64_t hws = 0;
+    for (size_t i = 0; i < b->descs.size(); ++i) {
+        const int cls = b->desc_class[i], rows = 2 * b->descs[i].n_var;
+        s->rows_max[cls] = std::max(s->rows_max[cls], rows);
+        if (cls == lfr::KC_GLOBAL) {
+            if (rows > kBwdMaxRows) { lfr::set_error("covariance: a component of %d rows exceeds the dense factorization's %d", rows, kBwdMaxRows); return LFR_ERR_UNSUPPORTED; }
+            off[i] = hws; hws += bwd_tri(rows, 0);
+        }
+    }
+    if (!s->slab.init(b->ctx, 8 * hws + 8 * nd + 4 * nd + ((size_t)1 << 16))) return LFR_ERR_NOMEM;
+    s->d_hws = s->slab.take_n<double>(std::max<uint64_t>(hws, 1));
+    s->d_hws_off = s->slab.take_n<uint64_t>(nd);
+    s->d_status = s->slab.take_n<int32_t>(nd);
+    if (!s->d_hws || !s->d_hws_off || !s->d_status) { lfr::set_error("covariance slab exhausted"); return LFR_ERR_NOMEM; }
+    HIP_TRY(hipEventCreate(&s->ev0)); HIP_TRY(hipEventCreate(&s->ev1));
+    hipStream_t st = b->ctx->s_main;
+    HIP_TRY(hipMemcpyAsync(s->d_hws_off, off.data(), 8 * nd, hipMemcpyHostToDevice, st));
+    HIP_TRY(lfr::stream_wait(st));
+    int sd = 0;
+    HIP_TRY(hipFuncSetAttribute((const void *)covariance_block_kernel<kCovThreads, true>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                (int)cov_lds_bytes(lfr::kBlockMaxRows, true, sd)));
+    HIP_TRY(hipFuncSetAttribute((const void *)covariance_block_kernel<kCovThreads, false>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                (int)cov_lds_bytes(kBwdMaxRows, false, sd)));
+    b->cov = s.release();
+    return LFR_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int lfr_batch_covariance(lfr_batch *b, void *cov_device, int flags, void *hip_stream, lfr_covariance_stats *stats) {
+    if (!b || !cov_device || (flags & ~LFR_COVARIANCE_F64)) { lfr::set_error("bad argument"); return LFR_ERR_ARG; }
+    if (b->n_solves == 0) { lfr::set_error("lfr_batch_covariance: the batch has not been solved"); return LFR_ERR_ARG; }
+    HIP_TRY(hipSetDevice(b->device));
+    if (!b->cov) { const int rc = cov_setup(b); if (rc != LFR_OK) return rc; }
+    CovState &s = *b->cov;
+    hipStream_t st = (hipStream_t)hip_stream;
+    const int f64 = (flags & LFR_COVARIANCE_F64) ? 1 : 0;
+    HIP_TRY(hipStreamWaitEvent(st, b->ev[1], 0));                               // the latest solve's positions and termination codes
+    HIP_TRY(hipEventRecord(s.ev0, st));
+    if (b->n_graph_nodes) HIP_TRY(hipMemsetAsync(cov_device, 0, 3 * (size_t)b->n_graph_nodes * (f64 ? 8 : 4), st));
+    {   // packed classes: one launch, the blocks dealt as lfr_batch_solve deals them
+        static const int kOrder[5] = {lfr::KC_G64_4, lfr::KC_G64_2, lfr::KC_G32, lfr::KC_G16, lfr::KC_G8};
+        static const int kGroups[5] = {1, 2, 2, 4, 8};
+        PackedRanges r;
+        int nb = 0;
+        for (int i = 0; i < 5; ++i) {
+            r.blk_begin[i] = nb;
+            r.desc_begin[i] = b->class_begin[kOrder[i]]; r.desc_end[i] = b->class_begin[kOrder[i] + 1];
+            nb += (r.desc_end[i] - r.desc_begin[i] + kGroups[i] - 1) / kGroups[i];
+        }
+        r.blk_begin[5] = nb;
+        CovArgs a;
+        memset(&a, 0, sizeof(a));
+        a.k.descs = b->d_descs; a.k.edges = b->d_edges; a.k.node_ids = b->d_node_ids; a.k.positions = b->d_positions; a.k.infos = b->d_infos;
+        a.k.tukey_variant = b->tukey_variant; a.k.edge_ref = b->d_edge_ref; a.k.edge_word = b->d_edge_word;
+        a.cov = cov_device; a.status = s.d_status; a.f64 = f64;
+        if (nb > 0) {
+            if (b->fused) {                  // the packed records have not been written yet: gather from the graph's arrays, as the solve did
+                const lfr::DevGraph &dgr = *b->dev_hold->graph;
+                a.k.f_row = dgr.flow_row; a.k.f_disp1 = dgr.disp1; a.k.f_disp2 = dgr.disp2; a.k.f_sim = dgr.sim;
+                hipLaunchKernelGGL(covariance_packed_kernel<true>, dim3(nb), dim3(64), 0, st, a, r);
+            } else {
+                hipLaunchKernelGGL(covariance_packed_kernel<false>, dim3(nb), dim3(64), 0, st, a, r);
+            }
+        }
+    }
+    CovBlockArgs c;
+    memset(&c, 0, sizeof(c));
+    c.b.descs = b->d_descs; c.b.edges = b->d_edges; c.b.node_ids = b->d_node_ids; c.b.node_inc = b->d_node_inc; c.b.in_idx = b->d_in_idx;
+    c.b.positions = b->d_positions; c.b.infos = b->d_infos; c.b.hws = s.d_hws; c.b.hws_off = s.d_hws_off; c.b.status = s.d_status;
+    c.b.tukey_variant = b->tukey_variant; c.b.scan_all = 0;
+    c.cov = cov_device; c.f64 = f64;
+    for (int cls = lfr::KC_BLOCK; cls < lfr::KC_COUNT; ++cls) {
+        c.b.desc_begin = b->class_begin[cls];
+        const int n = b->class_begin[cls + 1] - c.b.desc_begin, rows = std::max(s.rows_max[cls], 2);
+        if (n <= 0) continue;
+        if (cls == lfr::KC_GLOBAL) {
+            const size_t lds = cov_lds_bytes(rows, false, c.scratch_doubles);
+            hipLaunchKernelGGL((covariance_block_kernel<kCovThreads, false>), dim3(n), dim3(kCovThreads), lds, st, c);
+        } else {
+            const size_t lds = cov_lds_bytes(rows, true, c.scratch_doubles);
+            hipLaunchKernelGGL((covariance_block_kernel<kCovThreads, true>), dim3(n), dim3(kCovThreads), lds, st, c);
+        }
+    }
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(s.ev1, st));
+    s.last_stream = st;
+    ++s.n_calls;
+    if (stats) {
+        HIP_TRY(hipEventSynchronize(s.ev1));
+        std::vector<int32_t> status(b->descs.size());
+        if (!status.empty()) HIP_TRY(hipMemcpyAsync(status.data(), s.d_status, 4 * status.size(), hipMemcpyDeviceToHost, st));
+        HIP_TRY(lfr::stream_wait(st));
+        memset(stats, 0, sizeof(*stats));
+        for (int32_t v : status) {
+            if (v == 0) ++stats->n_computed;
+            else if (v == 1) ++stats->n_not_usable;
+            else ++stats->n_singular;
+        }
+        float ms = 0.f;
+        HIP_TRY(hipEventElapsedTime(&ms, s.ev0, s.ev1));
+        stats->kernel_ms = ms;
+    }
+    return LFR_OK;
+}
+
+int64_t lfr_batch_covariance_status(lfr_batch *b, int32_t *status) {
+    if (!b || !b->cov || !b->cov->n_calls) { lfr::set_error("lfr_batch_covariance_status: no covariance has run on this batch"); return LFR_ERR_ARG; }
+    HIP_TRY(hipSetDevice(b->device));
+    HIP_TRY(hipEventSynchronize(b->cov->ev1));
+    const size_t n = b->descs.size();
+    if (status && n) {
+        HIP_TRY(hipMemcpyAsync(status, b->cov->d_status, 4 * n, hipMemcpyDeviceToHost, b->cov->last_stream));
+        HIP_TRY(lfr::stream_wait(b->cov->last_stream));
+    }
+    return (int64_t)n;
+}
+
+int lfr_debug_invert_spd(int device, int solver, int64_t n_sys, const int32_t *n_rows, const double *A, double *Cinv, int32_t *status) {
+    static const int kLimit[4] = {8, 16, 24, 32};
+    static const int kGroups[4] = {8, 4, 2, 1};
+    if (solver < 0 || solver > 3 || n_sys < 0 || n_sys > (1 << 24) || (n_sys > 0 && (!n_rows || !A || !Cinv || !status))) {
+        lfr::set_error("bad argument"); return LFR_ERR_ARG;
+    }
+    std::vector<int64_t> off((size_t)n_sys);
+    int64_t n_tri = 0;
+    for (int64_t s = 0; s < n_sys; ++s) {
+        const int n = n_rows[s];
+        if (n < 0 || n > kLimit[solver] || (n & 1)) { lfr::set_error("n_rows[%lld] = %d: not an even row count the solver takes", (long long)s, n); return LFR_ERR_ARG; }
+        off[s] = n_tri;
+        n_tri += (int64_t)n * (n + 1) / 2;
+    }
+    lfr::DevCtx *ctx = lfr::dev_ctx(device);
+    if (!ctx) return LFR_ERR_HIP;
+    if (n_sys == 0) return LFR_OK;
+    HIP_TRY(hipSetDevice(device));
+    lfr::DevArena ar;
+    if (!ar.init(ctx, (size_t)n_sys * (4 + 8 + 4) + (size_t)n_tri * 16 + 16 * 256)) return LFR_ERR_NOMEM;
+    int32_t *d_rows = ar.take_n<int32_t>(n_sys), *d_status = ar.take_n<int32_t>(n_sys);
+    int64_t *d_off = ar.take_n<int64_t>(n_sys);
+    double *d_A = ar.take_n<double>(std::max<int64_t>(n_tri, 1)), *d_C = ar.take_n<double>(std::max<int64_t>(n_tri, 1));
+    if (!d_rows || !d_status || !d_off || !d_A || !d_C) { lfr::set_error("arena exhausted"); return LFR_ERR_NOMEM; }
+    hipStream_t st = ctx->s_main;
+    HIP_TRY(hipMemcpyAsync(d_rows, n_rows, 4 * (size_t)n_sys, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(d_off, off.data(), 8 * (size_t)n_sys, hipMemcpyHostToDevice, st));
+    if (n_tri) HIP_TRY(hipMemcpyAsync(d_A, A, 8 * (size_t)n_tri, hipMemcpyHostToDevice, st));
+    const dim3 grid((unsigned)((n_sys + kGroups[solver] - 1) / kGroups[solver]));
+    switch (solver) {
+        case 0: hipLaunchKernelGGL(debug_invert_kernel<0>, grid, dim3(64), 0, st, n_sys, d_rows, d_off, d_A, d_C, d_status); break;
+        case 1: hipLaunchKernelGGL(debug_invert_kernel<1>, grid, dim3(64), 0, st, n_sys, d_rows, d_off, d_A, d_C, d_status); break;
+        case 2: hipLaunchKernelGGL(debug_invert_kernel<2>, grid, dim3(64), 0, st, n_sys, d_rows, d_off, d_A, d_C, d_status); break;
+        default: hipLaunchKernelGGL(debug_invert_kernel<3>, grid, dim3(64), 0, st, n_sys, d_rows, d_off, d_A, d_C, d_status); break;
+    }
+    HIP_TRY(hipGetLastError());
+    if (n_tri) HIP_TRY(hipMemcpyAsync(Cinv, d_C, 8 * (size_t)n_tri, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(status, d_status, 4 * (size_t)n_sys, hipMemcpyDeviceToHost, st));
+    HIP_TRY(lfr::stream_wait(st));
+    return LFR_OK;
+}
+
+}  // extern "C"

@@ -3274,6 +3274,8 @@ constexpr size_t kProfWords = 8 * lfr::KC_COUNT + 8 + 64;  // phase counters of 
 constexpr uint32_t kPackedEventsAliased = 1u << 31;     // ev_recorded: the packed launch is timed by the solve's own pair of events
 struct BwdState;                                        // lfr_backward_impl.hpp
 void bwd_free(BwdState *s);
+struct CovState;                                        // lfr_covariance_impl.hpp
+void cov_free(CovState *s);
 struct lfr_batch {
     int device = 0;
     lfr::DevCtx *ctx = nullptr;
@@ -3351,10 +3353,12 @@ struct lfr_batch {
     const lfr::Graph *graph = nullptr;   // for the record -> directed-edge map of batches without edge_ref
     int64_t n_graph_matches = 0;
     BwdState *bwd = nullptr;
+    CovState *cov = nullptr;             // per-keypoint covariance (lfr_covariance_impl.hpp): set up on the first lfr_batch_covariance
 
     lfr_batch() { for (auto &e : ev_ring) e = nullptr; }
     ~lfr_batch() {
         bwd_free(bwd);
+        cov_free(cov);
         if (ctx) {
             (void)hipSetDevice(device);
             if (n_solves > 0) (void)hipStreamSynchronize(last_stream);      // nothing may still use the slab
@@ -4854,3 +4858,6 @@ int lfr_solve_graph_hip_multi(const lfr_graph *g, const int *devices, int n_devi
 
 // implicit-gradient backward pass (lfr_batch_backward)
 #include "lfr_backward_impl.hpp"
+
+// per-keypoint covariance of the refined positions (lfr_batch_covariance)
+#include "lfr_covariance_impl.hpp"

@@ -1137,6 +1137,28 @@ int lfr_apply_displacements(const lfr_graph *gh, const double *positions, const 
     return LFR_OK;
 }
 
+int lfr_keypoint_covariances(const lfr_graph *gh, const double *cov, const char *image_name, float *out, int64_t num_features) {
+    if (!gh || !image_name || (!out && num_features > 0) || num_features < 0 || (!cov && gh->g.n_nodes() > 0)) {
+        set_error("bad argument"); return LFR_ERR_ARG;
+    }
+    const Graph &g = gh->g;
+    for (int64_t i = 0; i < 3 * num_features; ++i) out[i] = 0.0f;
+    const auto it = g.image_index.find(image_name);
+    if (it == g.image_index.end()) return LFR_OK;
+    const int32_t im = it->second;
+    const double px = 16.0 * (double)g.image_fact[im], s = px * px;      // solver unit -> pixels (colmap_utils.py:133-136), squared
+    for (int64_t k = g.img_off[im]; k < g.img_off[im + 1]; ++k) {
+        const uint32_t n = g.img_nodes[k];
+        const uint32_t f = g.node_feat[n];
+        if ((int64_t)f >= num_features) { set_error("feature_idx %u out of range (%lld keypoints)", f, (long long)num_features); return LFR_ERR_ARG; }
+        // keypoint (x, y) = (dj, di): xx = C(dj,dj), xy = C(di,dj), yy = C(di,di)
+        out[3 * (size_t)f] = (float)(s * cov[3 * (size_t)n + 2]);
+        out[3 * (size_t)f + 1] = (float)(s * cov[3 * (size_t)n + 1]);
+        out[3 * (size_t)f + 2] = (float)(s * cov[3 * (size_t)n]);
+    }
+    return LFR_OK;
+}
+
 int lfr_write_solution(const lfr_graph *gh, const double *positions, const char *path, int64_t *n_outside) {
     if (!gh || !path || (!positions && gh->g.n_nodes() > 0)) { set_error("bad argument"); return LFR_ERR_ARG; }
     const Graph &g = gh->g;

@@ -46,6 +46,8 @@ class _Refine(torch.autograd.Function):
             b.solve(stream=stream, want_stats=False)
             pos = torch.empty((g.n_nodes, 2), dtype=torch.float64, device=device)
             b.positions_to(pos, stream=stream)
+            if meta["return_covariance"]:      # not an output of the Function: the covariance is not differentiated
+                meta["covariance"] = b.covariance(f64=True, stream=stream)
         node_image, node_feature = g.nodes()
         ctx.batch = b
         ctx.meta = meta
@@ -74,14 +76,17 @@ class _Refine(torch.autograd.Function):
 
 
 def refine(disp1, disp2, sim, *, image_names, pair_img1, pair_img2, pair_off, feat1, feat2, image_facts=None, banned=(),
-           tukey_variant="ceres1"):
+           tukey_variant="ceres1", return_covariance=False):
     """Multi-view refinement of the matches as a differentiable function of the flows and similarities.
 
     disp1, disp2: [n_matches, 18] (or [n_matches, 9, 2]) float32 tensors on one HIP device - disp2 = flow image1 -> image2, disp1 =
     flow image2 -> image1 (lfr_graph_from_arrays); sim: [n_matches] similarities (any device); the rest as lfr_graph_from_arrays.
     Returns (positions, node_image, node_feature): [n_nodes, 2] float64 device positions (di, dj per node, the solver's unit) and the
     node -> (image index, feature index) map as numpy arrays.  Gradients reach disp1, disp2 and sim; the matches of banned pairs
-    get 0."""
+    get 0.
+    return_covariance=True: a fourth value, the [n_nodes, 3] float64 device tensor of lfr_batch_covariance (C(di,di), C(di,dj),
+    C(dj,dj) per node, the solver's unit squared; 0 = no covariance for this node).  It is detached: the covariance is not
+    differentiated."""
     pair_img1 = np.ascontiguousarray(pair_img1, np.int32)
     pair_img2 = np.ascontiguousarray(pair_img2, np.int32)
     pair_off = np.ascontiguousarray(pair_off, np.int64)
@@ -90,7 +95,9 @@ def refine(disp1, disp2, sim, *, image_names, pair_img1, pair_img2, pair_off, fe
         raise ValueError("refine: disp1 and disp2 must be on the same HIP device")
     meta = {"image_names": list(image_names), "facts": facts, "pair_img1": pair_img1, "pair_img2": pair_img2, "pair_off": pair_off,
             "feat1": np.ascontiguousarray(feat1, np.uint32), "feat2": np.ascontiguousarray(feat2, np.uint32),
-            "banned": tuple(banned), "tukey_variant": tukey_variant,
+            "banned": tuple(banned), "tukey_variant": tukey_variant, "return_covariance": bool(return_covariance),
             "kept_rows": _kept_rows(pair_img1, pair_img2, pair_off, list(image_names), tuple(banned))}
     pos, node_image, node_feature = _Refine.apply(disp1, disp2, sim, meta)
+    if return_covariance:
+        return pos, node_image, node_feature, meta.pop("covariance").detach()
     return pos, node_image, node_feature

@@ -57,8 +57,17 @@ class BackwardStats(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+class CovarianceStats(C.Structure):
+    _fields_ = [(n, C.c_int64) for n in ("n_computed", "n_not_usable", "n_singular")] + [("kernel_ms", C.c_double)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
 BACKWARD_F64 = 1                # LFR_BACKWARD_F64
 BACKWARD_OK, BACKWARD_NOT_USABLE, BACKWARD_INDEFINITE = 0, 1, 2      # lfr_batch_backward_status
+COVARIANCE_F64 = 1              # LFR_COVARIANCE_F64
+COVARIANCE_OK, COVARIANCE_NOT_USABLE, COVARIANCE_SINGULAR = 0, 1, 2     # lfr_batch_covariance_status
 
 
 _lib = None
@@ -121,6 +130,10 @@ def lib():
         "lfr_batch_positions_to_device": (C.c_int, [vp, vp, vp]),
         "lfr_batch_backward": (C.c_int, [vp, vp, vp, vp, vp, C.c_int, vp, C.POINTER(BackwardStats)]),
         "lfr_batch_backward_status": (i64, [vp, vp]),
+        "lfr_batch_covariance": (C.c_int, [vp, vp, C.c_int, vp, C.POINTER(CovarianceStats)]),
+        "lfr_batch_covariance_status": (i64, [vp, vp]),
+        "lfr_keypoint_covariances": (C.c_int, [vp, vp, C.c_char_p, vp, i64]),
+        "lfr_debug_invert_spd": (C.c_int, [C.c_int, C.c_int, i64, vp, vp, vp, vp]),
         "lfr_batch_spin_timeouts": (i64, [vp]),
         "lfr_batch_team_runs": (i64, [vp]),
         "lfr_batch_team_fallbacks": (i64, [vp]),
@@ -153,7 +166,7 @@ EXPORTS = ["lfr_version", "lfr_last_error", "lfr_graph_from_files", "lfr_graph_f
            "lfr_graph_num_images", "lfr_graph_get_nodes", "lfr_graph_image_name", "lfr_graph_image_fact",
            "lfr_write_matching_file", "lfr_problem_build", "lfr_problem_build_labels", "lfr_problem_build_hip", "lfr_problem_free", "lfr_problem_get_stats",
            "lfr_problem_get_labels", "lfr_problem_shard_components", "lfr_hip_warmup", "lfr_batch_create", "lfr_batch_free", "lfr_batch_solve",
-           "lfr_batch_download", "lfr_batch_timing", "lfr_batch_spin_timeouts", "lfr_batch_team_runs", "lfr_batch_team_fallbacks", "lfr_debug_occupy", "lfr_batch_tree_stats", "lfr_batch_component_info", "lfr_batch_positions_to_device", "lfr_batch_backward", "lfr_batch_backward_status", "lfr_solve_hip", "lfr_solve_hip_multi", "lfr_solve_graph_hip_multi", "lfr_write_solution", "lfr_apply_displacements"]
+           "lfr_batch_download", "lfr_batch_timing", "lfr_batch_spin_timeouts", "lfr_batch_team_runs", "lfr_batch_team_fallbacks", "lfr_debug_occupy", "lfr_batch_tree_stats", "lfr_batch_component_info", "lfr_batch_positions_to_device", "lfr_batch_backward", "lfr_batch_backward_status", "lfr_batch_covariance", "lfr_batch_covariance_status", "lfr_keypoint_covariances", "lfr_debug_invert_spd", "lfr_solve_hip", "lfr_solve_hip_multi", "lfr_solve_graph_hip_multi", "lfr_write_solution", "lfr_apply_displacements"]
 
 
 def _check(rc):
@@ -285,6 +298,17 @@ class Graph:
                                              keypoints.shape[0], keypoints.shape[1]))
         return keypoints
 
+    def keypoint_covariances(self, cov, image_name, num_features):
+        """Per feature of `image_name` the 2x2 covariance in pixels and keypoint (x, y) order (lfr_keypoint_covariances): a float32
+        [num_features, 3] array of (xx, xy, yy) from the [n_nodes, 3] covariance of Batch.covariance (on the host); 0 where the graph
+        has no node, for roots and for unsolved nodes."""
+        c = np.ascontiguousarray(cov, np.float64)
+        if c.size != 3 * self.n_nodes:
+            raise ValueError("keypoint_covariances: need a [%d, 3] array" % self.n_nodes)
+        out = np.zeros((int(num_features), 3), np.float32)
+        _check(lib().lfr_keypoint_covariances(self._h, _ptr(c), image_name.encode("utf-8"), _ptr(out), int(num_features)))
+        return out
+
     def write_solution(self, positions, path):
         """SolutionFile emit (solve.cc:644-679); returns the '> 0.5' count of solve.cc:666-670."""
         pos = np.ascontiguousarray(positions, np.float64)
@@ -355,6 +379,22 @@ def solve_damped_hip(solver, n_rows, A, damp, g, device=0):
     status = np.zeros(n_rows.size, np.int32)
     _check(lib().lfr_debug_solve_damped(device, SOLVERS[solver], n_rows.size, _ptr(n_rows), _ptr(A), _ptr(damp), _ptr(g), _ptr(y), _ptr(status)))
     return y, status
+
+
+def invert_spd_hip(solver, n_rows, A, device=0):
+    """The packed classes' in-register inversion on the GPU (lfr_debug_invert_spd).  solver: "g8", "g16", "g64_2" or "g64_4";
+    n_rows[s] per system; A: the packed lower triangles concatenated (see lfr.h).  Returns (Cinv, status): the inverses' lower
+    triangles in the same layout, status 0 or COVARIANCE_SINGULAR (a pivot was not positive; that system's Cinv is zero)."""
+    n_rows = np.ascontiguousarray(n_rows, np.int32)
+    A = np.ascontiguousarray(A, np.float64)
+    if SOLVERS[solver] > 3:
+        raise ValueError("invert_spd_hip: a packed solver")
+    if A.size != int((n_rows.astype(np.int64) * (n_rows + 1) // 2).sum()):
+        raise ValueError("A does not match n_rows")
+    Cinv = np.zeros(A.size, np.float64)
+    status = np.zeros(n_rows.size, np.int32)
+    _check(lib().lfr_debug_invert_spd(device, SOLVERS[solver], n_rows.size, _ptr(n_rows), _ptr(A), _ptr(Cinv), _ptr(status)))
+    return Cinv, status
 
 
 def sort_pairs_hip(keys, vals, begin_bit, end_bit, use_library=False, device=0):
@@ -519,6 +559,7 @@ class Batch:
         h = C.c_void_p()
         _check(lib().lfr_batch_create(problem._h, device, shard_rank, shard_world, TUKEY[tukey_variant], C.byref(h)))
         self._h = h
+        self.device = int(device)
 
     def close(self):
         if getattr(self, "_h", None):
@@ -613,6 +654,32 @@ class Batch:
         n = lib().lfr_batch_component_info(self._h, None, None, None, None, None, None)
         out = np.zeros(max(n, 0), np.int32)
         rc = lib().lfr_batch_backward_status(self._h, _ptr(out))
+        if rc < 0:
+            _check(rc)
+        return out
+
+    def covariance(self, f64=False, stream=None, want_stats=False):
+        """Per-keypoint covariance of the latest solve (lfr_batch_covariance, include/lfr.h): a [n_nodes, 3] device tensor of
+        C(di,di), C(di,dj), C(dj,dj) per node in the solver's unit squared (float32, or float64 with f64=True); 0 for roots, unsolved
+        nodes and the nodes of components that are not usable or singular.  With want_stats also the stats dict (that waits)."""
+        import torch
+        n = self.problem.graph.n_nodes
+        dev = torch.device("cuda", self.device)
+        cov = torch.empty((n, 3), dtype=torch.float64 if f64 else torch.float32, device=dev)
+        if stream is None:
+            stream = torch.cuda.current_stream(dev).cuda_stream
+        st = CovarianceStats()
+        _check(lib().lfr_batch_covariance(self._h, C.c_void_p(cov.data_ptr() or 1), COVARIANCE_F64 if f64 else 0,
+                                          C.c_void_p(stream) if stream else None, C.byref(st) if want_stats else None))
+        if want_stats:
+            return cov, st.as_dict()
+        return cov
+
+    def covariance_status(self):
+        """Per component (order of component_info) of the latest covariance: COVARIANCE_OK / _NOT_USABLE / _SINGULAR."""
+        n = lib().lfr_batch_component_info(self._h, None, None, None, None, None, None)
+        out = np.zeros(max(n, 0), np.int32)
+        rc = lib().lfr_batch_covariance_status(self._h, _ptr(out))
         if rc < 0:
             _check(rc)
         return out
