@@ -424,6 +424,21 @@ int lfr_debug_ls_next_step(int device, int64_t n, const double *samples, const d
  * the factorization ran out.  Test infrastructure, not part of the solve path. */
 int lfr_debug_solve_damped(int device, int solver, int64_t n_sys, const int32_t *n_rows, const double *A, const double *damp, const double *g,
                            double *y, int32_t *status);
+/* Unit-level probe of the LM step solve of the elimination-tree kernel (components above 192 rows: the level-scheduled sparse LDL^T of
+ * solve_tree_component): for each of n_sys systems (A + D) y = g, ONE factorization and back substitution by the device code of the
+ * solve - the column tasks with their left-looking updates on the matrix cores, the barrier-free schedule of thin plans with the tiles
+ * finished behind the elimination, the barrier schedule with its tile and extra-row tasks, the back substitution - on the caller's
+ * matrix instead of a sweep's.  One workgroup per system (a team of one), all systems in one launch; a system's workspace behind the
+ * plan's words is filled with NaN before the kernel's own prologue runs.  blobs: the plans as lfr_debug_tree_plan returns them, one
+ * after the other, blob_words[s] words each (at most 4096 blocks).  tiles: the values of A in the plan's tile layout, n_tiles x 16 x 16
+ * doubles per system (tile t = rows of block rowsof[t], columns of the block whose colptr range holds t, row-major; the diagonal tile
+ * first in each column, its lower triangle read; tiles that are fill only: zero).  damp, g, y: n_pad = 16 x blocks doubles per system
+ * in MATRIX order (row 2 p + c of node position p), zero at padding rows.  The damping goes onto the diagonal tiles as the LM loop puts
+ * it there: damp is the kernels' D / s, the column task adds damp_i * damp_i (a product and a sum, each rounded).  y solves
+ * (A + D) y = g (the LM step is -y) and is exactly 0 at padding rows.  status[s] = 0 for a valid solve; bit 0: a pivot was not positive
+ * (y of that system is NaN), bit 1: a bounded spin-wait ran out.  Test infrastructure, not part of the solve path. */
+int lfr_debug_solve_tree(int device, int64_t n_sys, const int64_t *blob_words, const uint32_t *blobs, const double *tiles, const double *damp,
+                         const double *g, double *y, int32_t *status);
 /* The library's persistent host workers (they make the elimination-tree plans of a batch, solve.cc:79-143 for components above 192 rows:
  * the reference builds one problem per pool thread, solve.cc:617-635): `items` increments of one counter dealt to `threads` threads, the
  * caller among them, `reps` times.  Returns the number of increments performed (items * reps when nothing was lost).  Callable from

@@ -1936,8 +1936,21 @@ __device__ __forceinline__ void block_reduce5(double &s0, double &s1, double &s2
     s0 = a; s1 = b; s2 = e; s3 = f; m0 = c;
 }
 
-template <int kBlockThreads, bool TEAM>
-__device__ __forceinline__ void solve_tree_component(const KernelArgs &a, const int ci, BlockShared &sh, TreeShared &ts, TeamCtx &tm) {
+// lfr_debug_solve_tree (PROBE instantiation of solve_tree_component): per system the values of A in the plan's tile layout at
+// + tile_off[s], damping, right-hand side and result at + vec_off[s] (n_pad doubles), status bits as lfr.h states them
+struct TreeProbe {
+    const uint64_t *tile_off, *vec_off, *ws_doubles;
+    const double *A, *damp, *g;
+    double *y;
+    int32_t *status;
+};
+
+// PROBE (test infrastructure, one workgroup per system): no sweeps and no trust-region loop - the workspace behind the plan's words
+// is filled with NaN, the prologue below runs as it is, then A, D (into vD: the column tasks square it) and g (into vw) are placed from
+// the caller's buffers, and ONE factor() + back_substitute() produce y.  Every other instantiation compiles to what it was.
+template <int kBlockThreads, bool TEAM, bool PROBE = false>
+__device__ __forceinline__ void solve_tree_component(const KernelArgs &a, const int ci, BlockShared &sh, TreeShared &ts, TeamCtx &tm, const TreeProbe *pb = nullptr) {
+    static_assert(!(PROBE && TEAM), "the probe runs teams of one");
     constexpr int kWaves = kBlockThreads / 64;
     constexpr uint32_t kNone = 0xffffffffu;
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -2007,6 +2020,10 @@ __device__ __forceinline__ void solve_tree_component(const KernelArgs &a, const 
     const int n = n_pad;                                 // rows incl. padding (inert: x = g = step = 0)
 
     unsigned int *gteam = reinterpret_cast<unsigned int *>(wsb + pl[29]);      // TEAM: [0] bad-pivot flag, [16 + J] dependency counter of column J
+    if constexpr (PROBE) {     // whatever the prologue does not initialise reads as NaN
+        for (size_t i = pl[2] + (size_t)tid; i < pb->ws_doubles[ci]; i += kBlockThreads) wsb[i] = __builtin_nan("");
+        __syncthreads();
+    }
     for (int i = gt; i < (int)vs; i += GT) {
         vx[i] = 0.0; vxc[i] = 0.0; vscale[i] = 1.0; vD[i] = 0.0; vg[i] = 0.0; vgn[i] = 0.0; vstep[i] = 0.0; vinv[i] = 0.0; vw[i] = 0.0;
         vadiag[i] = 0.0; vdiag[i] = 0.0; vdelta[i] = 0.0;
@@ -2019,6 +2036,12 @@ __device__ __forceinline__ void solve_tree_component(const KernelArgs &a, const 
         for (size_t i = gt; i < ((size_t)n_tiles << 8); i += GT) t2[i] = z;
     }
     tsync();
+    if constexpr (PROBE) {
+        const double *As = pb->A + pb->tile_off[ci];
+        const uint64_t vo = pb->vec_off[ci];
+        for (size_t i = tid; i < ((size_t)n_tiles << 8); i += kBlockThreads) atiles[i] = As[i];
+        for (int i = tid; i < n; i += kBlockThreads) { vD[i] = pb->damp[vo + i]; vw[i] = pb->g[vo + i]; }
+    }
     // sums and maxima over the team: the workgroup's value first (every thread holds it), then the members' values in a fixed order
     // A reduction over the team IS a barrier: every workgroup publishes its five values as 16-byte {value, tag} granules (one lane,
     // one write-through store each; tag = launch << 32 | reduction number) once all its waves' stores have reached L2, and gathers
@@ -2322,6 +2345,7 @@ __device__ __forceinline__ void solve_tree_component(const KernelArgs &a, const 
             sh.flag = 1;
             if constexpr (TEAM) { if (team_ld(tm.ctl + 9) == 0u) atomicAdd(a.queue + 15, 1u); team_st(tm.ctl + 9, 1u); team_st(gteam, 1u); }
             else atomicAdd(a.queue + 15, 1u);
+            if constexpr (PROBE) atomicOr(pb->status + ci, 2);
         }
         wdead = true;                                     // (this wave gives up waiting for the rest of the solve: one timeout must not cascade into seconds)
     };
@@ -2486,7 +2510,7 @@ __device__ __forceinline__ void solve_tree_component(const KernelArgs &a, const 
                                                                 __builtin_bit_cast(u32x2_t, av[2 * j + 1])[0], __builtin_bit_cast(u32x2_t, av[2 * j + 1])[1]},
                                                        rV, 16u * j, so_w + (dc.J << 7), 0);
         }
-        if (bad && lane == 0) { sh.flag = 1; if constexpr (TEAM) team_st(gteam, 1u); }
+        if (bad && lane == 0) { sh.flag = 1; if constexpr (TEAM) team_st(gteam, 1u); if constexpr (PROBE) atomicOr(pb->status + ci, 1); }
         FPROF_MARK(3);                            // 3: stores
         if (finish_extra && dc.nsub > dc.nc) {
             // Tiles below the diagonal beyond the carried ones (thin plans: a few per component): this wave finishes them itself, three at
@@ -2820,6 +2844,17 @@ __device__ __forceinline__ void solve_tree_component(const KernelArgs &a, const 
     //      the LM diagonal.  Per iteration: that pass, the factorization, the back substitution, one pass + reduction for the
     //      model's cost change, and two reductions per sweep. ----
     // (-DLFR_PROFILE_PHASES: 0 sweeps, 1 factorization, 5 scaling, 6 back substitution, 4 everything else - the slots of the LDS kernels)
+    if constexpr (PROBE) {     // the state the LM loop leaves in front of factor(): no column factored, no bad pivot seen
+        if (thin) { for (int q = tid; q < NB; q += kBlockThreads) ts.pend[q] = 0; }
+        if (tid == 0) sh.flag = 0;
+        tsync();
+        const bool valid = factor();
+        if (valid) back_substitute();
+        __syncthreads();
+        const uint64_t vo = pb->vec_off[ci];
+        for (int i = tid; i < n; i += kBlockThreads) pb->y[vo + i] = valid ? vstep[i] : __builtin_nan("");
+        return;
+    }
     SweepOut sw = sweep(vx, vdelta, 0.0, false, vxc, vg);
     const double cost0 = uni(sw.cost);                // (uni: the loop's scalars are replicated - SGPRs, like the LDS kernel's)
     PROF_MARK(0);
@@ -4099,6 +4134,82 @@ int lfr_debug_solve_damped(int device, int solver, int64_t n_sys, const int32_t 
     if (block) HIP_TRY(hipMemcpyAsync(spins.data(), d_spins, 4 * (size_t)n_sys, hipMemcpyDeviceToHost, st));
     HIP_TRY(lfr::stream_wait(st));
     for (size_t s = 0; s < spins.size(); ++s) if (spins[s]) status[s] |= 2;
+    return LFR_OK;
+}
+
+extern "C++" {
+namespace {
+// lfr_debug_solve_tree: one workgroup per system runs the PROBE instantiation of solve_tree_component (the column tasks, factor_thin /
+// the barrier-schedule factor and back_substitute of the solve, on the caller's matrix instead of a sweep's)
+template <int kBlockThreads>
+__global__ __launch_bounds__(kBlockThreads) __attribute__((amdgpu_waves_per_eu((kBlockThreads + 255) / 256, (kBlockThreads + 255) / 256)))
+void debug_solve_tree_kernel(const KernelArgs a, const TreeProbe pb) {
+    __shared__ BlockShared sh;
+    __shared__ TreeShared ts;
+    TeamCtx tm;
+    solve_tree_component<kBlockThreads, false, true>(a, (int)blockIdx.x, sh, ts, tm, &pb);
+}
+
+// the header of a plan as lfr_treeplan.cpp lays it out: what the kernel derives addresses from must be consistent with the blob's length
+bool tree_blob_ok(const uint32_t *b, int64_t words) {
+    if (words < lfr::kTreeHdrWords || (words & 63) || b[2] != (uint64_t)words / 2) return false;
+    const uint64_t NB = b[0], n_tiles = b[1], n_items = b[6];
+    if (NB < 1 || NB > 4096 || n_tiles < NB || n_tiles >= (1u << 21) || b[4] != 16 * NB || b[5] < 1 || b[5] > NB || b[24] != 16 * NB + 16) return false;
+    if (b[23] != b[2] + 512 * n_tiles || b[3] < b[23] + 6 * n_items || (b[3] & 31) || b[29] != b[3] + (uint64_t)lfr::kTreeVectors * b[24]) return false;
+    for (int i = 8; i <= 27; ++i) if (i != 23 && i != 24 && (b[i] < (uint32_t)lfr::kTreeHdrWords || b[i] > (uint64_t)words)) return false;
+    if (b[27] + 32 * NB > (uint64_t)words || b[8] + NB + 1 > (uint64_t)words || b[9] + n_tiles > (uint64_t)words) return false;
+    return b[b[8]] == 0 && b[b[8] + NB] == n_tiles;
+}
+}  // namespace
+}  // extern "C++"
+
+int lfr_debug_solve_tree(int device, int64_t n_sys, const int64_t *blob_words, const uint32_t *blobs, const double *tiles, const double *damp,
+                         const double *g, double *y, int32_t *status) {
+    if (n_sys < 0 || n_sys > 4096 || (n_sys > 0 && (!blob_words || !blobs || !tiles || !damp || !g || !y || !status))) { lfr::set_error("bad argument"); return LFR_ERR_ARG; }
+    std::vector<uint64_t> off(4 * (size_t)n_sys);          // per system: workspace, tiles, vectors (doubles), doubles of its workspace
+    uint64_t n_ws = 0, n_til = 0, n_vec = 0, n_blob = 0;
+    for (int64_t s = 0; s < n_sys; ++s) {
+        const uint32_t *b = blobs + n_blob;
+        if (blob_words[s] <= 0 || !tree_blob_ok(b, blob_words[s])) { lfr::set_error("system %lld: not a plan of lfr_debug_tree_plan", (long long)s); return LFR_ERR_ARG; }
+        const uint64_t doubles = (uint64_t)b[29] + (16ull + b[0] + 1) / 2;       // TreePlan::doubles()
+        off[s] = n_ws; off[n_sys + s] = n_til; off[2 * n_sys + s] = n_vec; off[3 * n_sys + s] = doubles;
+        n_ws += (doubles + 31) / 32 * 32; n_til += 256ull * b[1]; n_vec += b[4]; n_blob += (uint64_t)blob_words[s];
+    }
+    lfr::DevCtx *ctx = lfr::dev_ctx(device);
+    if (!ctx) return LFR_ERR_HIP;
+    if (n_sys == 0) return LFR_OK;
+    HIP_TRY(hipSetDevice(device));
+    lfr::DevArena ar;
+    if (!ar.init(ctx, 8 * (n_ws + n_til + 3 * n_vec) + (size_t)n_sys * (32 + 16 + 4) + 64 + 16 * 256)) return LFR_ERR_NOMEM;
+    double *d_ws = ar.take_n<double>(n_ws), *d_A = ar.take_n<double>(n_til), *d_damp = ar.take_n<double>(n_vec), *d_g = ar.take_n<double>(n_vec),
+           *d_y = ar.take_n<double>(n_vec);
+    uint64_t *d_off = ar.take_n<uint64_t>(4 * n_sys);
+    CompDesc *d_descs = ar.take_n<CompDesc>(n_sys);
+    int32_t *d_status = ar.take_n<int32_t>(n_sys);
+    unsigned int *d_queue = ar.take_n<unsigned int>(16);
+    if (!d_queue) { lfr::set_error("arena exhausted"); return LFR_ERR_NOMEM; }
+    hipStream_t st = ctx->s_main;
+    n_blob = 0;
+    for (int64_t s = 0; s < n_sys; ++s) {                  // the plan's words at the head of each workspace, as k_place_plans leaves them
+        HIP_TRY(hipMemcpyAsync(d_ws + off[s], blobs + n_blob, 4 * (size_t)blob_words[s], hipMemcpyHostToDevice, st));
+        n_blob += (uint64_t)blob_words[s];
+    }
+    HIP_TRY(hipMemcpyAsync(d_off, off.data(), 8 * off.size(), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(d_A, tiles, 8 * (size_t)n_til, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(d_damp, damp, 8 * (size_t)n_vec, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(d_g, g, 8 * (size_t)n_vec, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemsetAsync(d_descs, 0, sizeof(CompDesc) * (size_t)n_sys, st));
+    HIP_TRY(hipMemsetAsync(d_status, 0, 4 * (size_t)n_sys, st));
+    HIP_TRY(hipMemsetAsync(d_queue, 0, 64, st));
+    KernelArgs a{};
+    a.descs = d_descs; a.workspace = d_ws; a.ws_off = d_off; a.queue = d_queue; a.cls = lfr::KC_GLOBAL; a.desc_end = (int)n_sys;
+    a.tukey_variant = LFR_TUKEY_CERES1;
+    const TreeProbe pb{d_off + n_sys, d_off + 2 * n_sys, d_off + 3 * n_sys, d_A, d_damp, d_g, d_y, d_status};
+    hipLaunchKernelGGL((debug_solve_tree_kernel<kThreadsG>), dim3((unsigned)n_sys), dim3(kThreadsG), 0, st, a, pb);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(y, d_y, 8 * (size_t)n_vec, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(status, d_status, 4 * (size_t)n_sys, hipMemcpyDeviceToHost, st));
+    HIP_TRY(lfr::stream_wait(st));
     return LFR_OK;
 }
 

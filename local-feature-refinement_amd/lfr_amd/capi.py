@@ -143,6 +143,7 @@ def lib():
         "lfr_debug_ls_next_step": (C.c_int, [C.c_int, i64, vp, vp, C.c_int, vp]),
         "lfr_debug_solve_damped": (C.c_int, [C.c_int, C.c_int, i64, vp, vp, vp, vp, vp, vp]),
         "lfr_debug_tree_plan": (i64, [i32, i64, vp, vp, i64, vp]),
+        "lfr_debug_solve_tree": (C.c_int, [C.c_int, i64, vp, vp, vp, vp, vp, vp, vp]),
         "lfr_debug_pool_selftest": (i64, [C.c_int, i64, C.c_int]),
         "lfr_debug_sort_pairs": (C.c_int, [C.c_int, i64, C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp]),
         "lfr_debug_exclusive_sum": (C.c_int, [C.c_int, i64, C.c_int, vp, vp]),
@@ -162,7 +163,7 @@ def lib():
 
 EXPORTS = ["lfr_version", "lfr_last_error", "lfr_graph_from_files", "lfr_graph_from_matches_file", "lfr_graph_from_matches_file_device",
            "lfr_graph_from_arrays", "lfr_graph_from_arrays_device_flows", "lfr_graph_to_device", "lfr_graph_evict_device",
-           "lfr_problem_build_hip_ex", "lfr_problem_build_hip_shard", "lfr_problem_cc_sharded", "lfr_hip_reserve", "lfr_hip_trim", "lfr_batch_positions_view", "lfr_batch_positions_view_f32", "lfr_bisect_graph", "lfr_debug_eval_edges", "lfr_debug_ls_next_step", "lfr_debug_solve_damped", "lfr_debug_tree_plan", "lfr_debug_pool_selftest", "lfr_debug_sort_pairs", "lfr_debug_exclusive_sum", "lfr_debug_recursive_cut", "lfr_hip_synchronize", "lfr_graph_free", "lfr_graph_num_nodes", "lfr_graph_num_edges",
+           "lfr_problem_build_hip_ex", "lfr_problem_build_hip_shard", "lfr_problem_cc_sharded", "lfr_hip_reserve", "lfr_hip_trim", "lfr_batch_positions_view", "lfr_batch_positions_view_f32", "lfr_bisect_graph", "lfr_debug_eval_edges", "lfr_debug_ls_next_step", "lfr_debug_solve_damped", "lfr_debug_tree_plan", "lfr_debug_solve_tree", "lfr_debug_pool_selftest", "lfr_debug_sort_pairs", "lfr_debug_exclusive_sum", "lfr_debug_recursive_cut", "lfr_hip_synchronize", "lfr_graph_free", "lfr_graph_num_nodes", "lfr_graph_num_edges",
            "lfr_graph_num_images", "lfr_graph_get_nodes", "lfr_graph_image_name", "lfr_graph_image_fact",
            "lfr_write_matching_file", "lfr_problem_build", "lfr_problem_build_labels", "lfr_problem_build_hip", "lfr_problem_free", "lfr_problem_get_stats",
            "lfr_problem_get_labels", "lfr_problem_shard_components", "lfr_hip_warmup", "lfr_batch_create", "lfr_batch_free", "lfr_batch_solve",
@@ -379,6 +380,26 @@ def solve_damped_hip(solver, n_rows, A, damp, g, device=0):
     status = np.zeros(n_rows.size, np.int32)
     _check(lib().lfr_debug_solve_damped(device, SOLVERS[solver], n_rows.size, _ptr(n_rows), _ptr(A), _ptr(damp), _ptr(g), _ptr(y), _ptr(status)))
     return y, status
+
+
+def solve_tree_hip(blobs, tiles, damp, g, device=0):
+    """The elimination-tree kernel's LM step solve (A + D) y = g on the GPU (lfr_debug_solve_tree), one workgroup per system, all in
+    one launch.  Per system: blobs[s] the plan (tree_plan), tiles[s] A in the plan's tile layout [n_tiles, 16, 16], damp[s], g[s] of
+    n_pad doubles in matrix order (see lfr.h).  Returns (list of y, status): status bit 0 = a pivot was not positive (y NaN), bit 1 =
+    a spin-wait ran out."""
+    blobs = [np.ascontiguousarray(b, np.uint32) for b in blobs]
+    words = np.array([b.size for b in blobs], np.int64)
+    n_pad = [16 * int(b[0]) for b in blobs]
+    for b, t, d, gg, n in zip(blobs, tiles, damp, g, n_pad):
+        if np.size(t) != 256 * int(b[1]) or np.size(d) != n or np.size(gg) != n:
+            raise ValueError("tiles, damp, g do not match the plan")
+    cat = lambda xs, dt: np.ascontiguousarray(np.concatenate([np.zeros(0, dt)] + [np.asarray(x, dt).reshape(-1) for x in xs]))
+    B, T, D, G = cat(blobs, np.uint32), cat(tiles, np.float64), cat(damp, np.float64), cat(g, np.float64)
+    y = np.zeros(D.size, np.float64)
+    status = np.zeros(len(blobs), np.int32)
+    _check(lib().lfr_debug_solve_tree(device, len(blobs), _ptr(words), _ptr(B), _ptr(T), _ptr(D), _ptr(G), _ptr(y), _ptr(status)))
+    o = np.r_[0, np.cumsum(n_pad)]
+    return [y[o[i]:o[i + 1]] for i in range(len(blobs))], status
 
 
 def invert_spd_hip(solver, n_rows, A, device=0):

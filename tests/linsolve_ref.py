@@ -1,8 +1,9 @@
-"""Extended-precision reference for the LM step solves of the solver kernels (lfr_debug_solve_damped), and the systems the GPU
-tests feed them.
+"""Extended-precision reference for the LM step solves of the solver kernels (lfr_debug_solve_damped, lfr_debug_solve_tree), and the
+systems the GPU tests feed them.
 
 The kernels solve the damped normal equations (A + D) y = g.  The damped matrix is formed here in float64 exactly as each kernel
 forms it - packed classes: a_ii + dd (one addition), workgroup classes: a_ii + d_i * d_i (one fused multiply-add, one rounding) -
+elimination-tree kernel ("tree"): a_ii + round(d_i * d_i), the column task's product and sum, two roundings -
 and then solved in np.longdouble (80-bit on x86-64: a 64-bit mantissa, 2^11 times finer than float64) by Gaussian elimination with
 partial pivoting, so that the reference's own error lies three orders of magnitude below any float64 solve of the same system."""
 from fractions import Fraction
@@ -34,8 +35,13 @@ def from_tri(t, n):
 
 # ---- the damped matrix, as the kernels form it ----
 def damped(A, damp, solver):
-    """float64 A + D: packed solvers add damp_i to a_ii, the workgroup solvers damp_i * damp_i with one rounding."""
+    """float64 A + D: packed solvers add damp_i to a_ii, the workgroup solvers damp_i * damp_i with one rounding, the elimination-tree
+    kernel ("tree") the rounded product damp_i * damp_i."""
     M = np.array(A, np.float64, copy=True)
+    if solver == "tree":
+        d = np.asarray(damp, np.float64)
+        M[np.diag_indices_from(M)] = np.diag(M) + d * d
+        return M
     for i in range(M.shape[0]):
         if solver in PACKED:
             M[i, i] = M[i, i] + damp[i]
@@ -62,6 +68,31 @@ def solve_ld(M, g):
     y = np.zeros(n, LD)
     for k in range(n - 1, -1, -1):
         y[k] = (W[k, n] - np.dot(W[k, k + 1:n], y[k + 1:])) / W[k, k]
+    return y
+
+
+def solve_refined(M, g, rounds=8):
+    """The same solution for SPD systems of thousands of rows, where solve_ld's elimination in longdouble is out of reach: a float64
+    LAPACK Cholesky factorization, then iterative refinement with longdouble residuals and updates until the correction stops
+    shrinking (as covariance_ref.inverse_refined).  Accepted when the longdouble residual is that of a backward-stable longdouble
+    solve, |g - M y| <= 16 n 2^-64 (|M| |y| + |g|) in max norms; raises otherwise.  tests/test_linsolve_ref.py pins it to solve_ld."""
+    import scipy.linalg as sla
+    n = M.shape[0]
+    M = np.asarray(M, np.float64)
+    c = sla.cho_factor(M, lower=True)
+    Mld, gld = M.astype(LD), np.asarray(g, np.float64).astype(LD)
+    y = sla.cho_solve(c, np.asarray(g, np.float64)).astype(LD)
+    prev = np.inf
+    for _ in range(rounds):
+        dy = sla.cho_solve(c, (gld - Mld @ y).astype(np.float64)).astype(LD)
+        y = y + dy
+        size = float(np.max(np.abs(dy)))
+        if size <= 2.0 ** -62 * float(np.max(np.abs(y))) or size > 0.25 * prev:
+            break
+        prev = size
+    res = float(np.max(np.abs(gld - Mld @ y)))
+    if not res <= 16.0 * n * 2.0 ** -64 * (float(np.max(np.sum(np.abs(M), 1))) * float(np.max(np.abs(y))) + float(np.max(np.abs(g)))):
+        raise np.linalg.LinAlgError("iterative refinement did not reach a longdouble-stable residual")
     return y
 
 
@@ -158,3 +189,47 @@ def packed_cl(solver, nv2_max):
         return [c for c in (18, 20, 22, 24) if nv2_max <= c or c == 24][0]
     c_hi = (nv2_max + 1) // 2                      # <32,2,5>: two lanes per row
     return ("lpr2", [c for c in (10, 12, 14, 16) if c_hi <= c or c == 16][0])
+
+
+# ---- the elimination-tree kernel's tile layout (plan: tree_plan_emul.Plan) ----
+def to_tiles(plan, M):
+    """A dense symmetric matrix in the plan's (padded) matrix order -> [n_tiles, 16, 16]: tile t holds rows of block rowsof[t] and
+    columns of the block J with colptr[J] <= t < colptr[J + 1]; of a diagonal tile the lower triangle, as the sweep stores it.  Raises
+    when M has an entry outside the plan's tiles."""
+    M = np.asarray(M, np.float64)
+    tiles = np.zeros((plan.n_tiles, 16, 16))
+    for J in range(plan.NB):
+        for t in range(plan.colptr[J], plan.colptr[J + 1]):
+            I = int(plan.rowsof[t])
+            blk = M[16 * I:16 * I + 16, 16 * J:16 * J + 16]
+            tiles[t] = np.tril(blk) if I == J else blk
+    if not np.array_equal(from_tiles(plan, tiles), M):
+        raise ValueError("the matrix is not symmetric with the plan's block sparsity")
+    return tiles
+
+
+def from_tiles(plan, tiles):
+    """The inverse of to_tiles: the dense symmetric matrix of [n_tiles, 16, 16] tiles."""
+    L = np.zeros((plan.n_pad, plan.n_pad))
+    for J in range(plan.NB):
+        for t in range(plan.colptr[J], plan.colptr[J + 1]):
+            I = int(plan.rowsof[t])
+            L[16 * I:16 * I + 16, 16 * J:16 * J + 16] = tiles[t]
+    return L + np.tril(L, -1).T
+
+
+def real_rows(plan):
+    """Mask over the n_pad matrix rows: True at the two rows of every node position that holds a node (the rest is padding)."""
+    return np.repeat(plan.ipos != 0xFFFFFFFF, 2)
+
+
+def solve_ref(M, g):
+    """solve_ld up to 200 rows, solve_refined above."""
+    return solve_ld(M, g) if M.shape[0] <= 200 else solve_refined(M, g)
+
+
+def emulate_tree(plan, A, damp, g):
+    """The plan executed in float64 on the CPU (tree_plan_emul: the kernel's algorithm, plain numpy): y of (A + D) y = g, n_pad long."""
+    tiles = to_tiles(plan, damped(A, damp, "tree"))
+    ft, w, inv = plan.factor(tiles, np.asarray(g, np.float64))
+    return plan.back_substitute(ft, w, inv)

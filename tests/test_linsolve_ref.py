@@ -85,3 +85,104 @@ def test_cl_dispatch_replica():
     assert [R.packed_cl("g16", n) for n in (2, 10, 12, 14, 16)] == [10, 10, 12, 14, 16]
     assert [R.packed_cl("g64_2", n) for n in (2, 18, 20, 22, 24)] == [18, 18, 20, 22, 24]
     assert R.packed_cl("g64_4", 32) == ("lpr2", 16)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# the elimination-tree kernel's solve (tests/test_gpu_tree_solve.py): reference, tile layout, and the inputs checked before a GPU sees them
+# ---------------------------------------------------------------------------------------------------------------------------
+def test_tree_damping_as_the_column_task_forms_it():
+    a = np.array([[2.0 ** 24, 0.5], [0.5, 3.0]])
+    d = np.array([1.0 + 2.0 ** -30, 3.0])
+    # two roundings: the product (1 + 2^-30)^2 loses its 2^-60, and the sum 2^24 + 1 + 2^-29 is then a tie that goes to even; the
+    # workgroup solvers' single rounding sees the 2^-60 and goes up
+    Mt = R.damped(a, d, "tree")
+    assert Mt[0, 0] == 2.0 ** 24 + 1.0 and Mt[1, 1] == 12.0 and Mt[0, 1] == 0.5
+    assert R.damped(a, d, "block_m")[0, 0] == 2.0 ** 24 + 1.0 + 2.0 ** -28
+
+
+@pytest.mark.parametrize("kind", ["normal", "graded", "cond1e8"])
+def test_refined_solve_matches_the_elimination_in_longdouble(kind):
+    """solve_refined (float64 Cholesky + longdouble refinement) against solve_ld, and against mpmath on the small sizes."""
+    rng = np.random.default_rng(21)
+    for n in (2, 6, 16, 40, 130):
+        A = {"normal": lambda: R.normal_matrix(rng, n), "graded": lambda: R.graded(rng, n, 1e3, 1e3),
+             "cond1e8": lambda: R.spd_with_cond(rng, n, 1e8)}[kind]()
+        M = R.damped(A, np.sqrt(1e-3 * np.diag(A)), "tree")
+        g = rng.normal(0, 1, n)
+        y, yl = R.solve_refined(M, g), R.solve_ld(M, g)
+        kappa = float(np.linalg.cond(M, np.inf))
+        ynorm = float(np.max(np.abs(yl)))
+        assert float(np.max(np.abs(y - yl))) <= 8 * n * 2.0 ** -64 * kappa * ynorm, (n, kappa)
+        if n <= 16:
+            ym = _mp_solve(M, g)
+            with mpmath.workdps(50):
+                err = max(abs(_mp_exact(y[i]) - ym[i]) for i in range(n))
+            assert float(err) <= 4 * n * 2.0 ** -64 * kappa * ynorm, (n, float(err), kappa)
+
+
+@pytest.fixture(scope="module")
+def tree_cases(lfr_lib):
+    import tree_solve_cases as C
+    structs = C.structures()
+    return C, structs, C.plans(structs)
+
+
+def test_tile_layout_round_trip(tree_cases):
+    C, structs, pls = tree_cases
+    for name in ("dense_track", "chords", "comb"):
+        pl = pls[name]
+        A, _ = C.jtj(pl, *structs[name], np.random.default_rng(31))
+        tiles = R.to_tiles(pl, A)
+        assert tiles.shape == (pl.n_tiles, 16, 16) and np.array_equal(R.from_tiles(pl, tiles), A)
+        assert not np.triu(tiles[pl.colptr[0]], 1).any()                       # of a diagonal tile the lower triangle
+        real = R.real_rows(pl)
+        assert not A[~real].any() and (np.diag(A)[real] > 0).all()
+        B = A.copy()
+        far = [(i, j) for i in range(pl.NB) for j in range(i) if j not in pl.rowsof[pl.colptr[j]:pl.colptr[j + 1]].tolist()
+               and i not in pl.rowsof[pl.colptr[j]:pl.colptr[j + 1]].tolist()]
+        if far:
+            i, j = far[0]
+            B[16 * i, 16 * j] = B[16 * j, 16 * i] = 1.0
+            with pytest.raises(ValueError):
+                R.to_tiles(pl, B)
+
+
+def test_tree_structures_reach_every_path_of_the_kernel(tree_cases):
+    """What tests/test_gpu_tree_solve.py relies on, from the plans' words (it asserts the same on the GPU box)."""
+    C, structs, pls = tree_cases
+    C.assert_coverage(pls)
+
+
+def test_tree_emulator_meets_the_bounds_of_the_gpu_test(tree_cases):
+    """scatter -> Plan.factor -> Plan.back_substitute in float64 (the kernel's algorithm in plain numpy) reproduces the reference
+    within the bounds the GPU test asserts: the systems are well posed before any GPU sees them."""
+    C, structs, pls = tree_cases
+    worst = {}
+    for name, kind, sysm in C.corpus(structs, pls):
+        pl = pls[name]
+        y = R.emulate_tree(pl, *sysm)
+        assert not y[~R.real_rows(pl)].any()
+        f, b = C.errors(pl, C.reference(pl, sysm), y)
+        w = worst.setdefault(C.FAMILY[name], [0.0, 0.0])
+        w[0], w[1] = max(w[0], f), max(w[1], b)
+        print("%-14s %-9s forward %.3f of its bound, backward %.3f of 8 n u" % (name, kind, f, b))
+        assert f <= 1.0 and b <= 1.0, (name, kind, f, b)
+    print(worst)
+
+
+def test_bad_pivot_cases_have_the_pivot_they_claim(tree_cases):
+    """Eliminating the real rows in matrix order: every pivot before the chosen row is positive, the chosen one is not."""
+    C, structs, pls = tree_cases
+    cases = C.bad_pivot_cases(structs, pls)
+    assert {w.replace("_zero", "") for _, w, _, _ in cases} == {"first_level", "root", "half_filled", "through_tile"}
+    assert any(w.endswith("_zero") for _, w, _, _ in cases)
+    for name, where, row, (A, damp, g) in cases:
+        pl = pls[name]
+        real = R.real_rows(pl)
+        idx = np.nonzero(real)[0]
+        W = R.damped(A, damp, "tree")[np.ix_(idx, idx)]
+        k = int(np.nonzero(idx == row)[0][0])
+        for j in range(k):
+            assert W[j, j] > 0, (name, where, j)
+            W[j + 1:, j:] -= np.outer(W[j + 1:, j] / W[j, j], W[j, j:])
+        assert (W[k, k] == 0.0) if where.endswith("_zero") else (W[k, k] < 0), (name, where, W[k, k])

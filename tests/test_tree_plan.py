@@ -81,9 +81,7 @@ def test_chain_of_tracks_becomes_a_shallow_tree(lfr_lib):
     assert info["column_rounds"] <= info["blocks"] // 8 + 2 * info["levels"]
 
 
-def test_random_tree_of_tracks_with_cycles(lfr_lib):
-    rng = np.random.default_rng(5)
-    T = 120
+def _random_tree_of_tracks_with_cycles(rng, T=120):
     sizes = rng.integers(1, 11, size=T)
     off = np.r_[0, np.cumsum(sizes)]
     n_var = int(off[-1])
@@ -103,18 +101,18 @@ def test_random_tree_of_tracks_with_cycles(lfr_lib):
         t, u = rng.integers(T, size=2)
         if t != u:
             a.append(off[t] + int(rng.integers(sizes[t]))); b.append(off[u] + int(rng.integers(sizes[u]))); k.append(1)
-    w = _by_source(_words(a, b, k))
+    return n_var, _by_source(_words(a, b, k))
+
+
+def test_random_tree_of_tracks_with_cycles(lfr_lib):
+    n_var, w = _random_tree_of_tracks_with_cycles(np.random.default_rng(5))
     pl, info, lvl = _run(n_var, w, seed=1)
     assert info["levels"] <= 40
     assert info["tiles"] < 0.25 * info["blocks"] * (info["blocks"] + 1) // 2
 
 
-def test_duplicated_matches_and_a_long_dense_track(lfr_lib):
-    """a 44-node all-pairs track (a dense chain of blocks: every column has many rows -> extra-row tasks) plus short tracks with
-    duplicated matches hanging off it"""
-    rng = np.random.default_rng(9)
+def _long_dense_track_with_short_tracks(rng, L=44):
     a, b, k = [], [], []
-    L = 44
     for i in range(L):
         for j in range(i + 1, L):
             a.append(i); b.append(j); k.append(0)
@@ -130,15 +128,18 @@ def test_duplicated_matches_and_a_long_dense_track(lfr_lib):
         a.append(base); b.append(int(rng.integers(L))); k.append(1)
         a.append(base); b.append(b[-1]); k.append(1)                              # the inter-track match twice
         n_var += sz
-    w = _by_source(_words(a, b, k))
+    return n_var, _by_source(_words(a, b, k))
+
+
+def test_duplicated_matches_and_a_long_dense_track(lfr_lib):
+    """a 44-node all-pairs track (a dense chain of blocks: every column has many rows -> extra-row tasks) plus short tracks with
+    duplicated matches hanging off it"""
+    n_var, w = _long_dense_track_with_short_tracks(np.random.default_rng(9))
     pl, info, lvl = _run(n_var, w, seed=2)
     assert pl.x_ptr[-1] > 0                                      # the dense track's columns have more than three rows below the diagonal
 
 
-def test_dense_meta_graph_falls_back_to_one_segment(lfr_lib):
-    """tracks matched to (nearly) every other track: no separator exists; the plan must still be valid"""
-    rng = np.random.default_rng(11)
-    T, L = 14, 3
+def _dense_meta_graph(rng, T=14, L=3):
     a, b, k = [], [], []
     for t in range(T):
         for i in range(L):
@@ -148,15 +149,24 @@ def test_dense_meta_graph_falls_back_to_one_segment(lfr_lib):
         for u in range(t + 1, T):
             if rng.random() < 0.8:
                 a.append(t * L + int(rng.integers(L))); b.append(u * L + int(rng.integers(L))); k.append(1)
-    w = _by_source(_words(a, b, k))
-    _run(T * L, w, seed=3)
+    return T * L, _by_source(_words(a, b, k))
+
+
+def test_dense_meta_graph_falls_back_to_one_segment(lfr_lib):
+    """tracks matched to (nearly) every other track: no separator exists; the plan must still be valid"""
+    n_var, w = _dense_meta_graph(np.random.default_rng(11))
+    _run(n_var, w, seed=3)
+
+
+def _tracks_linked_only_through_a_constant(rng, T=6, L=4, links=1):
+    n_var, w1 = _chain_of_tracks(T, L, rng, links=links, shuffle=False)
+    a = list(range(0, T * L, L)); b = [T * L] * T                # every track's first node matched to one constant
+    return n_var, _by_source(np.concatenate([w1, _words(a, b, [0] * T)]))
 
 
 def test_variable_nodes_linked_only_through_constants(lfr_lib):
     """the variable nodes of a component may fall apart once the roots are constants: independent trees, one plan"""
-    n_var, w1 = _chain_of_tracks(6, 4, np.random.default_rng(13), shuffle=False)
-    a = list(range(0, 24, 4)); b = [24] * 6                      # every track's first node matched to one constant
-    w = _by_source(np.concatenate([w1, _words(a, b, [0] * 6)]))
+    n_var, w = _tracks_linked_only_through_a_constant(np.random.default_rng(13))
     pl, info, lvl = _run(n_var, w, seed=4)
 
 
