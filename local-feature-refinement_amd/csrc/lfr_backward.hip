@@ -1,6 +1,6 @@
 // Implicit-gradient backward pass through the batched LM solve (lfr_batch_backward, include/lfr.h).
-// Included at the end of lfr_solve.hip: it reads the batch layout (lfr_batch, CompInfoDev, ensure_mirrors) that lives there and
-// changes nothing the forward kernels read.
+// A translation unit of its own: it reads the batch layout (lfr_batch.hpp) and changes nothing the forward kernels read.  The Hessian's
+// assembly and LDL^T are shared with the covariance (lfr_hessian_device.hpp).
 //
 // Per solved component, one workgroup:
 //   1. the EXACT Hessian H of F = sum_e 1/2 w_e rho(|r_e|^2) over the free coordinates at the solve's x (owner computes: the thread of a
@@ -11,210 +11,23 @@
 //      marks the component indefinite: its gradient stays zero;
 //   3. the vector-Jacobian sweep: one thread per record writes -d/dtheta_e [v . grad F_e] into the match layout of the graph.
 // The packed lower triangle of H lives in LDS for the classes of up to 192 rows (<= 148 KB) and in an HBM workspace above.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <memory>
+#include <cstring>
+#include <vector>
+
+#include "lfr_batch.hpp"
+#include "lfr_hessian_device.hpp"
+
+using namespace lfrdev;
+using lfr::ensure_mirrors;
 
 namespace {
 
 constexpr int kBwdThreadsSmall = 64;         // packed classes (<= 32 rows): one wave per component
 constexpr int kBwdThreads = 256;             // workgroup classes
-constexpr int kBwdMaxRows = 6144;            // largest system of the HBM variant: its vectors fill the LDS (lfr.h: LFR_ERR_UNSUPPORTED above)
-
-// Derivatives of the biquadratic interpolant (cost.cc:13-48) at the source point, with the reference's zeroing of the first derivative
-// outside [-0.5, 0.5] (cost.cc:38-43) carried over to the second derivatives.
-struct BwdEdge {
-    double lr[3], dlr[3], d2lr[3], lc[3], dlc[3], d2lc[3];
-    double f[2], fr[2], fc[2], frr[2], frc[2], fcc[2];
-    double r[2], w, rho1, rho2;
-};
-
-__device__ __forceinline__ void bwd_basis(double x, double (&l)[3], double (&dl)[3], double (&d2l)[3]) {
-    const double t = fmax(fmin(x, 0.5), -0.5);
-    const bool in = (t == x);
-    l[0] = 2. * t * (t - .5); l[1] = (-4.) * (t - .5) * (t + .5); l[2] = 2. * t * (t + .5);
-    dl[0] = in ? 2. * t + 2. * (t - .5) : 0.; dl[1] = in ? (-4.) * (t - .5) + (-4.) * (t + .5) : 0.; dl[2] = in ? 2. * t + 2. * (t + .5) : 0.;
-    d2l[0] = in ? 4. : 0.; d2l[1] = in ? -8. : 0.; d2l[2] = in ? 4. : 0.;
-}
-
-__device__ __forceinline__ void bwd_eval(const EdgeRec &e, int kind, int tukey_variant, double x1r, double x1c, double x2r, double x2c,
-                                         BwdEdge &o) {
-    bwd_basis(x1r, o.lr, o.dlr, o.d2lr);
-    bwd_basis(x1c, o.lc, o.dlc, o.d2lc);
-#pragma unroll
-    for (int k = 0; k < 2; ++k) { o.f[k] = o.fr[k] = o.fc[k] = o.frr[k] = o.frc[k] = o.fcc[k] = 0.; }
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-        for (int j = 0; j < 3; ++j)
-#pragma unroll
-            for (int k = 0; k < 2; ++k) {
-                const double d = (double)e.flow[2 * (3 * i + j) + k];
-                o.f[k] += o.lr[i] * o.lc[j] * d;
-                o.fr[k] += o.dlr[i] * o.lc[j] * d;
-                o.fc[k] += o.lr[i] * o.dlc[j] * d;
-                o.frr[k] += o.d2lr[i] * o.lc[j] * d;
-                o.frc[k] += o.dlr[i] * o.dlc[j] * d;
-                o.fcc[k] += o.lr[i] * o.d2lc[j] * d;
-            }
-    o.r[0] = x2r - x1r - o.f[0];
-    o.r[1] = x2c - x1c - o.f[1];
-    const double s = o.r[0] * o.r[0] + o.r[1] * o.r[1];
-    o.w = (double)e.sim;
-    if (kind == 0) {                                   // CauchyLoss(0.25)
-        const double inv = 1.0 / (1.0 + s * kCauchyC);
-        o.rho1 = fmax(DBL_MIN, inv);
-        o.rho2 = -kCauchyC * inv * inv;
-    } else if (s <= kTukeyA2) {                        // TukeyLoss(0.0625), Ceres 1.x (1) or 2.x (2)
-        const double v = 1.0 - s / kTukeyA2;
-        o.rho1 = tukey_variant == 1 ? 0.5 * v * v : v * v;
-        o.rho2 = tukey_variant == 1 ? -v / kTukeyA2 : -2.0 * v / kTukeyA2;
-    } else {
-        o.rho1 = 0.; o.rho2 = 0.;
-    }
-}
-
-// M = w (rho' I + 2 rho'' r r^T), P = I + df/dx_src: the edge's Hessian over (x_src, x_dst) is [[P^T M P - w rho' sum_k r_k d2f_k, -P^T M],
-// [-M P, M]].
-template <bool EXACT = true>
-__device__ __forceinline__ void bwd_blocks(const BwdEdge &o, double (&M)[2][2], double (&P)[2][2]) {
-    const double a = o.w * o.rho1, b = EXACT ? 2.0 * o.w * o.rho2 : 0.0;      // (not EXACT: M = w rho' I, the Gauss-Newton part)
-    M[0][0] = a + b * o.r[0] * o.r[0]; M[0][1] = b * o.r[0] * o.r[1]; M[1][0] = M[0][1]; M[1][1] = a + b * o.r[1] * o.r[1];
-    P[0][0] = 1.0 + o.fr[0]; P[0][1] = o.fc[0]; P[1][0] = o.fr[1]; P[1][1] = 1.0 + o.fc[1];
-}
-
-struct BwdArgs {
-    const CompDesc *descs;
-    const EdgeRec *edges;
-    const uint32_t *node_ids;
-    const lfr::NodeInc *node_inc;
-    const uint32_t *in_idx;
-    const double *positions;
-    const CompInfoDev *infos;
-    const double *grad_pos;       // dL/dx of the whole graph (2 per node)
-    const uint32_t *eid;          // per record: directed edge id of the graph (2m: node1 -> node2, 2m+1: node2 -> node1)
-    double *hws;                  // HBM variant: packed lower triangles
-    const uint64_t *hws_off;      // per descriptor (doubles)
-    void *g_disp1, *g_disp2;      // n_matches x 18, float or double
-    double *g_sim_dir;            // per directed edge
-    int32_t *status;              // per descriptor
-    unsigned long long *counters; // [0] coordinates held at a bound
-    uint32_t n_matches;
-    int desc_begin, tukey_variant, f64;
-    int scan_all;                 // records in edge-id order (packed classes): no out-edge runs
-};
-
-__host__ __device__ __forceinline__ size_t bwd_tri(int i, int j) { return (size_t)i * (i + 1) / 2 + j; }     // j <= i
-
-// The matrix of a component's normal equations, lower triangle, owner computes: the thread of node l owns rows 2l, 2l+1 (columns of
-// nodes <= l) and sums them over the node's out- and in-edges in record order.  EXACT: the backward's Hessian (rho'' and the
-// interpolant's second derivatives included; coordinates with fr[i] == 0 become identity rows and columns); otherwise the loss-corrected
-// Gauss-Newton matrix J^T J = sum_e w rho' [[P^T P, -P^T], [-P, I]] of the covariance (lfr_covariance_impl.hpp), which ignores the bounds.
-template <int T, bool EXACT>
-__device__ __forceinline__ void bwd_assemble(const BwdArgs &a, const CompDesc &d, const int nv, const EdgeRec *E, const uint32_t *ids,
-                                             double *H, const uint8_t *fr, const int tid) {
-    // The workgroup classes' records come by source node (out-edges contiguous, NodeInc); the packed classes' in edge-id order: a thread scans them all (<= 320)
-    auto xof = [&](int m, int c) -> double { return m < nv ? a.positions[2 * (size_t)ids[m] + c] : 0.0; };
-    for (int l = tid; l < nv; l += T) {
-        lfr::NodeInc ni = a.node_inc[d.node_off + l];
-        if (a.scan_all) { ni.out_begin = 0; ni.out_count = d.n_edges; ni.in_count = 0; }
-        const double xr = xof(l, 0), xc = xof(l, 1);
-        double hd[3] = {0., 0., 0.};                          // (2l,2l) (2l+1,2l) (2l+1,2l+1)
-        for (uint32_t k = 0; k < ni.out_count; ++k) {         // l -> m (packed classes: and m -> l)
-            const EdgeRec e = E[ni.out_begin + k];
-            const int m = e.dst_kind & 0x7fff, kind = e.dst_kind >> 15;
-            if (a.scan_all && e.src != l) {
-                if (m != l) continue;
-                const int sm = e.src;                         // in-edge sm -> l
-                BwdEdge o;
-                bwd_eval(e, kind, a.tukey_variant, xof(sm, 0), xof(sm, 1), xr, xc, o);
-                double M[2][2], P[2][2];
-                bwd_blocks<EXACT>(o, M, P);
-                hd[0] += M[0][0]; hd[1] += M[1][0]; hd[2] += M[1][1];
-                if (sm < l) {
-#pragma unroll
-                    for (int p = 0; p < 2; ++p)
-#pragma unroll
-                        for (int q = 0; q < 2; ++q) H[bwd_tri(2 * l + p, 2 * sm + q)] -= M[p][0] * P[0][q] + M[p][1] * P[1][q];
-                }
-                continue;
-            }
-            BwdEdge o;
-            bwd_eval(e, kind, a.tukey_variant, xr, xc, xof(m, 0), xof(m, 1), o);
-            double M[2][2], P[2][2];
-            bwd_blocks<EXACT>(o, M, P);
-            double PM[2][2], S[2][2];                         // P^T M, P^T M P - w rho' sum_k r_k d2f_k
-#pragma unroll
-            for (int p = 0; p < 2; ++p)
-#pragma unroll
-                for (int q = 0; q < 2; ++q) PM[p][q] = P[0][p] * M[0][q] + P[1][p] * M[1][q];
-            const double c = o.w * o.rho1;
-#pragma unroll
-            for (int p = 0; p < 2; ++p)
-#pragma unroll
-                for (int q = 0; q < 2; ++q) S[p][q] = PM[p][0] * P[0][q] + PM[p][1] * P[1][q];
-            if constexpr (EXACT) {
-                S[0][0] -= c * (o.r[0] * o.frr[0] + o.r[1] * o.frr[1]);
-                S[1][0] -= c * (o.r[0] * o.frc[0] + o.r[1] * o.frc[1]);
-                S[1][1] -= c * (o.r[0] * o.fcc[0] + o.r[1] * o.fcc[1]);
-            }
-            hd[0] += S[0][0]; hd[1] += S[1][0]; hd[2] += S[1][1];
-            if (m < l) {                                      // src-dst block: -P^T M
-#pragma unroll
-                for (int p = 0; p < 2; ++p)
-#pragma unroll
-                    for (int q = 0; q < 2; ++q) H[bwd_tri(2 * l + p, 2 * m + q)] -= PM[p][q];
-            }
-        }
-        for (uint32_t k = 0; k < ni.in_count; ++k) {          // m -> l
-            const EdgeRec e = E[a.in_idx[d.edge_off + ni.in_begin + k]];
-            const int m = e.src, kind = e.dst_kind >> 15;
-            BwdEdge o;
-            bwd_eval(e, kind, a.tukey_variant, xof(m, 0), xof(m, 1), xr, xc, o);
-            double M[2][2], P[2][2];
-            bwd_blocks<EXACT>(o, M, P);
-            hd[0] += M[0][0]; hd[1] += M[1][0]; hd[2] += M[1][1];
-            if (m < l) {                                      // dst-src block: -M P
-#pragma unroll
-                for (int p = 0; p < 2; ++p)
-#pragma unroll
-                    for (int q = 0; q < 2; ++q) H[bwd_tri(2 * l + p, 2 * m + q)] -= M[p][0] * P[0][q] + M[p][1] * P[1][q];
-            }
-        }
-        H[bwd_tri(2 * l, 2 * l)] += hd[0]; H[bwd_tri(2 * l + 1, 2 * l)] += hd[1]; H[bwd_tri(2 * l + 1, 2 * l + 1)] += hd[2];
-        if constexpr (EXACT)
-            for (int p = 0; p < 2; ++p) {                     // bound coordinates: identity rows and columns
-                const int i = 2 * l + p;
-                for (int j = 0; j <= i; ++j)
-                    if (!fr[i] || !fr[j]) H[bwd_tri(i, j)] = (i == j) ? 1.0 : 0.0;
-            }
-    }
-}
-
-// LDL^T of the packed lower triangle H (n rows), right-looking over the nonzeros of each column (D on the diagonal, L below it).
-// lval / lidx: n entries of scratch, cnt: two counters (cnt[0] = cnt[1] = 0 on entry).  Returns true when a pivot was not positive
-// (or not finite); every thread returns the same.
-template <int T>
-__device__ __forceinline__ bool bwd_ldlt(double *H, const int n, double *lval, int *lidx, int *cnt, const int tid) {
-    bool indefinite = false;
-    for (int k = 0; k < n; ++k) {
-        const double dk = H[bwd_tri(k, k)];
-        if (!(dk > 0.0) || !isfinite(dk)) { indefinite = true; break; }       // (uniform: every thread read the same pivot)
-        const double dinv = 1.0 / dk;
-        int *c = &cnt[k & 1];
-        for (int i = k + 1 + tid; i < n; i += T) {
-            const double x = H[bwd_tri(i, k)];
-            if (x != 0.0) { const int p = atomicAdd(c, 1); lidx[p] = i; lval[p] = x; }
-        }
-        __syncthreads();
-        const int nc = *c;
-        if (tid == 0) cnt[(k + 1) & 1] = 0;
-        for (int t = tid; t < nc * nc; t += T) {
-            const int p = t / nc, q = t - p * nc, i = lidx[p], j = lidx[q];
-            if (j <= i) H[bwd_tri(i, j)] -= lval[p] * (lval[q] * dinv);
-        }
-        for (int p = tid; p < nc; p += T) H[bwd_tri(lidx[p], k)] = lval[p] * dinv;
-        __syncthreads();
-    }
-    return indefinite;
-}
 
 template <int T, bool LDS_MATRIX>
 __global__ __launch_bounds__(T) void backward_kernel(const BwdArgs a) {
@@ -456,10 +269,7 @@ int lfr_batch_backward(lfr_batch *b, const double *grad_positions_device, void *
     const size_t M = (size_t)b->n_graph_matches, elt = f64 ? 8 : 4;
     HIP_TRY(hipStreamWaitEvent(st, b->ev[1], 0));                               // the latest solve's positions and termination codes
     HIP_TRY(hipEventRecord(s.ev0, st));
-    if (b->fused && b->packed_edges)         // the packed records have not been written yet: write them (the next solve would write the same bytes)
-        hipLaunchKernelGGL(k_materialize_records, dim3((unsigned)(((uint64_t)5 * b->packed_edges + 255) / 256)), dim3(256), 0, st, b->packed_edges,
-                           b->d_edge_ref, b->d_edge_word, b->dev_hold->graph->flow_row, b->dev_hold->graph->disp1, b->dev_hold->graph->disp2,
-                           b->dev_hold->graph->sim, reinterpret_cast<uint4 *>(b->d_edges));
+    if (b->fused) lfr::materialize_records(b, st);     // the packed records have not been written yet: write them (the next solve would write the same bytes)
     if (M) {
         HIP_TRY(hipMemsetAsync(grad_disp1_device, 0, 18 * M * elt, st));
         HIP_TRY(hipMemsetAsync(grad_disp2_device, 0, 18 * M * elt, st));

@@ -1,0 +1,212 @@
+// What the solver's translation units share (internal): the kernel argument blocks, the batch (lfr_batch, include/lfr.h's opaque
+// handle) and the host-side interface between them.  No kernel bodies.
+//   lfr_solve.hip        the forward kernels, their debug probes, and the launch functions declared at the end of this header
+//   lfr_batch.hip        batch creation, the launch plan of lfr_batch_solve, timing, downloads, warm-up, multi-GPU entry points
+//   lfr_backward.hip     implicit-gradient backward pass (lfr_batch_backward)
+//   lfr_covariance.hip   per-keypoint covariance (lfr_batch_covariance)
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+#include <memory>
+#include <vector>
+
+#include "lfr_internal.hpp"
+
+#define HIP_TRY(expr)                                                                         \
+    do {                                                                                      \
+        hipError_t _e = (expr);                                                               \
+        if (_e != hipSuccess) {                                                               \
+            lfr::set_error("%s failed: %s", #expr, hipGetErrorString(_e));                    \
+            return LFR_ERR_HIP;                                                               \
+        }                                                                                     \
+    } while (0)
+
+namespace lfr {
+
+struct CompInfoDev {
+    int32_t iterations, termination, n_successful, n_ls_evals, n_cand_evals, exec_passes;
+    double final_cost;
+};
+static_assert(sizeof(CompInfoDev) == 32, "CompInfoDev layout");
+
+struct KernelArgs {
+    const CompDesc *descs;
+    const EdgeRec *edges;
+    const uint32_t *node_ids;
+    double *positions;          // 2 * n_nodes of the whole graph
+    CompInfoDev *infos;
+    const lfr::NodeInc *node_inc;   // parallel to node_ids
+    const uint32_t *in_idx;     // parallel to edges
+    double *workspace;          // workgroup kernels: per-edge scratch (+ packed matrices for the HBM variant)
+    const uint64_t *ws_off;     // per desc: packed-matrix offset (HBM variant)
+    const uint64_t *es_off;     // per desc: per-edge scratch offset (8 doubles per edge)
+    unsigned long long *prof;   // -DLFR_PROFILE_PHASES: per-class cycle counters [cls*8 + phase]
+    unsigned int *queue;        // workgroup classes: next component of the class (one counter per class, zeroed per solve)
+    const uint32_t *wg_order;   // workgroup classes: descriptors in the order the queue hands them out (longest expected first)
+    int wg_begin;               // first descriptor of the workgroup classes (wg_order[0] belongs to it)
+    int desc_begin, desc_end;
+    int tukey_variant;
+    int scratch_sweep;         // 1: the workgroup kernels use the scratch sweep of rounds 1-2 (LFR_SCRATCH_SWEEP=1 at batch creation; A/B and tests)
+    int cls;
+    // fused gather (packed classes of a device-assembled whole batch): record p is directed edge edge_ref[p] of the graph - flow row
+    // (f_row ? f_row[m] : m) of f_disp2 (even ids) / f_disp1 (odd ids), similarity f_sim[m], m = id >> 1 - with local indices edge_word[p]
+    const uint32_t *edge_ref, *edge_word, *f_row;
+    const float *f_disp1, *f_disp2, *f_sim;
+    // elimination-tree class: teams of workgroups per component (nullptr: one workgroup per component); team_work[k]: smallest
+    // hand-out key (k_wg_order_keys' `work`) solved by 2 << k workgroups
+    unsigned int *team_ctl;
+    double *team_red;
+    uint32_t team_work[3];
+    uint32_t team_epoch;        // differs between launches that share the reduction slots
+    uint32_t team_patience_us;  // teams that cannot form for this long with nobody at work: the launch goes on one workgroup per component (LFR_TEAM_PATIENCE_MS)
+    unsigned long long *trace;  // -DLFR_TRACE_TREE: [0] = words used, then {s_memtime, type << 56 | wave of the team << 48 | iteration << 32 | column} pairs
+};
+
+// solve_packed_kernel / covariance_packed_kernel: blocks [blk_begin[i], blk_begin[i+1]) of the one launch belong to packed class i
+struct PackedRanges {
+    int blk_begin[6];          // G64_4, G64_2, G32, G16, G8 in dispatch order
+    int desc_begin[5], desc_end[5];
+};
+
+// ---- lfr_solve.hip: the forward kernels' launch functions.  The caller (the launch plan of lfr_batch_solve) chooses streams, events,
+// grids and the order; template arguments, block sizes and dynamic LDS are chosen beside the kernels.  Errors: hipGetLastError(). ----
+// Compile-time constants of the kernels (-DLFR_PACKED_WAVES, -DLFR_THREADS_*, -DLFR_TEAM_MAX) that size launches and workspaces.
+struct SolveGeometry {
+    int packed_waves;                    // waves per workgroup of the packed kernels
+    int comps_per_block[KC_COUNT];       // components a workgroup of the class hosts
+    int threads_s, threads_m, threads_l, threads_g;      // workgroup sizes of KC_BLOCK, KC_BLOCK_M, KC_BLOCK_L, KC_GLOBAL
+    int team_max, team_units_per_xcc, team_ctl_words, team_red_per_unit;     // teams of the elimination-tree class (the comment above TeamCtx)
+};
+const SolveGeometry &solve_geometry();
+size_t block_lds_bytes(int max_rows);    // dynamic LDS of a workgroup-class launch whose largest system has max_rows rows
+int reserve_block_lds(int lds_s, int lds_m, int lds_l);      // hipFuncAttributeMaxDynamicSharedMemorySize of the three LDS classes
+void launch_packed(const KernelArgs &a, const PackedRanges &r, bool fused, int n_blocks, hipStream_t cs);       // solve_packed_kernel
+void launch_group_class(int cls, const KernelArgs &a, bool fused, int n_blocks, hipStream_t cs);                // one packed class (LFR_SERIAL_CLASSES=1)
+void launch_block_class(int cls, const KernelArgs &a, int rows, int wgs, hipStream_t cs);                       // solve_block_kernel of an LDS class
+void launch_tree(const KernelArgs &a, bool team, int grid, hipStream_t cs);                                     // solve_tree_kernel / solve_tree_team_kernel
+void launch_warmup();                    // an empty kernel of lfr_solve.hip: loads the forward kernels' code object
+
+}  // namespace lfr
+
+// =============================================================================================
+// the batch
+// =============================================================================================
+constexpr size_t kProfWords = 8 * lfr::KC_COUNT + 8 + 64;  // phase counters of -DLFR_PROFILE_PHASES + 16 32-bit class queues + -DLFR_PROFILE_FACTOR (16 per workgroup class)
+
+constexpr uint32_t kPackedEventsAliased = 1u << 31;     // ev_recorded: the packed launch is timed by the solve's own pair of events
+struct BwdState;                                        // lfr_backward.hip
+void bwd_free(BwdState *s);
+struct CovState;                                        // lfr_covariance.hip
+void cov_free(CovState *s);
+struct lfr_batch {
+    int device = 0;
+    lfr::DevCtx *ctx = nullptr;
+    int tukey_variant = LFR_TUKEY_CERES1;
+    int64_t n_graph_nodes = 0;
+    int shard_world = 1;
+    // launch geometry (device-assembled batches: read back once as AsmSummary)
+    int n_desc = 0;
+    int class_begin[lfr::KC_COUNT + 1] = {0};
+    int64_t class_edges[lfr::KC_COUNT] = {0};
+    int class_max_rows[lfr::KC_COUNT] = {0};          // largest system of every workgroup class (sizes its launch's LDS)
+    int64_t n_edges = 0, n_nodes = 0, n_tracks = 0;
+    // device: everything lives in `slab` (+ the workgroup kernels' workspace in `ws_slab`)
+    lfr::DevArena slab, ws_slab;
+    lfr::CompDesc *d_descs = nullptr;
+    lfr::EdgeRec *d_edges = nullptr;
+    uint32_t *d_node_ids = nullptr;
+    double *d_positions = nullptr;
+    lfr::CompInfoDev *d_infos = nullptr;
+    double *d_workspace = nullptr;
+    uint64_t es_doubles = 0;                             // per-edge scratch of the workgroup classes (8 doubles per edge), the head of the workspace
+    int tree_levels_max = 0;                             // KC_GLOBAL: levels of the deepest elimination tree
+    int64_t tree_blocks = 0, tree_updates = 0;           // KC_GLOBAL: 16-row columns / left-looking tile updates per factorization, summed over the class
+    int tree_begin = 0;                                  // first descriptor of the class; per component of the class: columns, tiles, 16x16x16 updates, levels, sweep items
+    // teams of workgroups per component (solve_tree_team_kernel): control words + reduction slots at the tail of the workspace,
+    // the work thresholds of teams of 2 / 4 / 8 (LFR_TREE_TEAM), the workgroups the class's components ask for together
+    unsigned int *d_team_ctl = nullptr;
+    double *d_team_red = nullptr;
+    uint32_t team_work[3] = {0xffffffffu, 0xffffffffu, 0xffffffffu};
+    int team_wgs = 0;
+    uint32_t team_patience_us = 50000u;                  // LFR_TEAM_PATIENCE_MS: the comment above TeamCtx (Residency)
+    std::vector<int64_t> tree_comp_stats;                // 5 per component
+    int64_t tree_tiles = 0, tree_dense_tiles = 0;          // KC_GLOBAL: 16x16 tiles stored / tiles of the dense lower triangles
+    uint64_t *d_ws_off = nullptr, *d_es_off = nullptr;
+    // fused gather: the packed kernel reads the graph's own flow arrays (kept alive through dev_hold)
+    bool fused = false;                                  // the NEXT solve gathers (true until the records have been materialised)
+    uint32_t packed_edges = 0;                           // records of the packed classes (the head of the edge array)
+    uint32_t *d_edge_ref = nullptr, *d_edge_word = nullptr;
+    std::shared_ptr<lfr::DevProblem> dev_hold;
+    unsigned long long *d_prof = nullptr;
+    lfr::NodeInc *d_node_inc = nullptr;
+    uint32_t *d_in_idx = nullptr;
+    uint32_t *d_desc_component = nullptr, *d_desc_class = nullptr, *d_desc_tracks = nullptr;   // device-assembled: behind the host mirrors
+    // host mirrors (host-assembled: filled at creation; device-assembled: fetched on first use)
+    bool mirrors_valid = false;
+    std::vector<lfr::CompDesc> descs;
+    std::vector<int64_t> desc_component;
+    std::vector<int32_t> desc_class, desc_tracks;
+    std::vector<uint32_t> node_ids;
+    // pinned staging of the positions (downloads, zero-copy view)
+    double *h_positions = nullptr;
+    size_t h_positions_bytes = 0;
+    float *h_positions_f32 = nullptr, *d_positions_f32 = nullptr;      // lfr_batch_positions_view_f32: converted on the device, half the copy
+    size_t h_positions_f32_bytes = 0, d_positions_f32_bytes = 0;
+    // events / streams
+    static constexpr int kSlots = 64;                    // event ring: timings of the last 64 solves
+    static constexpr int kEvPerSlot = 2 * (lfr::KC_COUNT + 1);
+    hipEvent_t ev_ring[kSlots * kEvPerSlot];
+    hipEvent_t *ev = ev_ring;                            // slot of the current solve
+    uint32_t ev_recorded[kSlots] = {};                   // per slot: classes whose start/end events were recorded
+    int64_t n_solves = 0;
+    bool serial = false;                               // LFR_SERIAL_CLASSES=1: all classes on the caller's stream
+    hipEvent_t ev_fork = nullptr;
+    lfr::DevArena order_slab;                          // hand-out order of the workgroup classes + the sort's temporaries
+    uint32_t *d_wg_order = nullptr;
+    hipEvent_t ev_order = nullptr;                     // the order is sorted on the context's stream: solves wait for it
+    hipStream_t side_stream = nullptr;                 // the packed launch runs beside the workgroup-per-component kernels
+    hipStream_t wg_stream[lfr::KC_COUNT] = {nullptr};  // one stream per further workgroup class (all owned by the device context)
+    hipStream_t last_stream = nullptr;                 // stream of the latest solve (downloads wait for it)
+    int packed_slot = 0;                               // class slot that carries the packed launch's events
+    double h2d_ms = 0.0;             // upload (host-assembled) or device assembly incl. waiting for the flows
+    std::vector<lfr::CompInfoDev> infos;      // last downloaded
+    bool infos_valid = false;
+    // implicit-gradient backward (lfr_backward.hip): everything is set up on the first lfr_batch_backward
+    const lfr::Graph *graph = nullptr;   // for the record -> directed-edge map of batches without edge_ref
+    int64_t n_graph_matches = 0;
+    BwdState *bwd = nullptr;
+    CovState *cov = nullptr;             // per-keypoint covariance (lfr_covariance.hip): set up on the first lfr_batch_covariance
+
+    lfr_batch() { for (auto &e : ev_ring) e = nullptr; }
+    ~lfr_batch() {
+        bwd_free(bwd);
+        cov_free(cov);
+        if (ctx) {
+            (void)hipSetDevice(device);
+            if (n_solves > 0) (void)hipStreamSynchronize(last_stream);      // nothing may still use the slab
+            if (side_stream) (void)hipStreamSynchronize(side_stream);
+            for (auto &w : wg_stream) if (w) (void)hipStreamSynchronize(w);
+            (void)hipStreamSynchronize(ctx->s_main);
+            if (h_positions) ctx->pinned_release(h_positions, h_positions_bytes);
+            if (h_positions_f32) ctx->pinned_release(h_positions_f32, h_positions_f32_bytes);
+            if (d_positions_f32) ctx->dev_release(d_positions_f32, d_positions_f32_bytes);
+        }
+        if (ctx) {                                      // (every stream this batch used has been waited for above: the events are idle)
+            for (auto &e : ev_ring) ctx->event_release(e, true);
+            ctx->event_release(ev_fork, false);
+            ctx->event_release(ev_order, false);
+        } else {
+            for (auto &e : ev_ring) if (e) (void)hipEventDestroy(e);
+        }
+        // slab / ws_slab return to the context's cache in their destructors
+    }
+};
+
+namespace lfr {
+// host mirrors of a device-assembled batch (descriptors, component ids, classes, node ids): 2-6 MB, fetched once
+int ensure_mirrors(lfr_batch *b);
+// writes the packed-class records of a fused batch (lfr_batch_solve does so on a batch's second solve); the caller clears b->fused
+void materialize_records(lfr_batch *b, hipStream_t st);
+}  // namespace lfr

@@ -1,6 +1,7 @@
 // Per-keypoint covariance of the refined positions (lfr_batch_covariance, include/lfr.h).
-// Included at the end of lfr_solve.hip behind lfr_backward_impl.hpp: it reads the batch layout and the packed kernel's pieces that live
-// there (load_packed_edge, PackedRanges, eval_edge) and the backward's assembly and LDL^T, and changes nothing the solve or the backward read.
+// A translation unit of its own: it reads the batch layout (lfr_batch.hpp), the packed kernel's pieces of lfr_device.hpp (load_packed_edge,
+// eval_edge, the DPP / swizzle broadcasts) and the backward's assembly and LDL^T (lfr_hessian_device.hpp), and changes nothing the solve
+// or the backward read.
 //
 // Per solved component C = (J^T J)^-1 at the solve's x, J the loss-corrected Jacobian - the undamped, unscaled matrix of the LM loop:
 //   packed classes (<= 32 rows)   ONE launch in the forward's layout: a wave64 hosts 64/S components, one-wave workgroups, no barriers.
@@ -10,6 +11,23 @@
 //   workgroup classes (33..6144)  one workgroup per component: the backward's owner-computes assembly without rho'' and the second
 //                                 derivatives, its zero-skipping LDL^T, then per node two forward substitutions with unit right-hand
 //                                 sides and C(i,j) = sum_k W(k,i) W(k,j) / d_k, W = L^-1; nodes dealt to waves, fixed summation order.
+
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <memory>
+#include <type_traits>
+#include <cstring>
+#include <vector>
+
+#include "lfr_assemble.hpp"
+#include "lfr_batch.hpp"
+#include "lfr_hessian_device.hpp"
+
+using namespace lfrdev;
+using lfr::KernelArgs;
+using lfr::PackedRanges;
+using lfr::ensure_mirrors;
 
 namespace {
 

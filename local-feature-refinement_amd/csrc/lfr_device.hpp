@@ -882,4 +882,37 @@ __device__ __forceinline__ double group_bcast_k(double v, int k) {
     return swz_bcast_k<and_mask>(v, k);
 }
 
+
+// one record of a packed class: 18 flow values, similarity, src | (dst | kind << 15) << 16.  FUSED: gathered from the graph's
+// match-ordered arrays (9 + 3 loads); otherwise the 80-byte record of the batch (5 loads)
+// (Args: lfr::KernelArgs, lfr_batch.hpp - this header stays free of host types)
+template <bool FUSED, class Args>
+__device__ __forceinline__ void load_packed_edge(const Args &a, const uint32_t rec, float (&fl)[18], float &sm, uint32_t &word) {
+    if constexpr (FUSED) {
+        const uint32_t eid = a.edge_ref[rec], m = eid >> 1;
+        const size_t row = a.f_row ? (size_t)a.f_row[m] : (size_t)m;
+        const uint2 *fp = reinterpret_cast<const uint2 *>(((eid & 1u) ? a.f_disp1 : a.f_disp2) + 18 * row);
+        uint2 q[9];
+#pragma unroll
+        for (int i = 0; i < 9; ++i) q[i] = fp[i];
+        sm = a.f_sim[m];
+        word = a.edge_word[rec];
+#pragma unroll
+        for (int i = 0; i < 9; ++i) { fl[2 * i] = __uint_as_float(q[i].x); fl[2 * i + 1] = __uint_as_float(q[i].y); }
+    } else {
+        const uint4 *rp = reinterpret_cast<const uint4 *>(a.edges + rec);
+        uint4 q[5];
+#pragma unroll
+        for (int i = 0; i < 5; ++i) q[i] = rp[i];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            fl[4 * i] = __uint_as_float(q[i].x); fl[4 * i + 1] = __uint_as_float(q[i].y);
+            fl[4 * i + 2] = __uint_as_float(q[i].z); fl[4 * i + 3] = __uint_as_float(q[i].w);
+        }
+        fl[16] = __uint_as_float(q[4].x); fl[17] = __uint_as_float(q[4].y);
+        sm = __uint_as_float(q[4].z);
+        word = q[4].w;
+    }
+}
+
 }  // namespace lfrdev

@@ -1,8 +1,10 @@
 """Build liblfr_hip.so in-tree with hipcc for gfx950 (cross-compiles without a GPU).
 
 One object per source under csrc/_obj (rebuilt when the source or any header is newer), compiled in
-parallel, then linked: a kernel edit recompiles one file instead of six.
+parallel, then linked: an edit of one source recompiles that file alone, and the forward kernels
+(lfr_solve.hip, the longest compile by far) only when they or a header change.
 """
+import glob
 import os
 import subprocess
 from concurrent.futures import ThreadPoolExecutor
@@ -11,8 +13,8 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(_HERE))
 CSRC = os.path.join(os.path.dirname(_HERE), "csrc")
 OBJ = os.path.join(CSRC, "_obj")
-SOURCES = ["lfr_wire.cpp", "lfr_graph.cpp", "lfr_treeplan.cpp", "lfr_devctx.cpp", "lfr_solve.hip", "lfr_assemble.hip", "lfr_graphstage.hip"]
-HEADERS = ["lfr_backward_impl.hpp", "lfr_covariance_impl.hpp", "lfr_internal.hpp", "lfr_device.hpp", "lfr_assemble.hpp", "lfr_devctx.hpp", "lfr_sort.hpp"]
+SOURCES = ["lfr_wire.cpp", "lfr_graph.cpp", "lfr_treeplan.cpp", "lfr_devctx.cpp", "lfr_solve.hip", "lfr_batch.hip", "lfr_backward.hip",
+           "lfr_covariance.hip", "lfr_assemble.hip", "lfr_graphstage.hip"]
 OUT = os.path.join(_HERE, "liblfr_hip.so")
 
 
@@ -30,8 +32,8 @@ def _flags():
 
 
 def _header_mtime():
-    deps = [os.path.join(CSRC, f) for f in HEADERS] + [os.path.join(ROOT, "include", "lfr.h")]
-    return max(os.path.getmtime(d) for d in deps if os.path.exists(d))
+    deps = glob.glob(os.path.join(CSRC, "*.hpp")) + [os.path.join(ROOT, "include", "lfr.h")]     # every header: none can be forgotten
+    return max(os.path.getmtime(d) for d in deps)
 
 
 def _stale_objects(force):

@@ -1,16 +1,18 @@
 #!/bin/bash
 # ThreadSanitizer over the host code: the parallel whole-input scanner (speculative split, concurrent first-appearance map), the
-# host graph stage and the size cap with its parallel halves.  Builds the three .cpp files with -fsanitize=thread, links them with
+# host graph stage and the size cap with its parallel halves.  Builds the .cpp files of lfr_amd/build.py's SOURCES with -fsanitize=thread, links them with
 # the regular device objects (csrc/_obj) and scripts/probes/host_harness.cpp, and runs the harness on two generated inputs (short
 # tracks with many small cuts; long tracks on few images = one giant component, deep recursion).  Runs here, no GPU.
 set -e
 R=$(cd $(dirname $0)/.. && pwd); C=$R/local-feature-refinement_amd/csrc; O=/tmp/tsan; mkdir -p $O
 H=/opt/rocm/bin/hipcc
-for f in lfr_wire.cpp lfr_graph.cpp lfr_treeplan.cpp lfr_devctx.cpp; do
+SRCS=$(cd $R/local-feature-refinement_amd && python3 -c "from lfr_amd.build import SOURCES; print(' '.join(SOURCES))")      # the one list of sources: lfr_amd/build.py
+HOST=$(for f in $SRCS; do case $f in *.cpp) echo $f;; esac; done)
+for f in $HOST; do
   $H --offload-arch=gfx950 -O1 -g -std=c++17 -fPIC -fsanitize=thread -I $R/include -I $C -c $C/$f -o $O/$f.o
 done
 /opt/rocm/lib/llvm/bin/clang++ -O1 -g -fsanitize=thread -I $R/include -c $R/scripts/probes/host_harness.cpp -o $O/harness.o
-$H --offload-arch=gfx950 -fsanitize=thread $O/harness.o $O/lfr_wire.cpp.o $O/lfr_graph.cpp.o $O/lfr_treeplan.cpp.o $O/lfr_devctx.cpp.o $C/_obj/lfr_solve.hip.o $C/_obj/lfr_assemble.hip.o $C/_obj/lfr_graphstage.hip.o -o $O/harness
+$H --offload-arch=gfx950 -fsanitize=thread $O/harness.o $(for f in $HOST; do echo $O/$f.o; done) $C/_obj/*.hip.o -o $O/harness
 python - <<PY
 import sys
 sys.path.insert(0, "$R/local-feature-refinement_amd")
