@@ -341,13 +341,43 @@ typedef struct lfr_backward_stats {
 int lfr_batch_positions_to_device(lfr_batch *b, double *dst_device, void *hip_stream);
 /* The gradient above.  grad_positions_device: 2 * n_nodes doubles (dL/dx of the whole graph); grad_disp1/2_device: n_matches x 18,
  * grad_sim_device: n_matches, float32 (double with LFR_BACKWARD_F64); whole arrays are overwritten.  Runs on `hip_stream` after the
- * latest solve; asynchronous unless stats != NULL.  LFR_ERR_ARG before the first solve.  The first call sets up its workspace and,
- * for batches whose records do not carry their directed-edge ids, maps records to edges from the graph (which must still be alive). */
+ * latest solve; asynchronous unless stats != NULL.  LFR_ERR_ARG before the first solve, and between an lfr_batch_set_inputs and the
+ * next solve.  The first call sets up its workspace and, for batches whose records do not carry their directed-edge ids, maps records to
+ * edges from the graph (which must still be alive; lfr_batch_set_inputs shares the map). */
 int lfr_batch_backward(lfr_batch *b, const double *grad_positions_device, void *grad_disp1_device, void *grad_disp2_device,
                        void *grad_sim_device, int flags, void *hip_stream, lfr_backward_stats *stats);
 /* Per component (order of lfr_batch_component_info) of the latest backward: 0 differentiated, 1 not usable, 2 indefinite.
  * Waits for that backward.  Returns the count (< 0: error, LFR_ERR_ARG before the first backward). */
 int64_t lfr_batch_backward_status(lfr_batch *b, int32_t *status);
+
+/* ---------------------------------------------------------------------------------------------
+ * New flows and similarities into a live batch: the forward-side counterpart of the backward's contract (a training loop solves the
+ * same scenes thousands of times and only the network's outputs change; the reference re-reads its MatchingFile for every run).
+ *
+ * Contract.  The structure of the batch is held fixed: the kept edges, their kinds (Cauchy / Tukey), local indices, component
+ * descriptors, incidence lists, kernel classes, batch order, hand-out order, tree plans and teams are those of lfr_batch_create.  Only
+ * the 18 flow values and the similarity of every record change; the graph stage is not run again, so similarities that would have
+ * produced other tracks or roots do not.
+ *   - disp1/disp2: n_matches x 18 float32, sim: n_matches float32, DEVICE pointers on the batch's device, in the MATCH layout of the
+ *     graph (exactly the layout lfr_batch_backward writes its gradients in: input order of lfr_graph_from_arrays*, banned pairs removed;
+ *     edge node1->node2 of match m reads disp2[m], node2->node1 reads disp1[m], both read sim[m]);
+ *   - disp1 and disp2: both given or both NULL (= keep the flows); sim NULL = keep the similarities; all three NULL: LFR_ERR_ARG;
+ *   - only this shard's records are written: matches whose edges were dropped or lie outside the shard are not read;
+ *   - stream-ordered and asynchronous: the call waits BY EVENT for the batch's latest solve, backward and covariance, whatever streams
+ *     they ran on, and runs on `hip_stream`.  The inputs are read only by work enqueued in this call: the caller may overwrite or free
+ *     them in stream order afterwards.  No host synchronisation and no allocation, except in the first call of a batch whose records do
+ *     not carry their directed-edge ids: it maps records to edges from the graph (the map lfr_batch_backward makes; whichever of the two
+ *     comes first builds it), and the graph must still be alive then (LFR_ERR_ARG otherwise);
+ *   - the next lfr_batch_solve, on any stream, uses the new values, and so do lfr_batch_backward and lfr_batch_covariance after it.
+ *     BETWEEN this call and the next solve the positions are still those of the earlier solve (downloads, views and
+ *     lfr_batch_positions_to_device keep their meaning), but the records no longer belong to them: lfr_batch_backward and
+ *     lfr_batch_covariance return LFR_ERR_ARG ("inputs changed since the latest solve");
+ *   - undefined values follow the contract at the top of this file: a flow or similarity that is not finite fails its component only;
+ *   - a batch over one rank's connected components (lfr_problem_build_hip_shard with lfr_problem_cc_sharded = 1) numbers its matches
+ *     by itself: LFR_ERR_UNSUPPORTED.  Shards of lfr_batch_create(p, device, rank, world) are served.
+ * Kernel: one launch over all records of the batch, one thread per (record, 16-byte chunk), coalesced 16-byte stores; the
+ * similarity-only form is one 4-byte store per record and the flows-only form never touches the similarity. */
+int lfr_batch_set_inputs(lfr_batch *b, const float *disp1_device, const float *disp2_device, const float *sim_device, void *hip_stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Per-keypoint covariance of the refined positions (the counterpart of ceres::Covariance with apply_loss_function = true; the
@@ -381,8 +411,8 @@ typedef struct lfr_covariance_stats {
 #define LFR_COVARIANCE_F64 1       /* the output is double instead of float32 (the float32 output is the fp64 result rounded once) */
 
 /* cov_device: 3 * n_nodes float32 (double with LFR_COVARIANCE_F64) of the whole graph; the whole array is overwritten.  Runs on
- * `hip_stream` after the latest solve; asynchronous unless stats != NULL.  LFR_ERR_ARG before the first solve.  Changes nothing the
- * solve or the backward read. */
+ * `hip_stream` after the latest solve; asynchronous unless stats != NULL.  LFR_ERR_ARG before the first solve, and between an
+ * lfr_batch_set_inputs and the next solve.  Changes nothing the solve or the backward read. */
 int lfr_batch_covariance(lfr_batch *b, void *cov_device, int flags, void *hip_stream, lfr_covariance_stats *stats);
 /* Per component (order of lfr_batch_component_info) of the latest covariance: 0 computed, 1 not usable, 2 singular.  Waits for that
  * call.  Returns the count (< 0: error, LFR_ERR_ARG before the first lfr_batch_covariance). */

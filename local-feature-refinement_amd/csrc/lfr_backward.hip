@@ -127,11 +127,6 @@ __global__ void k_bwd_sim(int64_t n_matches, const double *dir, void *out, int f
     if (f64) static_cast<double *>(out)[m] = g; else static_cast<float *>(out)[m] = (float)g;
 }
 
-__global__ void k_bwd_words(uint32_t n, const EdgeRec *edges, uint32_t *words) {
-    const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
-    if (p < n) words[p] = (uint32_t)edges[p].src | ((uint32_t)edges[p].dst_kind << 16);
-}
-
 size_t bwd_lds_bytes(int rows, bool lds_matrix) {
     return (lds_matrix ? bwd_tri(rows, 0) * 8 : 0) + (size_t)rows * (8 + 8 + 4 + 1) + 16;
 }
@@ -140,7 +135,6 @@ size_t bwd_lds_bytes(int rows, bool lds_matrix) {
 
 struct BwdState {
     lfr::DevArena slab;
-    uint32_t *d_eid = nullptr;                 // nullptr: the batch's edge_ref
     double *d_gsim = nullptr, *d_hws = nullptr;
     uint64_t *d_hws_off = nullptr;
     int32_t *d_status = nullptr;
@@ -159,49 +153,16 @@ void bwd_free(BwdState *s) {
     delete s;
 }
 
-namespace {
+hipEvent_t bwd_last_event(const BwdState *s) { return s && s->n_calls ? s->ev1 : nullptr; }
 
-// record -> directed edge of the graph for batches without edge_ref: the records of a component come in the reference's residual-block
-// order (solve.cc:98-102: by source node, a node's out-edges in insertion order = ascending directed-edge id) or, in the packed
-// classes, in edge-id order - either way the records of one source node ascend in edge id - and a kept edge is kept for its two end
-// points' labels alone, so the k-th record from s to t is the k-th out-edge of s that ends at t.
-int bwd_edge_map(lfr_batch *b, std::vector<uint32_t> &eid) {
-    const lfr::Graph *g = b->graph;
-    const size_t ne = (size_t)b->n_edges;
-    std::vector<uint32_t> words(ne);
-    hipStream_t st = b->ctx->s_main;
-    if (b->n_solves > 0) HIP_TRY(hipStreamWaitEvent(st, b->ev[1], 0));
-    if (ne) {
-        uint32_t *d_words = static_cast<uint32_t *>(b->bwd->slab.take(4 * ne));
-        if (!d_words) { lfr::set_error("backward slab exhausted"); return LFR_ERR_NOMEM; }
-        hipLaunchKernelGGL(k_bwd_words, dim3((unsigned)((ne + 255) / 256)), dim3(256), 0, st, (uint32_t)ne, b->d_edges, d_words);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(words.data(), d_words, 4 * ne, hipMemcpyDeviceToHost, st));
-        HIP_TRY(lfr::stream_wait(st));
-    }
-    std::vector<int64_t> out_off, out_eid;
-    lfr::build_out_csr(*g, out_off, out_eid);
-    std::vector<int64_t> cursor(out_off.begin(), out_off.end() - 1);
-    eid.assign(ne, 0);
-    auto dst_of = [&](int64_t e) -> uint32_t { return (e & 1) ? g->m_node1[e >> 1] : g->m_node2[e >> 1]; };
-    for (const CompDesc &dsc : b->descs) {
-        for (uint32_t p = dsc.edge_off; p < dsc.edge_off + dsc.n_edges; ++p) {
-            const uint32_t sl = words[p] & 0xffffu, tl = (words[p] >> 16) & 0x7fffu;
-            const uint32_t s = b->node_ids[dsc.node_off + sl], t = b->node_ids[dsc.node_off + tl];
-            int64_t &c = cursor[s];
-            while (c < out_off[s + 1] && dst_of(out_eid[c]) != t) ++c;
-            if (c >= out_off[s + 1]) { lfr::set_error("backward: record %u has no edge in the graph", p); return LFR_ERR_ARG; }
-            eid[p] = (uint32_t)out_eid[c++];
-        }
-    }
-    return LFR_OK;
-}
+namespace {
 
 int bwd_setup(lfr_batch *b) {
     int rc = ensure_mirrors(b);
     if (rc != LFR_OK) return rc;
     std::unique_ptr<BwdState> s(new BwdState());
-    const size_t nd = std::max<size_t>(b->descs.size(), 1), ne = std::max<int64_t>(b->n_edges, 1);
+    if ((rc = lfr::ensure_edge_map(b)) != LFR_OK) return rc;     // (records -> edges of the graph: the batch's own, shared with lfr_batch_set_inputs)
+    const size_t nd = std::max<size_t>(b->descs.size(), 1);
     const size_t M = (size_t)std::max<int64_t>(b->n_graph_matches, 1);
     std::vector<uint64_t> off(nd, 0);
     uint64_t hws = 0;
@@ -213,8 +174,7 @@ int bwd_setup(lfr_batch *b) {
             off[i] = hws; hws += bwd_tri(rows, 0);
         }
     }
-    const bool map_on_host = b->d_edge_ref == nullptr;
-    const size_t bytes = (map_on_host ? 8 * ne : 0) + 16 * M + 8 * hws + 8 * nd + 4 * nd + 64 + ((size_t)1 << 16);
+    const size_t bytes = 16 * M + 8 * hws + 8 * nd + 4 * nd + 64 + ((size_t)1 << 16);
     if (!s->slab.init(b->ctx, bytes)) return LFR_ERR_NOMEM;
     s->d_gsim = s->slab.take_n<double>(2 * M);
     s->d_hws = s->slab.take_n<double>(std::max<uint64_t>(hws, 1));
@@ -226,14 +186,6 @@ int bwd_setup(lfr_batch *b) {
     hipStream_t st = b->ctx->s_main;
     HIP_TRY(hipMemcpyAsync(s->d_hws_off, off.data(), 8 * nd, hipMemcpyHostToDevice, st));
     b->bwd = s.release();
-    if (map_on_host) {
-        std::vector<uint32_t> eid;
-        if (!b->graph) { lfr::set_error("backward: the batch has no graph"); return LFR_ERR_ARG; }
-        if ((rc = bwd_edge_map(b, eid)) != LFR_OK) { bwd_free(b->bwd); b->bwd = nullptr; return rc; }
-        b->bwd->d_eid = b->bwd->slab.take_n<uint32_t>(ne);
-        if (!b->bwd->d_eid) { bwd_free(b->bwd); b->bwd = nullptr; lfr::set_error("backward slab exhausted"); return LFR_ERR_NOMEM; }
-        if (!eid.empty()) HIP_TRY(hipMemcpyAsync(b->bwd->d_eid, eid.data(), 4 * eid.size(), hipMemcpyHostToDevice, st));
-    }
     HIP_TRY(lfr::stream_wait(st));
     HIP_TRY(hipFuncSetAttribute((const void *)backward_kernel<kBwdThreads, true>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                 (int)bwd_lds_bytes(lfr::kBlockMaxRows, true)));
@@ -261,6 +213,7 @@ int lfr_batch_backward(lfr_batch *b, const double *grad_positions_device, void *
         lfr::set_error("bad argument"); return LFR_ERR_ARG;
     }
     if (b->n_solves == 0) { lfr::set_error("lfr_batch_backward: the batch has not been solved"); return LFR_ERR_ARG; }
+    if (b->inputs_epoch != b->solved_epoch) { lfr::set_error("lfr_batch_backward: inputs changed since the latest solve"); return LFR_ERR_ARG; }
     HIP_TRY(hipSetDevice(b->device));
     if (!b->bwd) { const int rc = bwd_setup(b); if (rc != LFR_OK) return rc; }
     BwdState &s = *b->bwd;
@@ -279,7 +232,7 @@ int lfr_batch_backward(lfr_batch *b, const double *grad_positions_device, void *
     BwdArgs a;
     a.descs = b->d_descs; a.edges = b->d_edges; a.node_ids = b->d_node_ids; a.node_inc = b->d_node_inc; a.in_idx = b->d_in_idx;
     a.positions = b->d_positions; a.infos = b->d_infos; a.grad_pos = grad_positions_device;
-    a.eid = s.d_eid ? s.d_eid : b->d_edge_ref;
+    a.eid = lfr::edge_map(b);
     a.hws = s.d_hws; a.hws_off = s.d_hws_off; a.g_disp1 = grad_disp1_device; a.g_disp2 = grad_disp2_device; a.g_sim_dir = s.d_gsim;
     a.status = s.d_status; a.counters = s.d_counters; a.tukey_variant = b->tukey_variant; a.f64 = f64;
     a.n_matches = (uint32_t)M;

@@ -1,7 +1,7 @@
 // The batch behind the C ABI (include/lfr.h): creation (device- or host-assembled), the workspace of the workgroup classes, the launch
 // plan of lfr_batch_solve, timing, downloads, warm-up / reserve and the multi-GPU entry points.  The forward kernels live in
 // lfr_solve.hip and are reached through the launch functions of lfr_batch.hpp; this file holds only the small utility kernels of the
-// host code (k_materialize_records, k_wg_order_keys, k_place_plans, k_positions_to_f32, k_occupy).
+// host code (k_materialize_records, k_wg_order_keys, k_place_plans, k_positions_to_f32, k_occupy).  lfr_batch_set_inputs: lfr_inputs.hip.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -615,7 +615,8 @@ int lfr_batch_create(const lfr_problem *ph, int device, int shard_rank, int shar
     b->device = device; b->ctx = ctx; b->tukey_variant = tukey_variant; b->shard_world = shard_world;
     { const char *e = getenv("LFR_SERIAL_CLASSES"); b->serial = e && e[0] == '1'; }
     b->n_graph_nodes = p.g->n_nodes();
-    b->graph = p.g; b->n_graph_matches = p.g->n_matches();
+    b->graph = p.g; b->graph_serial = p.g->serial; b->n_graph_matches = p.g->n_matches();
+    b->cc_sharded = p.cc_sharded;
     int rc = p.host_batch ? create_from_host(b.get(), p, shard_rank, shard_world) : create_on_device(b.get(), p, shard_rank, shard_world);
     if (rc != LFR_OK) return rc;
     if ((rc = finish_workspace(b.get(), p)) != LFR_OK) return rc;
@@ -697,6 +698,11 @@ int lfr_batch_solve(lfr_batch *b, void *hip_stream, lfr_solve_stats *stats) {
             materialised = true;
         }
     }
+    if (b->inputs_pending) {             // records rewritten by lfr_batch_set_inputs, possibly on another stream
+        if (b->inputs_stream != st) HIP_TRY(hipStreamWaitEvent(st, b->ev_inputs, 0));
+        b->inputs_pending = false;
+    }
+    b->solved_epoch = b->inputs_epoch;
     b->ev = b->ev_ring + (b->n_solves % lfr_batch::kSlots) * lfr_batch::kEvPerSlot;
     uint32_t &recorded = b->ev_recorded[b->n_solves % lfr_batch::kSlots];
     recorded = 0;

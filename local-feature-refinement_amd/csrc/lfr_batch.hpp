@@ -4,6 +4,7 @@
 //   lfr_batch.hip        batch creation, the launch plan of lfr_batch_solve, timing, downloads, warm-up, multi-GPU entry points
 //   lfr_backward.hip     implicit-gradient backward pass (lfr_batch_backward)
 //   lfr_covariance.hip   per-keypoint covariance (lfr_batch_covariance)
+//   lfr_inputs.hip       new flows / similarities into a live batch (lfr_batch_set_inputs) and the record -> directed-edge map
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -98,8 +99,10 @@ constexpr size_t kProfWords = 8 * lfr::KC_COUNT + 8 + 64;  // phase counters of 
 constexpr uint32_t kPackedEventsAliased = 1u << 31;     // ev_recorded: the packed launch is timed by the solve's own pair of events
 struct BwdState;                                        // lfr_backward.hip
 void bwd_free(BwdState *s);
+hipEvent_t bwd_last_event(const BwdState *s);           // end of the latest backward (nullptr: none has run)
 struct CovState;                                        // lfr_covariance.hip
 void cov_free(CovState *s);
+hipEvent_t cov_last_event(const CovState *s);           // end of the latest covariance (nullptr: none has run)
 struct lfr_batch {
     int device = 0;
     lfr::DevCtx *ctx = nullptr;
@@ -175,7 +178,19 @@ struct lfr_batch {
     bool infos_valid = false;
     // implicit-gradient backward (lfr_backward.hip): everything is set up on the first lfr_batch_backward
     const lfr::Graph *graph = nullptr;   // for the record -> directed-edge map of batches without edge_ref
+    uint64_t graph_serial = 0;           // (lfr::graph_alive: the map is made on first use, the graph may be gone by then)
     int64_t n_graph_matches = 0;
+    // record -> directed edge of the graph for batches without edge_ref (lfr::ensure_edge_map): the backward scatters through it,
+    // lfr_batch_set_inputs gathers through it; whichever comes first builds it
+    lfr::DevArena map_slab;
+    uint32_t *d_eid = nullptr;
+    // new inputs into the live batch (lfr_inputs.hip): inputs_epoch counts lfr_batch_set_inputs calls, solved_epoch is its value at
+    // the latest solve - backward and covariance combine positions with records and refuse to run while the two differ
+    bool cc_sharded = false;             // the problem covers one rank's connected components: its match numbering is not the graph's
+    uint64_t inputs_epoch = 0, solved_epoch = 0;
+    hipEvent_t ev_inputs = nullptr;      // end of the latest lfr_batch_set_inputs
+    hipStream_t inputs_stream = nullptr;
+    bool inputs_pending = false;         // no solve has been issued since: the next one waits for ev_inputs
     BwdState *bwd = nullptr;
     CovState *cov = nullptr;             // per-keypoint covariance (lfr_covariance.hip): set up on the first lfr_batch_covariance
 
@@ -186,6 +201,7 @@ struct lfr_batch {
         if (ctx) {
             (void)hipSetDevice(device);
             if (n_solves > 0) (void)hipStreamSynchronize(last_stream);      // nothing may still use the slab
+            if (inputs_epoch > 0) (void)hipStreamSynchronize(inputs_stream);
             if (side_stream) (void)hipStreamSynchronize(side_stream);
             for (auto &w : wg_stream) if (w) (void)hipStreamSynchronize(w);
             (void)hipStreamSynchronize(ctx->s_main);
@@ -197,6 +213,7 @@ struct lfr_batch {
             for (auto &e : ev_ring) ctx->event_release(e, true);
             ctx->event_release(ev_fork, false);
             ctx->event_release(ev_order, false);
+            ctx->event_release(ev_inputs, false);
         } else {
             for (auto &e : ev_ring) if (e) (void)hipEventDestroy(e);
         }
@@ -209,4 +226,8 @@ namespace lfr {
 int ensure_mirrors(lfr_batch *b);
 // writes the packed-class records of a fused batch (lfr_batch_solve does so on a batch's second solve); the caller clears b->fused
 void materialize_records(lfr_batch *b, hipStream_t st);
+// the batch's record -> directed-edge map (lfr_inputs.hip): nothing to do for a batch with edge_ref; otherwise built once from the graph
+// (LFR_ERR_ARG when that has been freed) - a synchronising call the first time, free afterwards
+int ensure_edge_map(lfr_batch *b);
+inline const uint32_t *edge_map(const lfr_batch *b) { return b->d_edge_ref ? b->d_edge_ref : b->d_eid; }
 }  // namespace lfr

@@ -366,6 +366,8 @@ void cov_free(CovState *s) {
     delete s;
 }
 
+hipEvent_t cov_last_event(const CovState *s) { return s && s->n_calls ? s->ev1 : nullptr; }
+
 namespace {
 
 int cov_setup(lfr_batch *b) {
@@ -408,6 +410,7 @@ extern "C" {
 int lfr_batch_covariance(lfr_batch *b, void *cov_device, int flags, void *hip_stream, lfr_covariance_stats *stats) {
     if (!b || !cov_device || (flags & ~LFR_COVARIANCE_F64)) { lfr::set_error("bad argument"); return LFR_ERR_ARG; }
     if (b->n_solves == 0) { lfr::set_error("lfr_batch_covariance: the batch has not been solved"); return LFR_ERR_ARG; }
+    if (b->inputs_epoch != b->solved_epoch) { lfr::set_error("lfr_batch_covariance: inputs changed since the latest solve"); return LFR_ERR_ARG; }
     HIP_TRY(hipSetDevice(b->device));
     if (!b->cov) { const int rc = cov_setup(b); if (rc != LFR_OK) return rc; }
     CovState &s = *b->cov;

@@ -417,6 +417,27 @@ std::unordered_map<int, int> recursive_cut(const std::vector<std::pair<int, int>
 }
 
 
+// live graphs by address and serial number (lfr_internal.hpp: graph_alive)
+namespace {
+std::mutex g_live_mu;
+std::unordered_map<const Graph *, uint64_t> &live_graphs() { static std::unordered_map<const Graph *, uint64_t> m; return m; }
+}  // namespace
+
+uint64_t graph_register(const Graph *g) {
+    static uint64_t next = 0;
+    std::lock_guard<std::mutex> lk(g_live_mu);
+    return live_graphs()[g] = ++next;
+}
+void graph_unregister(const Graph *g) {
+    std::lock_guard<std::mutex> lk(g_live_mu);
+    live_graphs().erase(g);
+}
+bool graph_alive(const Graph *g, uint64_t serial) {
+    std::lock_guard<std::mutex> lk(g_live_mu);
+    const auto it = live_graphs().find(g);
+    return it != live_graphs().end() && it->second == serial;
+}
+
 // out-edge CSR of the match graph: out_eid[out_off[n] .. out_off[n+1]) = directed edge ids of node n, ascending =
 // the reference's insertion order (graph.cc:17-23)
 void build_out_csr(const Graph &g, std::vector<int64_t> &out_off, std::vector<int64_t> &out_eid) {

@@ -24,7 +24,19 @@ struct DevProblem;
 // (solve.cc:477-478).  A node's out-edges in the reference's insertion order are exactly its
 // directed edges in ascending id.
 // ------------------------------------------------------------------------------------------
+// live graphs by address and serial number (lfr_graph.cpp): a batch keeps a plain pointer to its graph and needs it once more, late,
+// for its record -> edge map; graph_alive tells whether that pointer still means the graph the batch was made from
+struct Graph;
+uint64_t graph_register(const Graph *g);
+void graph_unregister(const Graph *g);
+bool graph_alive(const Graph *g, uint64_t serial);
+
 struct Graph {
+    const uint64_t serial = graph_register(this);
+    Graph() = default;
+    Graph(const Graph &) = delete;
+    Graph &operator=(const Graph &) = delete;
+    ~Graph() { graph_unregister(this); }
     std::vector<std::string> image_names;      // seen (non-banned) images, order of first appearance
     std::vector<float> image_fact;             // first-wins (solve.cc:449,451)
     std::unordered_map<std::string, int32_t> image_index;

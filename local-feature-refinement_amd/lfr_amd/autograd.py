@@ -5,6 +5,14 @@ the implicit-function-theorem gradient back (lfr_batch_backward, include/lfr.h; 
                                            feat1=..., feat2=...)
     loss(pos).backward()        # fills disp1.grad, disp2.grad, sim.grad
 
+A training loop solves the same scenes again and again and only the network's outputs change: `Refiner` runs the graph stage and the
+assembly ONCE and gives every later forward new flows (and similarities) into the live batch (lfr_batch_set_inputs):
+
+    r = Refiner(disp1, disp2, sim, image_names=..., pair_img1=..., pair_img2=..., pair_off=..., feat1=..., feat2=...)
+    for step in ...:
+        pos = r(disp1, disp2)           # set_inputs + solve + positions on torch's current stream, no host synchronisation
+        loss(pos).backward()
+
 One device, first-order only (the backward is not itself differentiable).  The graph stage (tracks, roots, components, the cut) is
 discrete and the box's active set piecewise constant: the gradient holds them fixed.
 """
@@ -101,3 +109,114 @@ def refine(disp1, disp2, sim, *, image_names, pair_img1, pair_img2, pair_off, fe
     if return_covariance:
         return pos, node_image, node_feature, meta.pop("covariance").detach()
     return pos, node_image, node_feature
+
+
+class _RefinerStep(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, disp1, disp2, sim, refiner):
+        ctx.refiner = refiner
+        ctx.epoch = refiner._forward(disp1, disp2, sim)
+        ctx.n_in = (disp1.shape, disp2.shape, None if sim is None else sim.shape, disp1.dtype, disp2.dtype,
+                    None if sim is None else (sim.dtype, sim.device))
+        pos = torch.empty((refiner.n_nodes, 2), dtype=torch.float64, device=refiner.device)
+        refiner._batch.positions_to(pos)
+        return pos
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_pos):
+        r = ctx.refiner
+        if r._batch is None:
+            raise RuntimeError("Refiner: backward after close()")
+        if ctx.epoch != r._epoch:
+            raise RuntimeError("Refiner: this forward (step %d) is stale - the shared batch holds only its latest solve (step %d); "
+                               "run backward before the next forward" % (ctx.epoch, r._epoch))
+        s1, s2, ss, t1, t2, ts = ctx.n_in
+        g1, g2, gs = r._batch.backward(grad_pos, f64=False)
+        if r._idx is not None:      # back to the caller's rows (matches of banned pairs get 0)
+            f1 = torch.zeros((r.n_rows, 18), dtype=g1.dtype, device=g1.device)
+            f2 = torch.zeros_like(f1)
+            fs = torch.zeros((r.n_rows,), dtype=gs.dtype, device=gs.device)
+            f1[r._idx], f2[r._idx], fs[r._idx] = g1, g2, gs
+            g1, g2, gs = f1, f2, fs
+        return (g1.reshape(s1).to(t1) if ctx.needs_input_grad[0] else None,
+                g2.reshape(s2).to(t2) if ctx.needs_input_grad[1] else None,
+                gs.reshape(ss).to(device=ts[1], dtype=ts[0]) if ss is not None and ctx.needs_input_grad[2] else None, None)
+
+
+class Refiner:
+    """refine() for a loop over the same scenes: the graph stage (tracks, roots, components) and the batch assembly run once, in the
+    constructor, from the values given there; every call gives the live batch new flows - and similarities, if passed - and solves
+    it again.  The structure stays that of the constructor's values: similarities that would have produced other tracks or roots do
+    not (the gradient holds the structure fixed anyway).
+
+    r(disp1, disp2, sim=None) -> [n_nodes, 2] float64 device positions, differentiable with respect to what was passed (sim=None:
+    the similarities stay, no gradient).  Tensors as for refine(), in the caller's rows (banned pairs included).  The forward issues
+    set_inputs, solve and the positions' copy on torch's current stream and does not synchronise the host.  The batch is shared and
+    holds only its latest solve: backward() of an older forward raises RuntimeError; several backwards of the latest one are fine.
+    node_image, node_feature, n_nodes: as refine() returns them.  covariance(f64=True): lfr_batch_covariance of the latest solve."""
+
+    def __init__(self, disp1, disp2, sim, *, image_names, pair_img1, pair_img2, pair_off, feat1, feat2, image_facts=None, banned=(),
+                 tukey_variant="ceres1"):
+        pair_img1 = np.ascontiguousarray(pair_img1, np.int32)
+        pair_img2 = np.ascontiguousarray(pair_img2, np.int32)
+        pair_off = np.ascontiguousarray(pair_off, np.int64)
+        facts = np.ones(len(image_names), np.float32) if image_facts is None else np.ascontiguousarray(image_facts, np.float32)
+        if not disp1.is_cuda or disp2.device != disp1.device:
+            raise ValueError("Refiner: disp1 and disp2 must be on the same HIP device")
+        device = disp1.device
+        dev = device.index if device.index is not None else torch.cuda.current_device()
+        self.device = torch.device("cuda", dev)
+        d1 = disp1.detach().to(torch.float32).reshape(-1, 18).contiguous()
+        d2 = disp2.detach().to(torch.float32).reshape(-1, 18).contiguous()
+        self.n_rows = int(d1.shape[0])
+        ma = MatchArrays(image_names=list(image_names), facts=facts, pair_img1=pair_img1, pair_img2=pair_img2, pair_off=pair_off,
+                         feat1=np.ascontiguousarray(feat1, np.uint32), feat2=np.ascontiguousarray(feat2, np.uint32),
+                         sim=sim.detach().to(torch.float32).cpu().numpy(), disp1=None, disp2=None)
+        rows = _kept_rows(pair_img1, pair_img2, pair_off, list(image_names), tuple(banned))
+        self._idx = None if rows is None else torch.as_tensor(rows, device=self.device)
+        with torch.cuda.device(dev):
+            # the library reads the flows on its own streams: they must be complete before the graph takes them (once, here)
+            torch.cuda.current_stream(self.device).synchronize()
+            self._graph = capi.Graph.from_device_flows(ma, d1.data_ptr(), d2.data_ptr(), device=dev, banned=tuple(banned))
+            self._problem = capi.Problem(self._graph, device_graph_stage=dev)
+            self._batch = capi.Batch(self._problem, dev, tukey_variant=tukey_variant)     # (gathers its records: d1 / d2 may go after this)
+        self.n_nodes = self._graph.n_nodes
+        self.node_image, self.node_feature = self._graph.nodes()
+        self._epoch = 0
+
+    def _forward(self, disp1, disp2, sim):
+        if self._batch is None:
+            raise RuntimeError("Refiner: called after close()")
+        if disp1.device != self.device or disp2.device != self.device:
+            raise ValueError("Refiner: disp1 and disp2 must be on %s" % self.device)
+        with torch.cuda.device(self.device):
+            def rows(t, shape):
+                t = t.detach().to(device=self.device, dtype=torch.float32).reshape(shape)
+                if t.shape[0] != self.n_rows:
+                    raise ValueError("Refiner: %d rows, the constructor saw %d" % (t.shape[0], self.n_rows))
+                return (t if self._idx is None else t.index_select(0, self._idx)).contiguous()
+            d1, d2 = rows(disp1, (-1, 18)), rows(disp2, (-1, 18))
+            s = None if sim is None else rows(sim, (-1,))
+            # (d1, d2, s may be temporaries: they are read by work enqueued here, and torch reuses their memory in stream order)
+            self._batch.set_inputs(d1, d2, s)
+            self._batch.solve(stream=torch.cuda.current_stream(self.device).cuda_stream, want_stats=False)
+        self._epoch += 1
+        return self._epoch
+
+    def __call__(self, disp1, disp2, sim=None):
+        return _RefinerStep.apply(disp1, disp2, sim, self)
+
+    def covariance(self, f64=True):
+        """[n_nodes, 3] device tensor of lfr_batch_covariance for the latest forward (detached: the covariance is not differentiated)."""
+        if self._epoch == 0:
+            raise RuntimeError("Refiner: covariance before the first forward")
+        with torch.cuda.device(self.device):
+            return self._batch.covariance(f64=f64)
+
+    def close(self):
+        for name in ("_batch", "_problem", "_graph"):
+            h = getattr(self, name, None)
+            if h is not None:
+                h.close()
+            setattr(self, name, None)

@@ -130,6 +130,7 @@ def lib():
         "lfr_batch_positions_to_device": (C.c_int, [vp, vp, vp]),
         "lfr_batch_backward": (C.c_int, [vp, vp, vp, vp, vp, C.c_int, vp, C.POINTER(BackwardStats)]),
         "lfr_batch_backward_status": (i64, [vp, vp]),
+        "lfr_batch_set_inputs": (C.c_int, [vp, vp, vp, vp, vp]),
         "lfr_batch_covariance": (C.c_int, [vp, vp, C.c_int, vp, C.POINTER(CovarianceStats)]),
         "lfr_batch_covariance_status": (i64, [vp, vp]),
         "lfr_keypoint_covariances": (C.c_int, [vp, vp, C.c_char_p, vp, i64]),
@@ -167,7 +168,7 @@ EXPORTS = ["lfr_version", "lfr_last_error", "lfr_graph_from_files", "lfr_graph_f
            "lfr_graph_num_images", "lfr_graph_get_nodes", "lfr_graph_image_name", "lfr_graph_image_fact",
            "lfr_write_matching_file", "lfr_problem_build", "lfr_problem_build_labels", "lfr_problem_build_hip", "lfr_problem_free", "lfr_problem_get_stats",
            "lfr_problem_get_labels", "lfr_problem_shard_components", "lfr_hip_warmup", "lfr_batch_create", "lfr_batch_free", "lfr_batch_solve",
-           "lfr_batch_download", "lfr_batch_timing", "lfr_batch_spin_timeouts", "lfr_batch_team_runs", "lfr_batch_team_fallbacks", "lfr_debug_occupy", "lfr_batch_tree_stats", "lfr_batch_component_info", "lfr_batch_positions_to_device", "lfr_batch_backward", "lfr_batch_backward_status", "lfr_batch_covariance", "lfr_batch_covariance_status", "lfr_keypoint_covariances", "lfr_debug_invert_spd", "lfr_solve_hip", "lfr_solve_hip_multi", "lfr_solve_graph_hip_multi", "lfr_write_solution", "lfr_apply_displacements"]
+           "lfr_batch_download", "lfr_batch_timing", "lfr_batch_spin_timeouts", "lfr_batch_team_runs", "lfr_batch_team_fallbacks", "lfr_debug_occupy", "lfr_batch_tree_stats", "lfr_batch_component_info", "lfr_batch_positions_to_device", "lfr_batch_backward", "lfr_batch_backward_status", "lfr_batch_set_inputs", "lfr_batch_covariance", "lfr_batch_covariance_status", "lfr_keypoint_covariances", "lfr_debug_invert_spd", "lfr_solve_hip", "lfr_solve_hip_multi", "lfr_solve_graph_hip_multi", "lfr_write_solution", "lfr_apply_displacements"]
 
 
 def _check(rc):
@@ -645,6 +646,35 @@ class Batch:
         if n:
             _check(lib().lfr_batch_positions_to_device(self._h, C.c_void_p(tensor.data_ptr()), C.c_void_p(stream) if stream else None))
         return tensor
+
+    def set_inputs(self, disp1=None, disp2=None, sim=None, stream=None):
+        """New flows and / or similarities into the live batch (lfr_batch_set_inputs, include/lfr.h): contiguous float32 tensors on
+        the batch's device in the graph's match layout - disp1, disp2: [n_matches, 18] or [n_matches, 9, 2], given together or not
+        at all (None = keep); sim: [n_matches] (None = keep).  The structure of the batch stays that of its creation.  Stream-ordered
+        on `stream` (a hipStream_t as int, None = torch's current stream) without a host synchronisation: the tensors may be
+        overwritten or freed in stream order afterwards.  The next solve() uses the new values."""
+        import torch
+        m = self.problem.graph.n_edges // 2
+        dev = torch.device("cuda", self.device)
+
+        def ptr(t, name, shapes):
+            if t is None:
+                return None
+            if not isinstance(t, torch.Tensor):
+                raise ValueError("set_inputs: %s must be a torch tensor" % name)
+            if not t.is_cuda or t.device != dev:
+                raise ValueError("set_inputs: %s is on %s, the batch on %s" % (name, t.device, dev))
+            if t.dtype != torch.float32:
+                raise ValueError("set_inputs: %s is %s, need float32" % (name, t.dtype))
+            if tuple(t.shape) not in shapes or not t.is_contiguous():
+                raise ValueError("set_inputs: %s has shape %s, need a contiguous %s" % (name, tuple(t.shape), " or ".join(map(str, shapes))))
+            return C.c_void_p(t.data_ptr() or 1)          # (no matches: an empty tensor has no address, and nothing is read)
+
+        flow_shapes = ((m, 18), (m, 9, 2))
+        p1, p2, ps = ptr(disp1, "disp1", flow_shapes), ptr(disp2, "disp2", flow_shapes), ptr(sim, "sim", ((m,),))
+        if stream is None:
+            stream = torch.cuda.current_stream(dev).cuda_stream
+        _check(lib().lfr_batch_set_inputs(self._h, p1, p2, ps, C.c_void_p(stream) if stream else None))
 
     def backward(self, grad_positions, f64=False, stream=None, want_stats=False):
         """Implicit gradient of the latest solve (lfr_batch_backward, include/lfr.h): grad_positions = dL/dx, [n_nodes, 2] float64 on
