@@ -14,15 +14,12 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <memory>
 #include <cstring>
-#include <vector>
 
 #include "lfr_batch.hpp"
 #include "lfr_hessian_device.hpp"
 
 using namespace lfrdev;
-using lfr::ensure_mirrors;
 
 namespace {
 
@@ -131,68 +128,27 @@ size_t bwd_lds_bytes(int rows, bool lds_matrix) {
     return (lds_matrix ? bwd_tri(rows, 0) * 8 : 0) + (size_t)rows * (8 + 8 + 4 + 1) + 16;
 }
 
-}  // namespace
-
-struct BwdState {
-    lfr::DevArena slab;
-    double *d_gsim = nullptr, *d_hws = nullptr;
-    uint64_t *d_hws_off = nullptr;
-    int32_t *d_status = nullptr;
+// the shared state of a pass behind a solve (lfr_batch.hpp) + the backward's own: dL/dsim per directed edge, {bound coordinates, ...}
+struct BwdState : lfr::PassState {
+    double *d_gsim = nullptr;
     unsigned long long *d_counters = nullptr;
-    int rows_max[lfr::KC_COUNT] = {0};
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    hipStream_t last_stream = nullptr;
-    int64_t n_calls = 0;
 };
 
-void bwd_free(BwdState *s) {
-    if (!s) return;
-    if (s->last_stream || s->n_calls) (void)hipStreamSynchronize(s->last_stream);
-    if (s->ev0) (void)hipEventDestroy(s->ev0);
-    if (s->ev1) (void)hipEventDestroy(s->ev1);
-    delete s;
-}
-
-hipEvent_t bwd_last_event(const BwdState *s) { return s && s->n_calls ? s->ev1 : nullptr; }
-
-namespace {
-
-int bwd_setup(lfr_batch *b) {
-    int rc = ensure_mirrors(b);
+int bwd_setup_extra(lfr_batch *b, lfr::PassState *ps) {
+    BwdState *s = static_cast<BwdState *>(ps);
+    const int rc = lfr::ensure_edge_map(b);     // (records -> edges of the graph: the batch's own, shared with lfr_batch_set_inputs)
     if (rc != LFR_OK) return rc;
-    std::unique_ptr<BwdState> s(new BwdState());
-    if ((rc = lfr::ensure_edge_map(b)) != LFR_OK) return rc;     // (records -> edges of the graph: the batch's own, shared with lfr_batch_set_inputs)
-    const size_t nd = std::max<size_t>(b->descs.size(), 1);
-    const size_t M = (size_t)std::max<int64_t>(b->n_graph_matches, 1);
-    std::vector<uint64_t> off(nd, 0);
-    uint64_t hws = 0;
-    for (size_t i = 0; i < b->descs.size(); ++i) {
-        const int cls = b->desc_class[i], rows = 2 * b->descs[i].n_var;
-        s->rows_max[cls] = std::max(s->rows_max[cls], rows);
-        if (cls == lfr::KC_GLOBAL) {
-            if (rows > kBwdMaxRows) { lfr::set_error("backward: a component of %d rows exceeds the dense backward's %d", rows, kBwdMaxRows); return LFR_ERR_UNSUPPORTED; }
-            off[i] = hws; hws += bwd_tri(rows, 0);
-        }
-    }
-    const size_t bytes = 16 * M + 8 * hws + 8 * nd + 4 * nd + 64 + ((size_t)1 << 16);
-    if (!s->slab.init(b->ctx, bytes)) return LFR_ERR_NOMEM;
-    s->d_gsim = s->slab.take_n<double>(2 * M);
-    s->d_hws = s->slab.take_n<double>(std::max<uint64_t>(hws, 1));
-    s->d_hws_off = s->slab.take_n<uint64_t>(nd);
-    s->d_status = s->slab.take_n<int32_t>(nd);
+    s->d_gsim = s->slab.take_n<double>(2 * (size_t)std::max<int64_t>(b->n_graph_matches, 1));
     s->d_counters = s->slab.take_n<unsigned long long>(8);
-    if (!s->d_gsim || !s->d_hws || !s->d_hws_off || !s->d_status || !s->d_counters) { lfr::set_error("backward slab exhausted"); return LFR_ERR_NOMEM; }
-    HIP_TRY(hipEventCreate(&s->ev0)); HIP_TRY(hipEventCreate(&s->ev1));
-    hipStream_t st = b->ctx->s_main;
-    HIP_TRY(hipMemcpyAsync(s->d_hws_off, off.data(), 8 * nd, hipMemcpyHostToDevice, st));
-    b->bwd = s.release();
-    HIP_TRY(lfr::stream_wait(st));
+    if (!s->d_gsim || !s->d_counters) { lfr::set_error("backward slab exhausted"); return LFR_ERR_NOMEM; }
     HIP_TRY(hipFuncSetAttribute((const void *)backward_kernel<kBwdThreads, true>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                 (int)bwd_lds_bytes(lfr::kBlockMaxRows, true)));
     HIP_TRY(hipFuncSetAttribute((const void *)backward_kernel<kBwdThreads, false>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                 (int)bwd_lds_bytes(kBwdMaxRows, false)));
     return LFR_OK;
 }
+
+const lfr::PassKind kBackward = {"backward", [] { return static_cast<lfr::PassState *>(new BwdState()); }, bwd_setup_extra};
 
 }  // namespace
 
@@ -212,16 +168,11 @@ int lfr_batch_backward(lfr_batch *b, const double *grad_positions_device, void *
     if (!b || !grad_positions_device || !grad_disp1_device || !grad_disp2_device || !grad_sim_device || (flags & ~LFR_BACKWARD_F64)) {
         lfr::set_error("bad argument"); return LFR_ERR_ARG;
     }
-    if (b->n_solves == 0) { lfr::set_error("lfr_batch_backward: the batch has not been solved"); return LFR_ERR_ARG; }
-    if (b->inputs_epoch != b->solved_epoch) { lfr::set_error("lfr_batch_backward: inputs changed since the latest solve"); return LFR_ERR_ARG; }
-    HIP_TRY(hipSetDevice(b->device));
-    if (!b->bwd) { const int rc = bwd_setup(b); if (rc != LFR_OK) return rc; }
-    BwdState &s = *b->bwd;
     hipStream_t st = (hipStream_t)hip_stream;
     const int f64 = (flags & LFR_BACKWARD_F64) ? 1 : 0;
     const size_t M = (size_t)b->n_graph_matches, elt = f64 ? 8 : 4;
-    HIP_TRY(hipStreamWaitEvent(st, b->ev[1], 0));                               // the latest solve's positions and termination codes
-    HIP_TRY(hipEventRecord(s.ev0, st));
+    { const int rc = lfr::pass_begin(b, &b->bwd, kBackward, 16 * std::max<size_t>(M, 1) + 64, st); if (rc != LFR_OK) return rc; }
+    BwdState &s = *static_cast<BwdState *>(b->bwd);
     if (b->fused) lfr::materialize_records(b, st);     // the packed records have not been written yet: write them (the next solve would write the same bytes)
     if (M) {
         HIP_TRY(hipMemsetAsync(grad_disp1_device, 0, 18 * M * elt, st));
@@ -256,40 +207,19 @@ int lfr_batch_backward(lfr_batch *b, const double *grad_positions_device, void *
     }
     if (M) hipLaunchKernelGGL(k_bwd_sim, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, st, (int64_t)M, s.d_gsim, grad_sim_device, f64);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(s.ev1, st));
-    s.last_stream = st;
-    ++s.n_calls;
+    { const int rc = lfr::pass_end(&s, st); if (rc != LFR_OK) return rc; }
     if (stats) {
-        HIP_TRY(hipEventSynchronize(s.ev1));
-        std::vector<int32_t> status(b->descs.size());
         unsigned long long cnt[8];
-        if (!status.empty()) HIP_TRY(hipMemcpyAsync(status.data(), s.d_status, 4 * status.size(), hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipMemcpyAsync(cnt, s.d_counters, sizeof(cnt), hipMemcpyDeviceToHost, st));
-        HIP_TRY(lfr::stream_wait(st));
+        int64_t count[3];
         memset(stats, 0, sizeof(*stats));
-        for (int32_t v : status) {
-            if (v == 0) ++stats->n_differentiated;
-            else if (v == 1) ++stats->n_not_usable;
-            else ++stats->n_indefinite;
-        }
+        HIP_TRY(hipMemcpyAsync(cnt, s.d_counters, sizeof(cnt), hipMemcpyDeviceToHost, st));       // (pass_histogram waits for st)
+        { const int rc = lfr::pass_histogram(b, &s, st, count, &stats->kernel_ms); if (rc != LFR_OK) return rc; }
+        stats->n_differentiated = count[0]; stats->n_not_usable = count[1]; stats->n_indefinite = count[2];
         stats->n_bound_coordinates = (int64_t)cnt[0];
-        float ms = 0.f;
-        HIP_TRY(hipEventElapsedTime(&ms, s.ev0, s.ev1));
-        stats->kernel_ms = ms;
     }
     return LFR_OK;
 }
 
-int64_t lfr_batch_backward_status(lfr_batch *b, int32_t *status) {
-    if (!b || !b->bwd || !b->bwd->n_calls) { lfr::set_error("lfr_batch_backward_status: no backward has run on this batch"); return LFR_ERR_ARG; }
-    HIP_TRY(hipSetDevice(b->device));
-    HIP_TRY(hipEventSynchronize(b->bwd->ev1));
-    const size_t n = b->descs.size();
-    if (status && n) {
-        HIP_TRY(hipMemcpyAsync(status, b->bwd->d_status, 4 * n, hipMemcpyDeviceToHost, b->bwd->last_stream));
-        HIP_TRY(lfr::stream_wait(b->bwd->last_stream));
-    }
-    return (int64_t)n;
-}
+int64_t lfr_batch_backward_status(lfr_batch *b, int32_t *status) { return lfr::pass_status(b, b ? b->bwd : nullptr, "backward", status); }
 
 }  // extern "C"

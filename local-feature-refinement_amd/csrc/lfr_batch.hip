@@ -1,5 +1,6 @@
 // The batch behind the C ABI (include/lfr.h): creation (device- or host-assembled), the workspace of the workgroup classes, the launch
-// plan of lfr_batch_solve, timing, downloads, warm-up / reserve and the multi-GPU entry points.  The forward kernels live in
+// plan of lfr_batch_solve with its diagnostic read-backs and statistics, the state that the passes behind a solve share (PassState),
+// timing, downloads, warm-up / reserve and the multi-GPU entry points.  The forward kernels live in
 // lfr_solve.hip and are reached through the launch functions of lfr_batch.hpp; this file holds only the small utility kernels of the
 // host code (k_materialize_records, k_wg_order_keys, k_place_plans, k_positions_to_f32, k_occupy).  lfr_batch_set_inputs: lfr_inputs.hip.
 #include <hip/hip_runtime.h>
@@ -18,6 +19,7 @@
 
 #include "lfr_assemble.hpp"
 #include "lfr_batch.hpp"
+#include "lfr_hessian_device.hpp"
 #include "lfr_internal.hpp"
 
 using lfr::CompDesc;
@@ -109,6 +111,107 @@ void lfr::materialize_records(lfr_batch *b, hipStream_t st) {
     const lfr::DevGraph &dgr = *b->dev_hold->graph;
     hipLaunchKernelGGL(k_materialize_records, dim3((unsigned)(((uint64_t)5 * b->packed_edges + 255) / 256)), dim3(256), 0, st, b->packed_edges,
                        b->d_edge_ref, b->d_edge_word, dgr.flow_row, dgr.disp1, dgr.disp2, dgr.sim, reinterpret_cast<uint4 *>(b->d_edges));
+}
+
+// =============================================================================================
+// the packed launch's blocks; the state of a pass that runs after a solve (lfr_batch.hpp)
+// =============================================================================================
+void lfr::packed_ranges(const lfr_batch *b, int waves_per_block, PackedRanges *r, int *n_blocks) {
+    static const int kPackedOrder[5] = {lfr::KC_G64_4, lfr::KC_G64_2, lfr::KC_G32, lfr::KC_G16, lfr::KC_G8};     // dispatch order: PackedRanges is indexed by it
+    const lfr::SolveGeometry &geo = lfr::solve_geometry();
+    int nb = 0;
+    for (int i = 0; i < 5; ++i) {
+        const int cls = kPackedOrder[i], per_block = geo.comps_per_block[cls] / geo.packed_waves * waves_per_block;
+        r->blk_begin[i] = nb;
+        r->desc_begin[i] = b->class_begin[cls]; r->desc_end[i] = b->class_begin[cls + 1];
+        nb += (r->desc_end[i] - r->desc_begin[i] + per_block - 1) / per_block;
+    }
+    r->blk_begin[5] = nb;
+    *n_blocks = nb;
+}
+
+void lfr::pass_free(PassState *s) {
+    if (!s) return;
+    if (s->last_stream || s->n_calls) (void)hipStreamSynchronize(s->last_stream);
+    if (s->ev0) (void)hipEventDestroy(s->ev0);
+    if (s->ev1) (void)hipEventDestroy(s->ev1);
+    delete s;
+}
+
+hipEvent_t lfr::pass_last_event(const PassState *s) { return s && s->n_calls ? s->ev1 : nullptr; }
+
+namespace {
+// first call of a pass on this batch: the dense triangles of the components above the LDS classes live in HBM, one status per descriptor
+int pass_setup(lfr_batch *b, lfr::PassState **slot, const lfr::PassKind &kind, size_t extra_bytes) {
+    int rc = ensure_mirrors(b);
+    if (rc != LFR_OK) return rc;
+    std::unique_ptr<lfr::PassState, void (*)(lfr::PassState *)> s(kind.make(), lfr::pass_free);      // every error path releases slab and events
+    const size_t nd = std::max<size_t>(b->descs.size(), 1);
+    std::vector<uint64_t> off(nd, 0);
+    uint64_t hws = 0;
+    for (size_t i = 0; i < b->descs.size(); ++i) {
+        const int cls = b->desc_class[i], rows = 2 * b->descs[i].n_var;
+        s->rows_max[cls] = std::max(s->rows_max[cls], rows);
+        if (cls == lfr::KC_GLOBAL) {
+            if (rows > lfrdev::kBwdMaxRows) { lfr::set_error("%s: a component of %d rows exceeds the dense factorization's %d", kind.name, rows, lfrdev::kBwdMaxRows); return LFR_ERR_UNSUPPORTED; }
+            off[i] = hws; hws += lfrdev::bwd_tri(rows, 0);
+        }
+    }
+    if (!s->slab.init(b->ctx, extra_bytes + 8 * hws + 8 * nd + 4 * nd + ((size_t)1 << 16))) return LFR_ERR_NOMEM;
+    s->d_hws = s->slab.take_n<double>(std::max<uint64_t>(hws, 1));
+    s->d_hws_off = s->slab.take_n<uint64_t>(nd);
+    s->d_status = s->slab.take_n<int32_t>(nd);
+    if (!s->d_hws || !s->d_hws_off || !s->d_status) { lfr::set_error("%s slab exhausted", kind.name); return LFR_ERR_NOMEM; }
+    HIP_TRY(hipEventCreate(&s->ev0)); HIP_TRY(hipEventCreate(&s->ev1));
+    hipStream_t st = b->ctx->s_main;
+    HIP_TRY(hipMemcpyAsync(s->d_hws_off, off.data(), 8 * nd, hipMemcpyHostToDevice, st));
+    HIP_TRY(lfr::stream_wait(st));
+    if ((rc = kind.extra(b, s.get())) != LFR_OK) return rc;
+    *slot = s.release();
+    return LFR_OK;
+}
+}  // namespace
+
+int lfr::pass_begin(lfr_batch *b, PassState **slot, const PassKind &kind, size_t extra_bytes, hipStream_t st) {
+    if (b->n_solves == 0) { lfr::set_error("lfr_batch_%s: the batch has not been solved", kind.name); return LFR_ERR_ARG; }
+    if (b->inputs_epoch != b->solved_epoch) { lfr::set_error("lfr_batch_%s: inputs changed since the latest solve", kind.name); return LFR_ERR_ARG; }
+    HIP_TRY(hipSetDevice(b->device));
+    if (!*slot) { const int rc = pass_setup(b, slot, kind, extra_bytes); if (rc != LFR_OK) return rc; }
+    HIP_TRY(hipStreamWaitEvent(st, b->ev[1], 0));                               // the latest solve's positions and termination codes
+    HIP_TRY(hipEventRecord((*slot)->ev0, st));
+    return LFR_OK;
+}
+
+int lfr::pass_end(PassState *s, hipStream_t st) {
+    HIP_TRY(hipEventRecord(s->ev1, st));
+    s->last_stream = st;
+    ++s->n_calls;
+    return LFR_OK;
+}
+
+int64_t lfr::pass_status(lfr_batch *b, PassState *s, const char *name, int32_t *status) {
+    if (!b || !s || !s->n_calls) { lfr::set_error("lfr_batch_%s_status: no %s has run on this batch", name, name); return LFR_ERR_ARG; }
+    HIP_TRY(hipSetDevice(b->device));
+    HIP_TRY(hipEventSynchronize(s->ev1));
+    const size_t n = b->descs.size();
+    if (status && n) {
+        HIP_TRY(hipMemcpyAsync(status, s->d_status, 4 * n, hipMemcpyDeviceToHost, s->last_stream));
+        HIP_TRY(lfr::stream_wait(s->last_stream));
+    }
+    return (int64_t)n;
+}
+
+int lfr::pass_histogram(lfr_batch *b, PassState *s, hipStream_t st, int64_t count[3], double *kernel_ms) {
+    HIP_TRY(hipEventSynchronize(s->ev1));
+    std::vector<int32_t> status(b->descs.size());
+    if (!status.empty()) HIP_TRY(hipMemcpyAsync(status.data(), s->d_status, 4 * status.size(), hipMemcpyDeviceToHost, st));
+    HIP_TRY(lfr::stream_wait(st));
+    count[0] = count[1] = count[2] = 0;
+    for (int32_t v : status) ++count[v == 0 ? 0 : v == 1 ? 1 : 2];
+    float ms = 0.f;
+    HIP_TRY(hipEventElapsedTime(&ms, s->ev0, s->ev1));
+    *kernel_ms = ms;
+    return LFR_OK;
 }
 
 namespace {
@@ -660,198 +763,166 @@ int lfr_batch_create(const lfr_problem *ph, int device, int shard_rank, int shar
     return LFR_OK;
 }
 
-int lfr_batch_solve(lfr_batch *b, void *hip_stream, lfr_solve_stats *stats) {
-    if (!b) { lfr::set_error("bad argument"); return LFR_ERR_ARG; }
-    host_trace("lfr_batch_solve enters");
-    HIP_TRY(hipSetDevice(b->device));
-    hipStream_t st = (hipStream_t)hip_stream;
-    const lfr::SolveGeometry &geo = lfr::solve_geometry();
-    const int kThreadsS = geo.threads_s, kThreadsM = geo.threads_m, kThreadsL = geo.threads_l, kTeamMax = geo.team_max, kTeamCtlWords = geo.team_ctl_words;
+}  // extern "C"
+
+namespace {
+
+KernelArgs make_kernel_args(const lfr_batch *b) {
     KernelArgs a;
     a.descs = b->d_descs; a.edges = b->d_edges; a.node_ids = b->d_node_ids; a.positions = b->d_positions;
     a.infos = b->d_infos; a.workspace = b->d_workspace; a.ws_off = b->d_ws_off; a.es_off = b->d_es_off;
     a.node_inc = b->d_node_inc; a.in_idx = b->d_in_idx; a.tukey_variant = b->tukey_variant; a.prof = b->d_prof;
     { const char *e = getenv("LFR_SCRATCH_SWEEP"); a.scratch_sweep = (e && e[0] == '1') ? 1 : 0; }
-    a.queue = reinterpret_cast<unsigned int *>(b->d_prof + 8 * lfr::KC_COUNT);
+    a.queue = lfr::queue_block(b->d_prof);
     a.wg_order = b->d_wg_order; a.wg_begin = b->class_begin[lfr::KC_BLOCK];
     a.edge_ref = b->d_edge_ref; a.edge_word = b->d_edge_word;
     a.f_row = nullptr; a.f_disp1 = a.f_disp2 = a.f_sim = nullptr;
-    a.team_ctl = b->d_team_ctl; a.team_red = b->d_team_red;
-    a.trace = nullptr;
-#ifdef LFR_TRACE_TREE
-    static unsigned long long *d_trace = nullptr;
-    if (!d_trace) { HIP_TRY(hipMalloc(&d_trace, ((size_t)1 << 20) * 8 + 64)); }
-    HIP_TRY(hipMemsetAsync(d_trace, 0, 64, st));
-    a.trace = d_trace;
-#endif
-    for (int k = 0; k < 3; ++k) a.team_work[k] = b->team_work[k];
-    a.team_epoch = (uint32_t)(b->n_solves + 1);
-    a.team_patience_us = b->team_patience_us;
-    bool materialised = false;
     if (b->fused) {
         const lfr::DevGraph &dgr = *b->dev_hold->graph;
         a.f_row = dgr.flow_row; a.f_disp1 = dgr.disp1; a.f_disp2 = dgr.disp2; a.f_sim = dgr.sim;
-        if (b->n_solves > 0) {           // solved before: this batch is being re-used - write the records once, read them from now on
-            lfr::materialize_records(b, st);
-            HIP_TRY(hipGetLastError());
-            b->fused = false;
-            materialised = true;
-        }
     }
-    if (b->inputs_pending) {             // records rewritten by lfr_batch_set_inputs, possibly on another stream
-        if (b->inputs_stream != st) HIP_TRY(hipStreamWaitEvent(st, b->ev_inputs, 0));
-        b->inputs_pending = false;
-    }
-    b->solved_epoch = b->inputs_epoch;
-    b->ev = b->ev_ring + (b->n_solves % lfr_batch::kSlots) * lfr_batch::kEvPerSlot;
-    uint32_t &recorded = b->ev_recorded[b->n_solves % lfr_batch::kSlots];
-    recorded = 0;
-    ++b->n_solves;
-    b->last_stream = st;
-    if (!b->ev[0]) for (int i = 0; i < lfr_batch::kEvPerSlot; ++i) if (!(b->ev[i] = b->ctx->event_acquire(true))) return LFR_ERR_HIP;
-    HIP_TRY(hipEventRecord(b->ev[0], st));
-    if (b->class_begin[lfr::KC_COUNT] > b->class_begin[lfr::KC_BLOCK]) {
-        HIP_TRY(hipStreamWaitEvent(st, b->ev_order, 0));
-        HIP_TRY(hipMemsetAsync(a.queue, 0, 64, st));                       // the classes' component queues
-        if (b->d_team_ctl) HIP_TRY(hipMemsetAsync(b->d_team_ctl, 0, kTeamCtlWords * sizeof(unsigned int), st));   // registrations, mailboxes, barrier counters of the teams
-    }
+    a.team_ctl = b->d_team_ctl; a.team_red = b->d_team_red;
+    a.trace = nullptr;
+    for (int k = 0; k < 3; ++k) a.team_work[k] = b->team_work[k];
+    a.team_epoch = (uint32_t)(b->n_solves + 1);
+    a.team_patience_us = b->team_patience_us;
+    return a;
+}
 
-    // The packed classes go out as ONE launch on the caller's stream (solve_packed_kernel); the few
-    // workgroup-per-component problems run beside it on a side stream.  LFR_SERIAL_CLASSES=1
-    // launches every class separately on the caller's stream (per-class timings for diagnostics).
-    static const int kPackedOrder[5] = {lfr::KC_G64_4, lfr::KC_G64_2, lfr::KC_G32, lfr::KC_G16, lfr::KC_G8};
-    const int *const kCompsPerBlock = geo.comps_per_block;
-    auto launch_block = [&](int cls, hipStream_t cs) -> int {
+// one workgroup class (persistent workgroups that take their components from the class's queue) on stream cs
+int launch_wg_class(lfr_batch *b, KernelArgs &a, int cls, hipStream_t cs) {
+    const lfr::SolveGeometry &geo = lfr::solve_geometry();
+    a.desc_begin = b->class_begin[cls]; a.desc_end = b->class_begin[cls + 1]; a.cls = cls;
+    const int n = a.desc_end - a.desc_begin;
+    if (n <= 0) return LFR_OK;
+    if (cls == lfr::KC_GLOBAL) {
+        if (const char *e = getenv("LFR_DEBUG_TREE_FIRST")) a.desc_end = std::min(a.desc_end, a.desc_begin + std::max(1, atoi(e)));   // (experiments: only the first k of the hand-out order)
+        // elimination-tree kernel: one 512-thread workgroup per CU (two waves per SIMD), static LDS only
+        // (at least 8 kTeamMax workgroups: whatever the placement, one of the eight XCDs then holds a complete unit)
+        if (b->d_team_ctl) lfr::launch_tree(a, true, std::max(lfr::kTeamXccs * geo.team_max, std::min(b->team_wgs, b->ctx->n_cu / 32 * 32)), cs);
+        else lfr::launch_tree(a, false, std::min(n, b->ctx->n_cu), cs);
+    } else {
+        const int rows = b->class_max_rows[cls];
+        const size_t lds = block_lds_bytes(rows);
+        // persistent workgroups: what the chip keeps resident for the class (by LDS, and 8 waves of 256 registers per CU)
+        const int threads = cls == lfr::KC_BLOCK ? geo.threads_s : cls == lfr::KC_BLOCK_M ? geo.threads_m : geo.threads_l;
+        const int by_waves = std::max(1, 512 / threads), by_lds = std::max(1, (int)((size_t)160 * 1024 / (lds + 256)));
+        const int wgs = std::min(n, b->ctx->n_cu * std::min(by_waves, by_lds));
+        lfr::launch_block_class(cls, a, rows, wgs, cs);
+    }
+    HIP_TRY(hipGetLastError());
+    return LFR_OK;
+}
+
+// LFR_SERIAL_CLASSES=1: every class separately on the caller's stream (per-class timings for diagnostics)
+int launch_serial(lfr_batch *b, KernelArgs &a, uint32_t &recorded, hipStream_t st) {
+    const int *const comps_per_block = lfr::solve_geometry().comps_per_block;
+    for (int cls = 0; cls < lfr::KC_COUNT; ++cls) {
         a.desc_begin = b->class_begin[cls]; a.desc_end = b->class_begin[cls + 1]; a.cls = cls;
         const int n = a.desc_end - a.desc_begin;
-        if (n <= 0) return LFR_OK;
-        if (cls == lfr::KC_GLOBAL) {
-            if (const char *e = getenv("LFR_DEBUG_TREE_FIRST")) a.desc_end = std::min(a.desc_end, a.desc_begin + std::max(1, atoi(e)));   // (experiments: only the first k of the hand-out order)
-            // elimination-tree kernel: one 512-thread workgroup per CU (two waves per SIMD), static LDS only
-            // (at least 8 kTeamMax workgroups: whatever the placement, one of the eight XCDs then holds a complete unit)
-            if (b->d_team_ctl) lfr::launch_tree(a, true, std::max(8 * kTeamMax, std::min(b->team_wgs, b->ctx->n_cu / 32 * 32)), cs);
-            else lfr::launch_tree(a, false, std::min(n, b->ctx->n_cu), cs);
-        } else {
-            const int rows = b->class_max_rows[cls];
-            const size_t lds = block_lds_bytes(rows);
-            // persistent workgroups: what the chip keeps resident for the class (by LDS, and 8 waves of 256 registers per CU)
-            const int threads = cls == lfr::KC_BLOCK ? kThreadsS : cls == lfr::KC_BLOCK_M ? kThreadsM : kThreadsL;
-            const int by_waves = std::max(1, 512 / threads), by_lds = std::max(1, (int)((size_t)160 * 1024 / (lds + 256)));
-            const int wgs = std::min(n, b->ctx->n_cu * std::min(by_waves, by_lds));
-            lfr::launch_block_class(cls, a, rows, wgs, cs);
+        if (n <= 0) continue;
+        recorded |= 1u << cls;
+        HIP_TRY(hipEventRecord(b->ev[2 + 2 * cls], st));
+        {
+            const int grid = (n + comps_per_block[cls] - 1) / comps_per_block[cls];
+            if (cls < lfr::KC_BLOCK) lfr::launch_group_class(cls, a, b->fused, grid, st);       // (KC_G32: retired class, never assigned)
+            else { const int rc = launch_wg_class(b, a, cls, st); if (rc != LFR_OK) return rc; }
+            HIP_TRY(hipGetLastError());
         }
+        HIP_TRY(hipEventRecord(b->ev[3 + 2 * cls], st));
+    }
+    return LFR_OK;
+}
+
+// The packed classes go out as ONE launch on the caller's stream (solve_packed_kernel); the few
+// workgroup-per-component problems run beside it on a side stream.
+// materialised: this solve wrote the packed records in front of its launches.
+int launch_plan(lfr_batch *b, KernelArgs &a, bool materialised, uint32_t &recorded, hipStream_t st) {
+    // Launch plan.  A workgroup-per-component kernel needs a (nearly) empty CU for each of its
+    // 512-thread workgroups; once the packed launch has flooded the chip such a workgroup only gets a
+    // CU at the packed launch's tail, i.e. the two kernels would run back to back.  So when big-workgroup
+    // classes exist THEY go first, on the caller's stream, and the packed launch follows from a side
+    // stream (its cross-queue wait makes it the later dispatch) and fills the remaining CUs.
+    // Events are barrier packets on their stream: only the launches that exist are bracketed.
+    const bool have_side = b->class_begin[lfr::KC_COUNT] > b->class_begin[lfr::KC_BLOCK];
+    PackedRanges r;
+    int nb = 0;
+    lfr::packed_ranges(b, lfr::solve_geometry().packed_waves, &r, &nb);
+    // the packed launch is timed as one unit: its events sit in the slot of the largest class
+    // (the only launch of the solve - no workgroup class, no records to materialise in front: the solve's own pair of events brackets
+    // exactly this kernel, a second pair would be two more barrier packets per solve for the same two time stamps)
+    const bool alias = !have_side && !materialised;
+    auto launch_packed = [&](hipStream_t cs) -> int {
+        if (!alias) HIP_TRY(hipEventRecord(b->ev[2 + 2 * b->packed_slot], cs));
+        lfr::launch_packed(a, r, b->fused, nb, cs);
         HIP_TRY(hipGetLastError());
+        if (!alias) HIP_TRY(hipEventRecord(b->ev[3 + 2 * b->packed_slot], cs));
+        recorded |= 1u << b->packed_slot;
+        if (alias) recorded |= kPackedEventsAliased;
         return LFR_OK;
     };
-    const bool have_side = b->class_begin[lfr::KC_COUNT] > b->class_begin[lfr::KC_BLOCK];
-    if (b->serial) {
-        for (int cls = 0; cls < lfr::KC_COUNT; ++cls) {
-            a.desc_begin = b->class_begin[cls]; a.desc_end = b->class_begin[cls + 1]; a.cls = cls;
-            const int n = a.desc_end - a.desc_begin;
-            if (n <= 0) continue;
-            recorded |= 1u << cls;
-            HIP_TRY(hipEventRecord(b->ev[2 + 2 * cls], st));
-            {
-                const int grid = (n + kCompsPerBlock[cls] - 1) / kCompsPerBlock[cls];
-                if (cls < lfr::KC_BLOCK) lfr::launch_group_class(cls, a, b->fused, grid, st);       // (KC_G32: retired class, never assigned)
-                else { const int rc = launch_block(cls, st); if (rc != LFR_OK) return rc; }
-                HIP_TRY(hipGetLastError());
-            }
-            HIP_TRY(hipEventRecord(b->ev[3 + 2 * cls], st));
-        }
-    } else {
-        // Launch plan.  A workgroup-per-component kernel needs a (nearly) empty CU for each of its
-        // 512-thread workgroups; once the packed launch has flooded the chip such a workgroup only gets a
-        // CU at the packed launch's tail, i.e. the two kernels would run back to back.  So when big-workgroup
-        // classes exist THEY go first, on the caller's stream, and the packed launch follows from a side
-        // stream (its cross-queue wait makes it the later dispatch) and fills the remaining CUs.
-        // Events are barrier packets on their stream: only the launches that exist are bracketed.
-        PackedRanges r;
-        int nb = 0;
-        for (int i = 0; i < 5; ++i) {
-            const int cls = kPackedOrder[i];
-            r.blk_begin[i] = nb;
-            r.desc_begin[i] = b->class_begin[cls]; r.desc_end[i] = b->class_begin[cls + 1];
-            const int n = r.desc_end[i] - r.desc_begin[i];
-            nb += (n + kCompsPerBlock[cls] - 1) / kCompsPerBlock[cls];
-        }
-        r.blk_begin[5] = nb;
-        // the packed launch is timed as one unit: its events sit in the slot of the largest class
-        // (the only launch of the solve - no workgroup class, no records to materialise in front: the solve's own pair of events brackets
-        // exactly this kernel, a second pair would be two more barrier packets per solve for the same two time stamps)
-        const bool alias = !have_side && !materialised;
-        auto launch_packed = [&](hipStream_t cs) -> int {
-            if (!alias) HIP_TRY(hipEventRecord(b->ev[2 + 2 * b->packed_slot], cs));
-            lfr::launch_packed(a, r, b->fused, nb, cs);
-            HIP_TRY(hipGetLastError());
-            if (!alias) HIP_TRY(hipEventRecord(b->ev[3 + 2 * b->packed_slot], cs));
-            recorded |= 1u << b->packed_slot;
-            if (alias) recorded |= kPackedEventsAliased;
-            return LFR_OK;
-        };
-        auto launch_big = [&](int cls, hipStream_t cs) -> int {
-            HIP_TRY(hipEventRecord(b->ev[2 + 2 * cls], cs));
-            const int rc = launch_block(cls, cs);
-            if (rc != LFR_OK) return rc;
-            HIP_TRY(hipEventRecord(b->ev[3 + 2 * cls], cs));
-            recorded |= 1u << cls;
-            return LFR_OK;
-        };
-        if (!have_side) {
-            if (nb > 0) { const int rc = launch_packed(st); if (rc != LFR_OK) return rc; }
-        } else {
-            // Every workgroup class on its own stream (the first on the caller's).  Dispatch order = issue order: the HBM-matrix
-            // class first (its components run longest), then the 130-row class, the 192-row class, the 88-row class.  A 160 KB
-            // workgroup only starts on an empty CU: issued first, the largest class kept the others out until its queue drained,
-            // and the one slow component among THEM (iteration counts vary 8x) then ended the solve alone (config 5: 17.0 ms
-            // against 13.8 at the time).  With persistent workgroups the middle class takes the whole chip for its 1.5 ms, the
-            // large class follows, and the small class fills the CUs the large one's tail leaves (measured 9.15 ms against
-            // 9.4-9.5 smallest-first and 12.4 largest-first); LFR_WG_ORDER overrides for experiments.  Round 3, with the fused sweep
-            // (5.1 ms): largest-first 7.9 ms; largest-first with only its share of the CUs (by rows x threads x components) and full
-            // grids behind it 5.8-7.2 ms - the pending workgroups of the later launches do not take the CUs the first one frees, and
-            // the packed launch starves; the order stays.
-            static const std::array<int, 4> kBigOrder = [] {
-                std::array<int, 4> o = {lfr::KC_GLOBAL, lfr::KC_BLOCK_M, lfr::KC_BLOCK_L, lfr::KC_BLOCK};
-                if (const char *e = getenv("LFR_WG_ORDER")) {
-                    int v[4];
-                    if (sscanf(e, "%d,%d,%d,%d", &v[0], &v[1], &v[2], &v[3]) == 4) {
-                        unsigned seen = 0;
-                        for (int i = 0; i < 4; ++i) if (v[i] >= lfr::KC_BLOCK && v[i] < lfr::KC_COUNT) seen |= 1u << v[i];
-                        if (seen == (0xfu << lfr::KC_BLOCK)) for (int i = 0; i < 4; ++i) o[i] = v[i];
-                    }
-                }
-                return o;
-            }();
-            int first = -1, n_big = 0;
-            for (int i = 0; i < 4; ++i) if (b->class_begin[kBigOrder[i] + 1] > b->class_begin[kBigOrder[i]]) { if (first < 0) first = kBigOrder[i]; ++n_big; }
-            if (n_big > 1 || nb > 0) HIP_TRY(hipEventRecord(b->ev_fork, st));
-            { const int rc = launch_big(first, st); if (rc != LFR_OK) return rc; }
-            for (int i = 0; i < 4; ++i) {
-                const int cls = kBigOrder[i];
-                if (cls == first || b->class_begin[cls + 1] <= b->class_begin[cls]) continue;
-                HIP_TRY(hipStreamWaitEvent(b->wg_stream[cls], b->ev_fork, 0));
-                const int rc = launch_big(cls, b->wg_stream[cls]);
-                if (rc != LFR_OK) return rc;
-            }
-            if (nb > 0) {
-                HIP_TRY(hipStreamWaitEvent(b->side_stream, b->ev_fork, 0));
-                const int rc = launch_packed(b->side_stream);
-                if (rc != LFR_OK) return rc;
-                HIP_TRY(hipStreamWaitEvent(st, b->ev[3 + 2 * b->packed_slot], 0));
-            }
-            for (int i = 0; i < 4; ++i) {
-                const int cls = kBigOrder[i];
-                if (cls == first || b->class_begin[cls + 1] <= b->class_begin[cls]) continue;
-                HIP_TRY(hipStreamWaitEvent(st, b->ev[3 + 2 * cls], 0));
-            }
-        }
+    auto launch_big = [&](int cls, hipStream_t cs) -> int {
+        HIP_TRY(hipEventRecord(b->ev[2 + 2 * cls], cs));
+        const int rc = launch_wg_class(b, a, cls, cs);
+        if (rc != LFR_OK) return rc;
+        HIP_TRY(hipEventRecord(b->ev[3 + 2 * cls], cs));
+        recorded |= 1u << cls;
+        return LFR_OK;
+    };
+    if (!have_side) {
+        if (nb > 0) { const int rc = launch_packed(st); if (rc != LFR_OK) return rc; }
+        return LFR_OK;
     }
-    HIP_TRY(hipEventRecord(b->ev[1], st));
-    b->infos_valid = false;
-    host_trace("lfr_batch_solve: launched");
-    if (!stats) return LFR_OK;
+    // Every workgroup class on its own stream (the first on the caller's).  Dispatch order = issue order: the HBM-matrix
+    // class first (its components run longest), then the 130-row class, the 192-row class, the 88-row class.  A 160 KB
+    // workgroup only starts on an empty CU: issued first, the largest class kept the others out until its queue drained,
+    // and the one slow component among THEM (iteration counts vary 8x) then ended the solve alone (config 5: 17.0 ms
+    // against 13.8 at the time).  With persistent workgroups the middle class takes the whole chip for its 1.5 ms, the
+    // large class follows, and the small class fills the CUs the large one's tail leaves (measured 9.15 ms against
+    // 9.4-9.5 smallest-first and 12.4 largest-first); LFR_WG_ORDER overrides for experiments.  Round 3, with the fused sweep
+    // (5.1 ms): largest-first 7.9 ms; largest-first with only its share of the CUs (by rows x threads x components) and full
+    // grids behind it 5.8-7.2 ms - the pending workgroups of the later launches do not take the CUs the first one frees, and
+    // the packed launch starves; the order stays.
+    static const std::array<int, 4> kBigOrder = [] {
+        std::array<int, 4> o = {lfr::KC_GLOBAL, lfr::KC_BLOCK_M, lfr::KC_BLOCK_L, lfr::KC_BLOCK};
+        if (const char *e = getenv("LFR_WG_ORDER")) {
+            int v[4];
+            if (sscanf(e, "%d,%d,%d,%d", &v[0], &v[1], &v[2], &v[3]) == 4) {
+                unsigned seen = 0;
+                for (int i = 0; i < 4; ++i) if (v[i] >= lfr::KC_BLOCK && v[i] < lfr::KC_COUNT) seen |= 1u << v[i];
+                if (seen == (0xfu << lfr::KC_BLOCK)) for (int i = 0; i < 4; ++i) o[i] = v[i];
+            }
+        }
+        return o;
+    }();
+    int first = -1, n_big = 0;
+    for (int i = 0; i < 4; ++i) if (b->class_begin[kBigOrder[i] + 1] > b->class_begin[kBigOrder[i]]) { if (first < 0) first = kBigOrder[i]; ++n_big; }
+    if (n_big > 1 || nb > 0) HIP_TRY(hipEventRecord(b->ev_fork, st));
+    { const int rc = launch_big(first, st); if (rc != LFR_OK) return rc; }
+    for (int i = 0; i < 4; ++i) {
+        const int cls = kBigOrder[i];
+        if (cls == first || b->class_begin[cls + 1] <= b->class_begin[cls]) continue;
+        HIP_TRY(hipStreamWaitEvent(b->wg_stream[cls], b->ev_fork, 0));
+        const int rc = launch_big(cls, b->wg_stream[cls]);
+        if (rc != LFR_OK) return rc;
+    }
+    if (nb > 0) {
+        HIP_TRY(hipStreamWaitEvent(b->side_stream, b->ev_fork, 0));
+        const int rc = launch_packed(b->side_stream);
+        if (rc != LFR_OK) return rc;
+        HIP_TRY(hipStreamWaitEvent(st, b->ev[3 + 2 * b->packed_slot], 0));
+    }
+    for (int i = 0; i < 4; ++i) {
+        const int cls = kBigOrder[i];
+        if (cls == first || b->class_begin[cls + 1] <= b->class_begin[cls]) continue;
+        HIP_TRY(hipStreamWaitEvent(st, b->ev[3 + 2 * cls], 0));
+    }
+    return LFR_OK;
+}
 
-    HIP_TRY(lfr::stream_wait(st));
+// What the diagnostic builds left in the solve's buffers (-DLFR_TRACE_TREE, -DLFR_PROFILE_FACTOR, -DLFR_PROFILE_PHASES), and the bounded
+// spins that ran out; the solve's stream has been waited for.
+int read_diagnostics(lfr_batch *b, const KernelArgs &a) {
 #ifdef LFR_TRACE_TREE
     if (const char *tf = getenv("LFR_TREE_TRACE_FILE")) {
         unsigned long long n = 0;
@@ -864,38 +935,45 @@ int lfr_batch_solve(lfr_batch *b, void *hip_stream, lfr_solve_stats *stats) {
 #endif
 #ifdef LFR_PROFILE_FACTOR
     {
-        unsigned long long h[64];
-        HIP_TRY(hipMemcpy(h, b->d_prof + 8 * lfr::KC_COUNT + 8, sizeof h, hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemset(b->d_prof + 8 * lfr::KC_COUNT + 8, 0, sizeof h));
-        for (int c = 0; c < 4; ++c) for (int w = 0; w < 2; ++w) if (h[16 * c + 8 * w + 7])
-            fprintf(stderr, "lfr-fprof class %d wave %d: factorizations %llu  cycles each: diag %.0f  trailing %.0f  wait %.0f  col-update %.0f  col-finish %.0f  barrier %.0f   (wave 0: diag = loads + elimination, trailing = its stores)\n",
-                    lfr::KC_BLOCK + c, w, h[16 * c + 8 * w + 7], (double)h[16 * c + 8 * w] / h[16 * c + 8 * w + 7], (double)h[16 * c + 8 * w + 1] / h[16 * c + 8 * w + 7],
-                    (double)h[16 * c + 8 * w + 2] / h[16 * c + 8 * w + 7], (double)h[16 * c + 8 * w + 3] / h[16 * c + 8 * w + 7],
-                    (double)h[16 * c + 8 * w + 4] / h[16 * c + 8 * w + 7], (double)h[16 * c + 8 * w + 5] / h[16 * c + 8 * w + 7]);
+        unsigned long long h[lfr::kProfFactorWords * (lfr::KC_COUNT - lfr::KC_BLOCK)];
+        HIP_TRY(hipMemcpy(h, lfr::factor_profile(b->d_prof, lfr::KC_BLOCK), sizeof h, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemset(lfr::factor_profile(b->d_prof, lfr::KC_BLOCK), 0, sizeof h));
+        for (int c = 0; c < lfr::KC_COUNT - lfr::KC_BLOCK; ++c) for (int w = 0; w < 2; ++w) {
+            const unsigned long long *q = h + lfr::kProfFactorWords * c + 8 * w;
+            if (q[7])
+                fprintf(stderr, "lfr-fprof class %d wave %d: factorizations %llu  cycles each: diag %.0f  trailing %.0f  wait %.0f  col-update %.0f  col-finish %.0f  barrier %.0f   (wave 0: diag = loads + elimination, trailing = its stores)\n",
+                        lfr::KC_BLOCK + c, w, q[7], (double)q[0] / q[7], (double)q[1] / q[7], (double)q[2] / q[7], (double)q[3] / q[7], (double)q[4] / q[7], (double)q[5] / q[7]);
+        }
     }
 #endif
 #ifdef LFR_PROFILE_PHASES
     {
-        unsigned long long h[8 * lfr::KC_COUNT];
+        unsigned long long h[lfr::kProfPhases * lfr::KC_COUNT];
         HIP_TRY(hipMemcpy(h, b->d_prof, sizeof h, hipMemcpyDeviceToHost));
         HIP_TRY(hipMemset(b->d_prof, 0, sizeof h));
-        for (int c = 0; c < lfr::KC_COUNT; ++c) if (h[c * 8 + 7])
-            fprintf(stderr, "lfr-prof class %d: waves %llu  per-wave cycles: [0] %.0f  [1] %.0f  [2] %.0f  [3] %.0f  [4] %.0f  [5] %.0f  [6] %.0f   (packed: prologue/elim/sweep/reduce/transitions/setup/zero; block: jac-sweeps/factor/ls-sweeps/-/bookkeeping/scaling/trisolve)\n", c,
-                    h[c * 8 + 7], (double)h[c * 8] / h[c * 8 + 7], (double)h[c * 8 + 1] / h[c * 8 + 7], (double)h[c * 8 + 2] / h[c * 8 + 7],
-                    (double)h[c * 8 + 3] / h[c * 8 + 7], (double)h[c * 8 + 4] / h[c * 8 + 7], (double)h[c * 8 + 5] / h[c * 8 + 7], (double)h[c * 8 + 6] / h[c * 8 + 7]);
-    }
-#endif
-    {   // bounded spins that ran out (wave hand-offs of the factorizations, the teams' barriers): a rejected LM step or a failed
-        // component instead of a hung GPU - visible under LFR_VERBOSE, an ERROR under LFR_SPIN_TIMEOUT_FATAL=1 (the GPU tests set it)
-        static const bool verbose = getenv("LFR_VERBOSE") != nullptr;
-        static const bool fatal = [] { const char *e = getenv("LFR_SPIN_TIMEOUT_FATAL"); return e && e[0] == '1'; }();
-        if ((verbose || fatal) && b->class_begin[lfr::KC_COUNT] > b->class_begin[lfr::KC_BLOCK]) {
-            unsigned int v = 0;
-            HIP_TRY(hipMemcpy(&v, a.queue + 15, sizeof v, hipMemcpyDeviceToHost));
-            if (v && verbose) fprintf(stderr, "lfr: %u bounded spin-wait(s) of the workgroup kernels ran out during this solve (rejected LM steps / failed components)\n", v);
-            if (v && fatal) { lfr::set_error("%u bounded spin-wait(s) of the workgroup kernels ran out (LFR_SPIN_TIMEOUT_FATAL=1)", v); return LFR_ERR_HIP; }
+        for (int c = 0; c < lfr::KC_COUNT; ++c) {
+            const unsigned long long *q = h + lfr::kProfPhases * c;
+            if (q[7])
+                fprintf(stderr, "lfr-prof class %d: waves %llu  per-wave cycles: [0] %.0f  [1] %.0f  [2] %.0f  [3] %.0f  [4] %.0f  [5] %.0f  [6] %.0f   (packed: prologue/elim/sweep/reduce/transitions/setup/zero; block: jac-sweeps/factor/ls-sweeps/-/bookkeeping/scaling/trisolve)\n", c,
+                        q[7], (double)q[0] / q[7], (double)q[1] / q[7], (double)q[2] / q[7], (double)q[3] / q[7], (double)q[4] / q[7], (double)q[5] / q[7], (double)q[6] / q[7]);
         }
     }
+#endif
+    // bounded spins that ran out (wave hand-offs of the factorizations, the teams' barriers): a rejected LM step or a failed
+    // component instead of a hung GPU - visible under LFR_VERBOSE, an ERROR under LFR_SPIN_TIMEOUT_FATAL=1 (the GPU tests set it)
+    static const bool verbose = getenv("LFR_VERBOSE") != nullptr;
+    static const bool fatal = [] { const char *e = getenv("LFR_SPIN_TIMEOUT_FATAL"); return e && e[0] == '1'; }();
+    if ((verbose || fatal) && b->class_begin[lfr::KC_COUNT] > b->class_begin[lfr::KC_BLOCK]) {
+        unsigned int v = 0;
+        HIP_TRY(hipMemcpy(&v, a.queue + lfr::kQueueSpinTimeouts, sizeof v, hipMemcpyDeviceToHost));
+        if (v && verbose) fprintf(stderr, "lfr: %u bounded spin-wait(s) of the workgroup kernels ran out during this solve (rejected LM steps / failed components)\n", v);
+        if (v && fatal) { lfr::set_error("%u bounded spin-wait(s) of the workgroup kernels ran out (LFR_SPIN_TIMEOUT_FATAL=1)", v); return LFR_ERR_HIP; }
+    }
+    return LFR_OK;
+}
+
+// the statistics of the solve just waited for: the infos come to the host, `recorded` names the launches that were bracketed by events
+int collect_stats(lfr_batch *b, uint32_t recorded, hipStream_t st, lfr_solve_stats *stats) {
     memset(stats, 0, sizeof *stats);
     float ms = 0.f;
     HIP_TRY(hipEventElapsedTime(&ms, b->ev[0], b->ev[1]));
@@ -947,41 +1025,81 @@ int lfr_batch_solve(lfr_batch *b, void *hip_stream, lfr_solve_stats *stats) {
     return LFR_OK;
 }
 
-// Bounded spins that ran out during the batch's latest solve (the hand-off flags of the LDS factorization, the dependency counters of
-// the elimination-tree kernel): a timeout rejects an LM step instead of hanging the GPU, so it must be visible - 0 in every test.
-int64_t lfr_batch_spin_timeouts(lfr_batch *b) {
+// A 32-bit control word of the batch's latest solve - of the team words, or of the queue block - read once that solve's stream has
+// drained; 0 when nothing has been solved or the batch has no such block.
+int64_t read_solve_word(lfr_batch *b, bool team, int word) {
     if (!b) { lfr::set_error("bad argument"); return LFR_ERR_ARG; }
-    if (b->n_solves == 0 || !b->d_prof) return 0;
+    const unsigned int *block = team ? b->d_team_ctl : b->d_prof ? lfr::queue_block(b->d_prof) : nullptr;
+    if (b->n_solves == 0 || !block) return 0;
     HIP_TRY(hipSetDevice(b->device));
     HIP_TRY(hipStreamSynchronize(b->last_stream));
     unsigned int v = 0;
-    HIP_TRY(hipMemcpy(&v, reinterpret_cast<unsigned int *>(b->d_prof + 8 * lfr::KC_COUNT) + 15, sizeof v, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(&v, block + word, sizeof v, hipMemcpyDeviceToHost));
     return (int64_t)v;
 }
+
+}  // namespace
+
+extern "C" {
+
+int lfr_batch_solve(lfr_batch *b, void *hip_stream, lfr_solve_stats *stats) {
+    if (!b) { lfr::set_error("bad argument"); return LFR_ERR_ARG; }
+    host_trace("lfr_batch_solve enters");
+    HIP_TRY(hipSetDevice(b->device));
+    hipStream_t st = (hipStream_t)hip_stream;
+    KernelArgs a = make_kernel_args(b);
+#ifdef LFR_TRACE_TREE
+    static unsigned long long *d_trace = nullptr;
+    if (!d_trace) { HIP_TRY(hipMalloc(&d_trace, ((size_t)1 << 20) * 8 + 64)); }
+    HIP_TRY(hipMemsetAsync(d_trace, 0, 64, st));
+    a.trace = d_trace;
+#endif
+    bool materialised = false;
+    if (b->fused && b->n_solves > 0) {           // solved before: this batch is being re-used - write the records once, read them from now on
+        lfr::materialize_records(b, st);
+        HIP_TRY(hipGetLastError());
+        b->fused = false;
+        materialised = true;
+    }
+    if (b->inputs_pending) {             // records rewritten by lfr_batch_set_inputs, possibly on another stream
+        if (b->inputs_stream != st) HIP_TRY(hipStreamWaitEvent(st, b->ev_inputs, 0));
+        b->inputs_pending = false;
+    }
+    b->solved_epoch = b->inputs_epoch;
+    b->ev = b->ev_ring + (b->n_solves % lfr_batch::kSlots) * lfr_batch::kEvPerSlot;
+    uint32_t &recorded = b->ev_recorded[b->n_solves % lfr_batch::kSlots];
+    recorded = 0;
+    ++b->n_solves;
+    b->last_stream = st;
+    if (!b->ev[0]) for (int i = 0; i < lfr_batch::kEvPerSlot; ++i) if (!(b->ev[i] = b->ctx->event_acquire(true))) return LFR_ERR_HIP;
+    HIP_TRY(hipEventRecord(b->ev[0], st));
+    if (b->class_begin[lfr::KC_COUNT] > b->class_begin[lfr::KC_BLOCK]) {
+        HIP_TRY(hipStreamWaitEvent(st, b->ev_order, 0));
+        HIP_TRY(hipMemsetAsync(a.queue, 0, lfr::kQueueWords * sizeof(unsigned int), st));      // the classes' component queues
+        if (b->d_team_ctl) HIP_TRY(hipMemsetAsync(b->d_team_ctl, 0, lfr::solve_geometry().team_ctl_words * sizeof(unsigned int), st));   // registrations, mailboxes, barrier counters of the teams
+    }
+    { const int rc = b->serial ? launch_serial(b, a, recorded, st) : launch_plan(b, a, materialised, recorded, st); if (rc != LFR_OK) return rc; }
+    HIP_TRY(hipEventRecord(b->ev[1], st));
+    b->infos_valid = false;
+    host_trace("lfr_batch_solve: launched");
+    if (!stats) return LFR_OK;
+
+    HIP_TRY(lfr::stream_wait(st));
+    { const int rc = read_diagnostics(b, a); if (rc != LFR_OK) return rc; }
+    return collect_stats(b, recorded, st, stats);
+}
+
+// Bounded spins that ran out during the batch's latest solve (the hand-off flags of the LDS factorization, the dependency counters of
+// the elimination-tree kernel): a timeout rejects an LM step instead of hanging the GPU, so it must be visible - 0 in every test.
+int64_t lfr_batch_spin_timeouts(lfr_batch *b) { return read_solve_word(b, false, lfr::kQueueSpinTimeouts); }
 
 // Components the latest solve handed to a TEAM of two or more workgroups (solve_tree_team_kernel); 0 when the batch has none above the
 // thresholds (LFR_TREE_TEAM) or no elimination-tree class at all.
-int64_t lfr_batch_team_runs(lfr_batch *b) {
-    if (!b) { lfr::set_error("bad argument"); return LFR_ERR_ARG; }
-    if (b->n_solves == 0 || !b->d_team_ctl) return 0;
-    HIP_TRY(hipSetDevice(b->device));
-    HIP_TRY(hipStreamSynchronize(b->last_stream));
-    unsigned int v = 0;
-    HIP_TRY(hipMemcpy(&v, b->d_team_ctl + 10, sizeof v, hipMemcpyDeviceToHost));
-    return (int64_t)v;
-}
+int64_t lfr_batch_team_runs(lfr_batch *b) { return read_solve_word(b, true, lfr::kCtlTeamRuns); }
 
 // Components the latest solve's teams could not serve at their size and a single workgroup solved instead (SOLO mode: the comment above
 // TeamCtx, Residency) - 0 whenever the launch's workgroups were resident together.
-int64_t lfr_batch_team_fallbacks(lfr_batch *b) {
-    if (!b) { lfr::set_error("bad argument"); return LFR_ERR_ARG; }
-    if (b->n_solves == 0 || !b->d_team_ctl) return 0;
-    HIP_TRY(hipSetDevice(b->device));
-    HIP_TRY(hipStreamSynchronize(b->last_stream));
-    unsigned int v = 0;
-    HIP_TRY(hipMemcpy(&v, b->d_team_ctl + 13, sizeof v, hipMemcpyDeviceToHost));
-    return (int64_t)v;
-}
+int64_t lfr_batch_team_fallbacks(lfr_batch *b) { return read_solve_word(b, true, lfr::kCtlOffSize); }
 
 // Test infrastructure: `workgroups` 512-thread workgroups of 256 registers per lane (a whole CU each, like the elimination-tree kernel's)
 // that do nothing but stay resident for `milliseconds`, on a stream of their own; returns once they have started.

@@ -1,9 +1,11 @@
-// What the solver's translation units share (internal): the kernel argument blocks, the batch (lfr_batch, include/lfr.h's opaque
-// handle) and the host-side interface between them.  No kernel bodies.
-//   lfr_solve.hip        the forward kernels, their debug probes, and the launch functions declared at the end of this header
-//   lfr_batch.hip        batch creation, the launch plan of lfr_batch_solve, timing, downloads, warm-up, multi-GPU entry points
-//   lfr_backward.hip     implicit-gradient backward pass (lfr_batch_backward)
-//   lfr_covariance.hip   per-keypoint covariance (lfr_batch_covariance)
+// What the solver's translation units share (internal): the kernel argument blocks, the layout of the control words that kernels and
+// host code both touch, the batch (lfr_batch, include/lfr.h's opaque handle), the state of a pass that runs after a solve (PassState)
+// and the host-side interface between the units.  No kernel bodies.
+//   lfr_solve.hip        the forward kernels, their debug probes, and the launch functions declared in this header
+//   lfr_batch.hip        batch creation, the launch plan of lfr_batch_solve (packed_ranges deals the packed launch), its diagnostic
+//                        read-backs and statistics, the PassState functions, timing, downloads, warm-up, multi-GPU entry points
+//   lfr_backward.hip     implicit-gradient backward pass (lfr_batch_backward): kernels, its own carvings, the launches
+//   lfr_covariance.hip   per-keypoint covariance (lfr_batch_covariance): kernels, the launches
 //   lfr_inputs.hip       new flows / similarities into a live batch (lfr_batch_set_inputs) and the record -> directed-edge map
 #pragma once
 
@@ -65,6 +67,35 @@ struct KernelArgs {
     unsigned long long *trace;  // -DLFR_TRACE_TREE: [0] = words used, then {s_memtime, type << 56 | wave of the team << 48 | iteration << 32 | column} pairs
 };
 
+// ---- control words: the ONE statement of where they live, for the kernels (lfr_solve.hip) and for the host code that zeroes and reads
+// them.  What the team words mean: the comment above TeamCtx in lfr_solve.hip. ----
+// KernelArgs::team_ctl, 32-bit words, zeroed per solve
+constexpr int kTeamXccs = 8;                 // XCDs a launch registers with
+constexpr int kCtlRegisteredXcc = 0;         // [0 .. kTeamXccs): workgroups registered per XCC
+constexpr int kCtlRegistered = 8;            // registered in total
+constexpr int kCtlAbort = 9;                 // a bounded spin ran out somewhere: every wait gives up
+constexpr int kCtlTeamRuns = 10;             // components solved by a team (lfr_batch_team_runs)
+constexpr int kCtlSolo = 11;                 // SOLO mode
+constexpr int kCtlAtWork = 12;               // components being solved right now
+constexpr int kCtlOffSize = 13;              // components solved off their team size (lfr_batch_team_fallbacks)
+constexpr int kCtlMailbox = 16;              // [kCtlMailbox + kCtlUnitWords * unit + member]: mailbox of a unit's member
+constexpr int kCtlUnitWords = 16;            // words per unit: mailboxes, then ...
+constexpr int kCtlUnitArrival = 8;           // ... from here the arrival counters, one per leader rank
+static_assert(kTeamXccs <= kCtlRegistered && kCtlOffSize < kCtlMailbox, "team control words");
+// KernelArgs::queue, the queue block: 32-bit words, zeroed per solve - word cls is the next component of workgroup class cls
+constexpr int kQueueWords = 16;
+constexpr int kQueueSpinTimeouts = 15;       // bounded spins that ran out during the solve (lfr_batch_spin_timeouts)
+static_assert(KC_COUNT <= kQueueSpinTimeouts, "queue block");
+// KernelArgs::prof, the batch's slab of 64-bit words: phase counters [cls * kProfPhases + phase] (-DLFR_PROFILE_PHASES), the queue
+// block, then kProfFactorWords per workgroup class (-DLFR_PROFILE_FACTOR: two waves x 8)
+constexpr int kProfPhases = 8;
+constexpr int kProfQueue = kProfPhases * KC_COUNT;
+constexpr int kProfFactor = kProfQueue + kQueueWords / 2;
+constexpr int kProfFactorWords = 16;
+constexpr size_t kProfWords = kProfFactor + kProfFactorWords * (KC_COUNT - KC_BLOCK);
+__host__ __device__ inline unsigned int *queue_block(unsigned long long *prof) { return reinterpret_cast<unsigned int *>(prof + kProfQueue); }
+__host__ __device__ inline unsigned long long *factor_profile(unsigned long long *prof, int cls) { return prof + kProfFactor + kProfFactorWords * (cls - KC_BLOCK); }
+
 // solve_packed_kernel / covariance_packed_kernel: blocks [blk_begin[i], blk_begin[i+1]) of the one launch belong to packed class i
 struct PackedRanges {
     int blk_begin[6];          // G64_4, G64_2, G32, G16, G8 in dispatch order
@@ -94,15 +125,43 @@ void launch_warmup();                    // an empty kernel of lfr_solve.hip: lo
 // =============================================================================================
 // the batch
 // =============================================================================================
-constexpr size_t kProfWords = 8 * lfr::KC_COUNT + 8 + 64;  // phase counters of -DLFR_PROFILE_PHASES + 16 32-bit class queues + -DLFR_PROFILE_FACTOR (16 per workgroup class)
+using lfr::kProfWords;                                  // (d_prof: the layout block above)
 
 constexpr uint32_t kPackedEventsAliased = 1u << 31;     // ev_recorded: the packed launch is timed by the solve's own pair of events
-struct BwdState;                                        // lfr_backward.hip
-void bwd_free(BwdState *s);
-hipEvent_t bwd_last_event(const BwdState *s);           // end of the latest backward (nullptr: none has run)
-struct CovState;                                        // lfr_covariance.hip
-void cov_free(CovState *s);
-hipEvent_t cov_last_event(const CovState *s);           // end of the latest covariance (nullptr: none has run)
+
+namespace lfr {
+// What a pass that runs after a solve (backward, covariance) keeps per batch, set up on its first call: workspace and offsets of the
+// dense triangles of the components above the LDS classes, a status word per descriptor, the events around its latest call.
+struct PassState {
+    DevArena slab;
+    double *d_hws = nullptr;
+    uint64_t *d_hws_off = nullptr;
+    int32_t *d_status = nullptr;
+    int rows_max[KC_COUNT] = {0};
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    hipStream_t last_stream = nullptr;
+    int64_t n_calls = 0;
+    virtual ~PassState() = default;                     // (a pass may derive its own fields: the backward does)
+};
+struct PassKind {                                       // what differs between the passes
+    const char *name;                                   // "backward": lfr_batch_backward in the messages
+    PassState *(*make)();                               // the pass's own state type
+    // the pass's part of the setup, run once the shared carvings are made: its own carvings from s->slab (the extra_bytes of
+    // pass_begin are there for them) and the dynamic-LDS reservation of its kernels
+    int (*extra)(lfr_batch *b, PassState *s);
+};
+void pass_free(PassState *s);                           // waits for the latest call
+hipEvent_t pass_last_event(const PassState *s);         // end of the latest call (nullptr: none has run)
+// Entry of lfr_batch_<name>: the checks that do not depend on the arguments (solved at all, inputs epoch), hipSetDevice, the setup on the
+// first call (*slot is installed only after every step has succeeded; slab and events are released on every error path), the wait
+// for the latest solve, the record of ev0 on st.
+int pass_begin(lfr_batch *b, PassState **slot, const PassKind &kind, size_t extra_bytes, hipStream_t st);
+int pass_end(PassState *s, hipStream_t st);             // records ev1; the call is now the pass's latest
+int64_t pass_status(lfr_batch *b, PassState *s, const char *name, int32_t *status);     // lfr_batch_<name>_status
+int pass_histogram(lfr_batch *b, PassState *s, hipStream_t st, int64_t count[3], double *kernel_ms);     // waits for the latest call: descriptors with status 0, 1, 2 and the time between its events
+// deals the blocks of the one packed launch to the packed classes, waves_per_block waves each (components per wave: solve_geometry())
+void packed_ranges(const lfr_batch *b, int waves_per_block, PackedRanges *r, int *n_blocks);
+}  // namespace lfr
 struct lfr_batch {
     int device = 0;
     lfr::DevCtx *ctx = nullptr;
@@ -191,13 +250,12 @@ struct lfr_batch {
     hipEvent_t ev_inputs = nullptr;      // end of the latest lfr_batch_set_inputs
     hipStream_t inputs_stream = nullptr;
     bool inputs_pending = false;         // no solve has been issued since: the next one waits for ev_inputs
-    BwdState *bwd = nullptr;
-    CovState *cov = nullptr;             // per-keypoint covariance (lfr_covariance.hip): set up on the first lfr_batch_covariance
+    lfr::PassState *bwd = nullptr, *cov = nullptr;       // lfr_backward.hip / lfr_covariance.hip: set up on the first call
 
     lfr_batch() { for (auto &e : ev_ring) e = nullptr; }
     ~lfr_batch() {
-        bwd_free(bwd);
-        cov_free(cov);
+        lfr::pass_free(bwd);
+        lfr::pass_free(cov);
         if (ctx) {
             (void)hipSetDevice(device);
             if (n_solves > 0) (void)hipStreamSynchronize(last_stream);      // nothing may still use the slab

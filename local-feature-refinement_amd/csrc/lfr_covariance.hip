@@ -15,7 +15,6 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <memory>
 #include <type_traits>
 #include <cstring>
 #include <vector>
@@ -27,7 +26,6 @@
 using namespace lfrdev;
 using lfr::KernelArgs;
 using lfr::PackedRanges;
-using lfr::ensure_mirrors;
 
 namespace {
 
@@ -345,63 +343,16 @@ size_t cov_lds_bytes(int rows, bool lds_matrix, int &scratch_doubles) {
     return mat + scratch;
 }
 
-}  // namespace
-
-struct CovState {
-    lfr::DevArena slab;
-    double *d_hws = nullptr;
-    uint64_t *d_hws_off = nullptr;
-    int32_t *d_status = nullptr;
-    int rows_max[lfr::KC_COUNT] = {0};
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    hipStream_t last_stream = nullptr;
-    int64_t n_calls = 0;
-};
-
-void cov_free(CovState *s) {
-    if (!s) return;
-    if (s->last_stream || s->n_calls) (void)hipStreamSynchronize(s->last_stream);
-    if (s->ev0) (void)hipEventDestroy(s->ev0);
-    if (s->ev1) (void)hipEventDestroy(s->ev1);
-    delete s;
-}
-
-hipEvent_t cov_last_event(const CovState *s) { return s && s->n_calls ? s->ev1 : nullptr; }
-
-namespace {
-
-int cov_setup(lfr_batch *b) {
-    int rc = ensure_mirrors(b);
-    if (rc != LFR_OK) return rc;
-    std::unique_ptr<CovState, void (*)(CovState *)> s(new CovState(), cov_free);
-    const size_t nd = std::max<size_t>(b->descs.size(), 1);
-    std::vector<uint64_t> off(nd, 0);
-    uint64_t hws = 0;
-    for (size_t i = 0; i < b->descs.size(); ++i) {
-        const int cls = b->desc_class[i], rows = 2 * b->descs[i].n_var;
-        s->rows_max[cls] = std::max(s->rows_max[cls], rows);
-        if (cls == lfr::KC_GLOBAL) {
-            if (rows > kBwdMaxRows) { lfr::set_error("covariance: a component of %d rows exceeds the dense factorization's %d", rows, kBwdMaxRows); return LFR_ERR_UNSUPPORTED; }
-            off[i] = hws; hws += bwd_tri(rows, 0);
-        }
-    }
-    if (!s->slab.init(b->ctx, 8 * hws + 8 * nd + 4 * nd + ((size_t)1 << 16))) return LFR_ERR_NOMEM;
-    s->d_hws = s->slab.take_n<double>(std::max<uint64_t>(hws, 1));
-    s->d_hws_off = s->slab.take_n<uint64_t>(nd);
-    s->d_status = s->slab.take_n<int32_t>(nd);
-    if (!s->d_hws || !s->d_hws_off || !s->d_status) { lfr::set_error("covariance slab exhausted"); return LFR_ERR_NOMEM; }
-    HIP_TRY(hipEventCreate(&s->ev0)); HIP_TRY(hipEventCreate(&s->ev1));
-    hipStream_t st = b->ctx->s_main;
-    HIP_TRY(hipMemcpyAsync(s->d_hws_off, off.data(), 8 * nd, hipMemcpyHostToDevice, st));
-    HIP_TRY(lfr::stream_wait(st));
+int cov_setup_extra(lfr_batch *, lfr::PassState *) {
     int sd = 0;
     HIP_TRY(hipFuncSetAttribute((const void *)covariance_block_kernel<kCovThreads, true>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                 (int)cov_lds_bytes(lfr::kBlockMaxRows, true, sd)));
     HIP_TRY(hipFuncSetAttribute((const void *)covariance_block_kernel<kCovThreads, false>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                 (int)cov_lds_bytes(kBwdMaxRows, false, sd)));
-    b->cov = s.release();
     return LFR_OK;
 }
+
+const lfr::PassKind kCovariance = {"covariance", [] { return new lfr::PassState(); }, cov_setup_extra};
 
 }  // namespace
 
@@ -409,27 +360,15 @@ extern "C" {
 
 int lfr_batch_covariance(lfr_batch *b, void *cov_device, int flags, void *hip_stream, lfr_covariance_stats *stats) {
     if (!b || !cov_device || (flags & ~LFR_COVARIANCE_F64)) { lfr::set_error("bad argument"); return LFR_ERR_ARG; }
-    if (b->n_solves == 0) { lfr::set_error("lfr_batch_covariance: the batch has not been solved"); return LFR_ERR_ARG; }
-    if (b->inputs_epoch != b->solved_epoch) { lfr::set_error("lfr_batch_covariance: inputs changed since the latest solve"); return LFR_ERR_ARG; }
-    HIP_TRY(hipSetDevice(b->device));
-    if (!b->cov) { const int rc = cov_setup(b); if (rc != LFR_OK) return rc; }
-    CovState &s = *b->cov;
     hipStream_t st = (hipStream_t)hip_stream;
     const int f64 = (flags & LFR_COVARIANCE_F64) ? 1 : 0;
-    HIP_TRY(hipStreamWaitEvent(st, b->ev[1], 0));                               // the latest solve's positions and termination codes
-    HIP_TRY(hipEventRecord(s.ev0, st));
+    { const int rc = lfr::pass_begin(b, &b->cov, kCovariance, 0, st); if (rc != LFR_OK) return rc; }
+    lfr::PassState &s = *b->cov;
     if (b->n_graph_nodes) HIP_TRY(hipMemsetAsync(cov_device, 0, 3 * (size_t)b->n_graph_nodes * (f64 ? 8 : 4), st));
-    {   // packed classes: one launch, the blocks dealt as lfr_batch_solve deals them
-        static const int kOrder[5] = {lfr::KC_G64_4, lfr::KC_G64_2, lfr::KC_G32, lfr::KC_G16, lfr::KC_G8};
-        static const int kGroups[5] = {1, 2, 2, 4, 8};
+    {   // packed classes: one launch of one-wave blocks, dealt as lfr_batch_solve deals its own
         PackedRanges r;
         int nb = 0;
-        for (int i = 0; i < 5; ++i) {
-            r.blk_begin[i] = nb;
-            r.desc_begin[i] = b->class_begin[kOrder[i]]; r.desc_end[i] = b->class_begin[kOrder[i] + 1];
-            nb += (r.desc_end[i] - r.desc_begin[i] + kGroups[i] - 1) / kGroups[i];
-        }
-        r.blk_begin[5] = nb;
+        lfr::packed_ranges(b, 1, &r, &nb);
         CovArgs a;
         memset(&a, 0, sizeof(a));
         a.k.descs = b->d_descs; a.k.edges = b->d_edges; a.k.node_ids = b->d_node_ids; a.k.positions = b->d_positions; a.k.infos = b->d_infos;
@@ -464,38 +403,17 @@ int lfr_batch_covariance(lfr_batch *b, void *cov_device, int flags, void *hip_st
         }
     }
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(s.ev1, st));
-    s.last_stream = st;
-    ++s.n_calls;
+    { const int rc = lfr::pass_end(&s, st); if (rc != LFR_OK) return rc; }
     if (stats) {
-        HIP_TRY(hipEventSynchronize(s.ev1));
-        std::vector<int32_t> status(b->descs.size());
-        if (!status.empty()) HIP_TRY(hipMemcpyAsync(status.data(), s.d_status, 4 * status.size(), hipMemcpyDeviceToHost, st));
-        HIP_TRY(lfr::stream_wait(st));
+        int64_t count[3];
         memset(stats, 0, sizeof(*stats));
-        for (int32_t v : status) {
-            if (v == 0) ++stats->n_computed;
-            else if (v == 1) ++stats->n_not_usable;
-            else ++stats->n_singular;
-        }
-        float ms = 0.f;
-        HIP_TRY(hipEventElapsedTime(&ms, s.ev0, s.ev1));
-        stats->kernel_ms = ms;
+        { const int rc = lfr::pass_histogram(b, &s, st, count, &stats->kernel_ms); if (rc != LFR_OK) return rc; }
+        stats->n_computed = count[0]; stats->n_not_usable = count[1]; stats->n_singular = count[2];
     }
     return LFR_OK;
 }
 
-int64_t lfr_batch_covariance_status(lfr_batch *b, int32_t *status) {
-    if (!b || !b->cov || !b->cov->n_calls) { lfr::set_error("lfr_batch_covariance_status: no covariance has run on this batch"); return LFR_ERR_ARG; }
-    HIP_TRY(hipSetDevice(b->device));
-    HIP_TRY(hipEventSynchronize(b->cov->ev1));
-    const size_t n = b->descs.size();
-    if (status && n) {
-        HIP_TRY(hipMemcpyAsync(status, b->cov->d_status, 4 * n, hipMemcpyDeviceToHost, b->cov->last_stream));
-        HIP_TRY(lfr::stream_wait(b->cov->last_stream));
-    }
-    return (int64_t)n;
-}
+int64_t lfr_batch_covariance_status(lfr_batch *b, int32_t *status) { return lfr::pass_status(b, b ? b->cov : nullptr, "covariance", status); }
 
 int lfr_debug_invert_spd(int device, int solver, int64_t n_sys, const int32_t *n_rows, const double *A, double *Cinv, int32_t *status) {
     static const int kLimit[4] = {8, 16, 24, 32};

@@ -147,8 +147,8 @@ int lfr_batch_set_inputs(lfr_batch *b, const float *disp1_device, const float *d
     hipStream_t st = (hipStream_t)hip_stream;
     // everything that reads the records: the latest solve, backward and covariance, whatever streams they ran on
     if (b->n_solves > 0) HIP_TRY(hipStreamWaitEvent(st, b->ev[1], 0));
-    if (hipEvent_t e = bwd_last_event(b->bwd)) HIP_TRY(hipStreamWaitEvent(st, e, 0));
-    if (hipEvent_t e = cov_last_event(b->cov)) HIP_TRY(hipStreamWaitEvent(st, e, 0));
+    for (const lfr::PassState *pass : {b->bwd, b->cov})
+        if (hipEvent_t e = lfr::pass_last_event(pass)) HIP_TRY(hipStreamWaitEvent(st, e, 0));
     if (b->inputs_epoch > 0 && b->inputs_stream != st) HIP_TRY(hipStreamWaitEvent(st, b->ev_inputs, 0));
     if (b->fused) {          // complete records first (words, and whichever of flows / similarity this call keeps), from the graph's arrays
         lfr::materialize_records(b, st);

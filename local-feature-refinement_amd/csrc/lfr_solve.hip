@@ -61,7 +61,7 @@ namespace {
 #ifdef LFR_PROFILE_PHASES
 #define PROF_DECL unsigned long long pt_[7] = {0, 0, 0, 0, 0, 0, 0}; unsigned long long pt0_ = __builtin_amdgcn_s_memtime();
 #define PROF_MARK(i) do { const unsigned long long t_ = __builtin_amdgcn_s_memtime(); pt_[i] += t_ - pt0_; pt0_ = t_; } while (0)
-#define PROF_FLUSH() do { if (lane == 0) for (int i_ = 0; i_ < 7; ++i_) atomicAdd(&a.prof[a.cls * 8 + i_], pt_[i_]); if (lane == 0) atomicAdd(&a.prof[a.cls * 8 + 7], 1ull); } while (0)
+#define PROF_FLUSH() do { if (lane == 0) for (int i_ = 0; i_ < 7; ++i_) atomicAdd(&a.prof[a.cls * lfr::kProfPhases + i_], pt_[i_]); if (lane == 0) atomicAdd(&a.prof[a.cls * lfr::kProfPhases + 7], 1ull); } while (0)
 #elif defined(LFR_ISA_MARKS)
 // -DLFR_ISA_MARKS (scripts/isa_account.py, compile only): comments in the ISA that delimit the phases of the packed kernel, so that the
 // instructions of each phase can be counted by kind
@@ -1623,7 +1623,7 @@ __device__ __forceinline__ void solve_component(const KernelArgs &a, const int m
         PROF_MARK(5);                                 // 5: damping
         double *vinv = vgn;            // free until the line search
         {
-            factor_lds<kBlockThreads>(Mat, vinv, n, sh, a.prof ? a.prof + 8 * lfr::KC_COUNT + 8 + 16 * (a.cls - lfr::KC_BLOCK) : nullptr, a.queue + 15);        // 16-column panels, one barrier per panel (see factor_lds)
+            factor_lds<kBlockThreads>(Mat, vinv, n, sh, a.prof ? lfr::factor_profile(a.prof, a.cls) : nullptr, a.queue + lfr::kQueueSpinTimeouts);        // 16-column panels, one barrier per panel (see factor_lds)
         }
         __syncthreads();
         PROF_MARK(1);
@@ -1795,29 +1795,31 @@ struct TreeShared {
 // No `buffer_wbl2` / `buffer_inv` anywhere: nothing has to leave or re-enter the XCD.  Teams never span XCDs by construction
 // (registration below); workgroups that cannot complete a unit of their XCD work alone.
 //
-// Control words of a launch (KernelArgs::team_ctl, zeroed per solve): [0..7] workgroups registered per XCC, [8] registered in total,
-// [9] abort (a bounded spin ran out somewhere: every wait gives up, the components involved fail), [10] components solved by a team,
-// [11] SOLO mode (below), [12] components being solved right now, [13] components solved off their team size, [16 + 16 u + m] mailbox
-// of member m of unit u (a one-slot channel: the leader stores when it reads 0, the member clears), [16 + 16 u + 8 + L] arrival counter
-// of the team led by rank L, [kTeamUnitState + u] state of unit u (0 forming, 1 complete, 2 dissolved: decided ONCE by compare-and-swap,
-// so that the members of a unit agree).  Reduction slots (KernelArgs::team_red): per unit and leader, two parities x members x 4 doubles.
+// Control words of a launch (KernelArgs::team_ctl, zeroed per solve; the word numbers are the kCtl* constants of lfr_batch.hpp):
+// [kCtlRegisteredXcc + x] workgroups registered with XCC x, [kCtlRegistered] registered in total, [kCtlAbort] a bounded spin ran out
+// somewhere: every wait gives up, the components involved fail, [kCtlTeamRuns] components solved by a team, [kCtlSolo] SOLO mode
+// (below), [kCtlAtWork] components being solved right now, [kCtlOffSize] components solved off their team size,
+// [kCtlMailbox + kCtlUnitWords u + m] mailbox of member m of unit u (a one-slot channel: the leader stores when it reads 0, the member
+// clears), [kCtlMailbox + kCtlUnitWords u + kCtlUnitArrival + L] arrival counter of the team led by rank L, [kTeamUnitState + u] state
+// of unit u (0 forming, 1 complete, 2 dissolved: decided ONCE by compare-and-swap, so that the members of a unit agree).
+// Reduction slots (KernelArgs::team_red): per unit and leader, two parities x members x 4 doubles.
 //
 // Residency.  Units form from workgroups that are resident at the same time, and nothing guarantees that: another
 // kernel may hold CUs (the other classes of the same solve do, by design; so may another process or a smaller partition).  Waiting is
 // harmless while SOMEBODY works - a team at work ends, takes the next component, exits when the queue is empty, and the CUs it frees
-// bring the missing registrations.  The one state that would never end by itself: nobody at work ([12] = 0), the queue not empty, and
+// bring the missing registrations.  The one state that would never end by itself: nobody at work ([kCtlAtWork] = 0), the queue not empty, and
 // everyone resident waiting - in registration for members that cannot arrive, or at the head of the queue for a team size that does not
-// exist.  A waiter that sees [12] = 0 and neither a registration nor the queue's head move for team_patience_us (wall clock, 50 ms by
-// default) raises [11]: units still forming dissolve, and from then on ANY leader takes the head of the queue and solves it alone -
+// exist.  A waiter that sees [kCtlAtWork] = 0 and neither a registration nor the queue's head move for team_patience_us (wall clock, 50 ms by
+// default) raises [kCtlSolo]: units still forming dissolve, and from then on ANY leader takes the head of the queue and solves it alone -
 // the launch degrades to one workgroup per component (the plain solve_tree_kernel's way; that component's bits are those of a team of
-// one, counted in [13] = lfr_batch_team_fallbacks), no wait runs out, nothing fails.
+// one, counted in [kCtlOffSize] = lfr_batch_team_fallbacks), no wait runs out, nothing fails.
 #ifndef LFR_TEAM_MAX
 #define LFR_TEAM_MAX 8
 #endif
 constexpr int kTeamMax = LFR_TEAM_MAX;                     // workgroups per unit (a power of two <= 8)
 constexpr int kTeamUnitsPerXcc = 256 / kTeamMax;           // a launch has at most 256 workgroups
-constexpr int kTeamUnitState = 16 + 16 * 8 * kTeamUnitsPerXcc;
-constexpr int kTeamCtlWords = kTeamUnitState + 8 * kTeamUnitsPerXcc;
+constexpr int kTeamUnitState = lfr::kCtlMailbox + lfr::kCtlUnitWords * lfr::kTeamXccs * kTeamUnitsPerXcc;      // behind the units' words
+constexpr int kTeamCtlWords = kTeamUnitState + lfr::kTeamXccs * kTeamUnitsPerXcc;
 constexpr int kTeamRedPerUnit = (kTeamMax / 2) * 2 * kTeamMax * 16;
 constexpr unsigned kTeamMsgEnd = 0xf0000000u;
 static_assert(kTeamMax == 2 || kTeamMax == 4 || kTeamMax == 8, "team size");
@@ -1827,7 +1829,7 @@ struct TeamCtx {
     unsigned int target = 0;          // its value when everyone has arrived at the latest barrier
     double *red = nullptr;            // reduction slots [2][kTeamMax][16]: five {value, tag} granules per member
     unsigned gen = 0, epoch = 0;      // reductions of this team so far; the launch (tags of earlier launches linger in the slots)
-    unsigned int *ctl = nullptr;      // control words of the launch ([9] = abort)
+    unsigned int *ctl = nullptr;      // control words of the launch ([kCtlAbort]: a wait gave up)
     bool dead = false;                // this workgroup has seen the abort word: waits return at once
 };
 __device__ __forceinline__ unsigned team_ld(const unsigned int *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
@@ -1837,9 +1839,9 @@ __device__ __noinline__ bool team_wait_counter(unsigned int *p, unsigned target,
     int spins = 0;
     while ((int)(team_ld(p) - target) < 0) {
         __builtin_amdgcn_s_sleep(1);
-        if ((++spins & 255) == 0 && (team_ld(ctl + 9) != 0u || (spins >> limit_log2) != 0)) {
-            if (team_ld(ctl + 9) == 0u) atomicAdd(timeouts, 1u);
-            team_st(ctl + 9, 1u);
+        if ((++spins & 255) == 0 && (team_ld(ctl + lfr::kCtlAbort) != 0u || (spins >> limit_log2) != 0)) {
+            if (team_ld(ctl + lfr::kCtlAbort) == 0u) atomicAdd(timeouts, 1u);
+            team_st(ctl + lfr::kCtlAbort, 1u);
             return false;
         }
     }
@@ -1923,7 +1925,7 @@ __device__ __forceinline__ void solve_tree_component(const KernelArgs &a, const 
             tm.target += (unsigned)tS;
             if (tid == 0 && !tm.dead) {
                 __hip_atomic_fetch_add(tm.bar, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                if (!team_wait_counter(tm.bar, tm.target, tm.ctl, a.queue + 15, 22)) tm.dead = true;
+                if (!team_wait_counter(tm.bar, tm.target, tm.ctl, a.queue + lfr::kQueueSpinTimeouts, 22)) tm.dead = true;
             }
             __syncthreads();
         } else {
@@ -2001,8 +2003,8 @@ __device__ __forceinline__ void solve_tree_component(const KernelArgs &a, const 
                     }
                     if (__ballot(!got) == 0ull) break;
                     __builtin_amdgcn_s_sleep(1);
-                    if ((++spins & 255) == 0 && (__builtin_amdgcn_readfirstlane((int)team_ld(tm.ctl + 9)) != 0 || (spins >> 22) != 0)) {
-                        if (lane == 0) { if (team_ld(tm.ctl + 9) == 0u) atomicAdd(a.queue + 15, 1u); team_st(tm.ctl + 9, 1u); }
+                    if ((++spins & 255) == 0 && (__builtin_amdgcn_readfirstlane((int)team_ld(tm.ctl + lfr::kCtlAbort)) != 0 || (spins >> 22) != 0)) {
+                        if (lane == 0) { if (team_ld(tm.ctl + lfr::kCtlAbort) == 0u) atomicAdd(a.queue + lfr::kQueueSpinTimeouts, 1u); team_st(tm.ctl + lfr::kCtlAbort, 1u); }
                         tm.dead = true;
                         break;
                     }
@@ -2272,8 +2274,8 @@ __device__ __forceinline__ void solve_tree_component(const KernelArgs &a, const 
     auto spin_timeout = [&]() {
         if (lane == 0) {
             sh.flag = 1;
-            if constexpr (TEAM) { if (team_ld(tm.ctl + 9) == 0u) atomicAdd(a.queue + 15, 1u); team_st(tm.ctl + 9, 1u); team_st(gteam, 1u); }
-            else atomicAdd(a.queue + 15, 1u);
+            if constexpr (TEAM) { if (team_ld(tm.ctl + lfr::kCtlAbort) == 0u) atomicAdd(a.queue + lfr::kQueueSpinTimeouts, 1u); team_st(tm.ctl + lfr::kCtlAbort, 1u); team_st(gteam, 1u); }
+            else atomicAdd(a.queue + lfr::kQueueSpinTimeouts, 1u);
             if constexpr (PROBE) atomicOr(pb->status + ci, 2);
         }
         wdead = true;                                     // (this wave gives up waiting for the rest of the solve: one timeout must not cascade into seconds)
@@ -2294,7 +2296,7 @@ __device__ __forceinline__ void solve_tree_component(const KernelArgs &a, const 
         while (!ready()) {
             __builtin_amdgcn_s_sleep(2);
             ++spins;
-            if constexpr (TEAM) { if ((spins & 255) == 0 && __builtin_amdgcn_readfirstlane((int)team_ld(tm.ctl + 9)) != 0) { wdead = true; sh.flag = 1; break; } }
+            if constexpr (TEAM) { if ((spins & 255) == 0 && __builtin_amdgcn_readfirstlane((int)team_ld(tm.ctl + lfr::kCtlAbort)) != 0) { wdead = true; sh.flag = 1; break; } }
             if (spins > (1 << 22)) { spin_timeout(); break; }
         }
     };
@@ -2519,7 +2521,7 @@ __device__ __forceinline__ void solve_tree_component(const KernelArgs &a, const 
     };
     auto factor_thin = [&]() -> bool {
         double *xd = ts.x[wave];
-        unsigned long long *fprof = a.prof ? a.prof + 8 * lfr::KC_COUNT + 8 + 16 * (a.cls - lfr::KC_BLOCK) : nullptr;      // (-DLFR_PROFILE_FACTOR)
+        unsigned long long *fprof = a.prof ? lfr::factor_profile(a.prof, a.cls) : nullptr;      // (-DLFR_PROFILE_FACTOR)
         (void)fprof;
         FPROF_DECL
         // (the columns' state words are zeroed by the pass that builds the LM diagonal, in front of its barrier)
@@ -2566,7 +2568,7 @@ __device__ __forceinline__ void solve_tree_component(const KernelArgs &a, const 
     auto factor = [&]() -> bool {
         if (thin || TEAM) return factor_thin();           // (a team only ever takes thin plans: solve_tree_kernel)
         double *xd = ts.x[wave];                          // (sh.flag was reset before the caller's last barrier)
-        unsigned long long *fprof = a.prof ? a.prof + 8 * lfr::KC_COUNT + 8 + 16 * (a.cls - lfr::KC_BLOCK) : nullptr;      // (-DLFR_PROFILE_FACTOR)
+        unsigned long long *fprof = a.prof ? lfr::factor_profile(a.prof, a.cls) : nullptr;      // (-DLFR_PROFILE_FACTOR)
         (void)fprof;
         FPROF_DECL
         for (int l = 0; l < n_levels; ++l) {
@@ -2917,7 +2919,7 @@ __device__ __forceinline__ void solve_tree_component(const KernelArgs &a, const 
     PROF_MARK(4);
     PROF_FLUSH();
     tsync();
-    if constexpr (TEAM) { if (team_ld(tm.ctl + 9) != 0u) lm.term = LFR_TERM_FAILURE; }   // a wait of this launch's teams gave up: nothing computed since can be trusted
+    if constexpr (TEAM) { if (team_ld(tm.ctl + lfr::kCtlAbort) != 0u) lm.term = LFR_TERM_FAILURE; }   // a wait of this launch's teams gave up: nothing computed since can be trusted
     for (int p = gt; p < 8 * NB; p += GT) {
         const uint32_t v = ipos[p];
         if (v == kNone) continue;
@@ -2969,10 +2971,10 @@ __global__ __launch_bounds__(kBlockThreads) __attribute__((amdgpu_waves_per_eu((
 struct TeamWatch {
     unsigned long long t_last = 0ull, sig_last = ~0ull;
     __device__ __forceinline__ void look(const KernelArgs &a, unsigned int *ctl) {
-        const unsigned long long sig = (unsigned long long)team_ld(ctl + 8) << 32 | team_ld(a.queue + a.cls);
+        const unsigned long long sig = (unsigned long long)team_ld(ctl + lfr::kCtlRegistered) << 32 | team_ld(a.queue + a.cls);
         const unsigned long long now = __builtin_amdgcn_s_memrealtime();
-        if (sig != sig_last || team_ld(ctl + 12) != 0u) { sig_last = sig; t_last = now; return; }
-        if (now - t_last > 100ull * a.team_patience_us) team_st(ctl + 11, 1u);
+        if (sig != sig_last || team_ld(ctl + lfr::kCtlAtWork) != 0u) { sig_last = sig; t_last = now; return; }
+        if (now - t_last > 100ull * a.team_patience_us) team_st(ctl + lfr::kCtlSolo, 1u);
     }
 };
 __device__ __forceinline__ int tree_team_size(const KernelArgs &a, const int ci) {
@@ -2992,9 +2994,9 @@ __global__ __launch_bounds__(kBlockThreads) __attribute__((amdgpu_waves_per_eu((
     unsigned int *const ctl = a.team_ctl;
     if (tid == 0) {
         const unsigned xcc = __builtin_amdgcn_s_getreg((20 << 0) | (0 << 6) | (3 << 11)) & 7u;             // XCC_ID [3:0]
-        const unsigned slot = __hip_atomic_fetch_add(ctl + xcc, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        const unsigned slot = __hip_atomic_fetch_add(ctl + lfr::kCtlRegisteredXcc + xcc, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // (the XCD's count is out before the total says "everyone has registered")
-        __hip_atomic_fetch_add(ctl + 8, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_fetch_add(ctl + lfr::kCtlRegistered, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         const unsigned unit = slot / kTeamMax;
         // A unit is complete when kTeamMax workgroups of this XCD hold its slots, and dissolved when that cannot happen (the whole grid
         // has registered and the XCD's count is short) or the launch has gone SOLO.  Its members must agree, so the unit's state word
@@ -3008,11 +3010,11 @@ __global__ __launch_bounds__(kBlockThreads) __attribute__((amdgpu_waves_per_eu((
             TeamWatch watch;
             int spins = 0;
             while ((state = team_ld(us)) == 0u) {
-                if (team_ld(ctl + 11) != 0u) { decide(2u); continue; }
-                if (team_ld(ctl + 8) >= gridDim.x && team_ld(ctl + xcc) < (unit + 1u) * kTeamMax) { decide(2u); continue; }
+                if (team_ld(ctl + lfr::kCtlSolo) != 0u) { decide(2u); continue; }
+                if (team_ld(ctl + lfr::kCtlRegistered) >= gridDim.x && team_ld(ctl + lfr::kCtlRegisteredXcc + xcc) < (unit + 1u) * kTeamMax) { decide(2u); continue; }
                 __builtin_amdgcn_s_sleep(4);
                 if ((++spins & 255) == 0) {
-                    if (team_ld(ctl + 9) != 0u) { state = 2u; break; }
+                    if (team_ld(ctl + lfr::kCtlAbort) != 0u) { state = 2u; break; }
                     watch.look(a, ctl);
                 }
             }
@@ -3025,7 +3027,7 @@ __global__ __launch_bounds__(kBlockThreads) __attribute__((amdgpu_waves_per_eu((
     const int rank = (int)__builtin_amdgcn_readfirstlane(bc[1]);
     int S = (int)__builtin_amdgcn_readfirstlane(bc[2]);
     int L = S == 1 ? rank : 0;                            // leader of my team: ranks [L, L + S) of the unit
-    unsigned int *const mbox = ctl + 16 + 16 * unit_slot, *const bars = mbox + 8;
+    unsigned int *const mbox = ctl + lfr::kCtlMailbox + lfr::kCtlUnitWords * unit_slot, *const bars = mbox + lfr::kCtlUnitArrival;
     TeamCtx tm;
     tm.ctl = ctl;
     tm.epoch = a.team_epoch;
@@ -3043,17 +3045,17 @@ __global__ __launch_bounds__(kBlockThreads) __attribute__((amdgpu_waves_per_eu((
                 for (;;) {
                     const unsigned head = team_ld(a.queue + a.cls);
                     const int k = a.desc_begin + (int)head;
-                    if (k >= a.desc_end || team_ld(ctl + 9) != 0u) break;
+                    if (k >= a.desc_end || team_ld(ctl + lfr::kCtlAbort) != 0u) break;
                     const int ci = (int)a.wg_order[k - a.wg_begin];
                     const bool thin = reinterpret_cast<const uint32_t *>(a.workspace + a.ws_off[ci])[28] != 0u;
                     const int want = thin ? tree_team_size(a, ci) : 1;
                     // SOLO mode (the comment above TeamCtx: Residency): the team this component asks for cannot form - its leader alone
-                    const bool off_size = want > S && team_ld(ctl + 11) != 0u;
+                    const bool off_size = want > S && team_ld(ctl + lfr::kCtlSolo) != 0u;
                     if (want <= S || off_size) {
                         unsigned expect = head;
                         if (__hip_atomic_compare_exchange_strong(a.queue + a.cls, &expect, head + 1u, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) {
-                            atomicAdd(ctl + 12, 1u);               // somebody is at work (until the matching decrement below)
-                            if (off_size) atomicAdd(ctl + 13, 1u);
+                            atomicAdd(ctl + lfr::kCtlAtWork, 1u);               // somebody is at work (until the matching decrement below)
+                            if (off_size) atomicAdd(ctl + lfr::kCtlOffSize, 1u);
                             // (a plan that keeps the barrier schedule, or an off-size component: the leader alone - message 0 -, the team stays as it is)
                             msg = (thin && !off_size ? (unsigned)(32 - __builtin_clz((unsigned)want)) << 28 : 0u) | (unsigned)(ci + 1);
                             break;
@@ -3063,7 +3065,7 @@ __global__ __launch_bounds__(kBlockThreads) __attribute__((amdgpu_waves_per_eu((
                     __builtin_amdgcn_s_sleep(16);                  // too large for this team: a larger one will take it
                     if ((++spins & 255) == 0) {
                         watch.look(a, ctl);
-                        if ((spins >> 25) != 0) { atomicAdd(a.queue + 15, 1u); team_st(ctl + 9, 1u); break; }
+                        if ((spins >> 25) != 0) { atomicAdd(a.queue + lfr::kQueueSpinTimeouts, 1u); team_st(ctl + lfr::kCtlAbort, 1u); break; }
                     }
                 }
                 if (msg == kTeamMsgEnd || (msg >> 28) != 0u) {
@@ -3086,9 +3088,9 @@ __global__ __launch_bounds__(kBlockThreads) __attribute__((amdgpu_waves_per_eu((
                     msg = team_ld(mbox + rank);
                     if (msg != 0u) { team_st(mbox + rank, 0u); break; }
                     __builtin_amdgcn_s_sleep(8);
-                    if ((++spins & 255) == 0 && (team_ld(ctl + 9) != 0u || (spins >> 25) != 0)) {
-                        if (team_ld(ctl + 9) == 0u) atomicAdd(a.queue + 15, 1u);
-                        team_st(ctl + 9, 1u);
+                    if ((++spins & 255) == 0 && (team_ld(ctl + lfr::kCtlAbort) != 0u || (spins >> 25) != 0)) {
+                        if (team_ld(ctl + lfr::kCtlAbort) == 0u) atomicAdd(a.queue + lfr::kQueueSpinTimeouts, 1u);
+                        team_st(ctl + lfr::kCtlAbort, 1u);
                         msg = kTeamMsgEnd;
                         break;
                     }
@@ -3117,10 +3119,10 @@ __global__ __launch_bounds__(kBlockThreads) __attribute__((amdgpu_waves_per_eu((
         } else {
             tm.S = S; tm.r = rank - L; tm.bar = bars + L;
             tm.red = a.team_red + (size_t)unit_slot * kTeamRedPerUnit + (size_t)(L / 2) * (2 * kTeamMax * 16);
-            if (tid == 0 && tm.r == 0) atomicAdd(ctl + 10, 1u);           // (statistics: components solved by a team)
+            if (tid == 0 && tm.r == 0) atomicAdd(ctl + lfr::kCtlTeamRuns, 1u);           // (statistics: components solved by a team)
             solve_tree_component<kBlockThreads, true>(a, ci, sh, ts, tm);
         }
-        if (tid == 0 && rank == L) atomicSub(ctl + 12, 1u);              // (the workgroup that took the component from the queue)
+        if (tid == 0 && rank == L) atomicSub(ctl + lfr::kCtlAtWork, 1u);              // (the workgroup that took the component from the queue)
         __syncthreads();
     }
 }
@@ -3512,7 +3514,7 @@ int lfr_debug_solve_tree(int device, int64_t n_sys, const int64_t *blob_words, c
     uint64_t *d_off = ar.take_n<uint64_t>(4 * n_sys);
     CompDesc *d_descs = ar.take_n<CompDesc>(n_sys);
     int32_t *d_status = ar.take_n<int32_t>(n_sys);
-    unsigned int *d_queue = ar.take_n<unsigned int>(16);
+    unsigned int *d_queue = ar.take_n<unsigned int>(lfr::kQueueWords);
     if (!d_queue) { lfr::set_error("arena exhausted"); return LFR_ERR_NOMEM; }
     hipStream_t st = ctx->s_main;
     n_blob = 0;
@@ -3526,7 +3528,7 @@ int lfr_debug_solve_tree(int device, int64_t n_sys, const int64_t *blob_words, c
     HIP_TRY(hipMemcpyAsync(d_g, g, 8 * (size_t)n_vec, hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemsetAsync(d_descs, 0, sizeof(CompDesc) * (size_t)n_sys, st));
     HIP_TRY(hipMemsetAsync(d_status, 0, 4 * (size_t)n_sys, st));
-    HIP_TRY(hipMemsetAsync(d_queue, 0, 64, st));
+    HIP_TRY(hipMemsetAsync(d_queue, 0, lfr::kQueueWords * sizeof(unsigned int), st));
     KernelArgs a{};
     a.descs = d_descs; a.workspace = d_ws; a.ws_off = d_off; a.queue = d_queue; a.cls = lfr::KC_GLOBAL; a.desc_end = (int)n_sys;
     a.tukey_variant = LFR_TUKEY_CERES1;

@@ -11,6 +11,7 @@ tests/test_covariance_ref.py): all columns up to 400 rows, above that a sample o
 maxima of the bound taken over those columns only, which does not widen it.  Every node of every component is still checked for
 status, zeros and positivity."""
 import copy
+import dataclasses
 
 import numpy as np
 import pytest
@@ -400,3 +401,71 @@ def test_keypoint_covariances_on_a_solve(lfr_lib, small):
     for im, name in list(enumerate(g.image_names()))[:6]:
         out = g.keypoint_covariances(cov, name, nfeat)
         assert (out == CR.keypoint_covariances(cov, ni, nf, im, facts[im], nfeat)).all() and out.any()
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# 9. covariance and backward share one batch: independent of each other, of their order and of lfr_batch_set_inputs in between
+# ---------------------------------------------------------------------------------------------------------------------------
+# the "allclasses" graph of tests/test_gpu_set_inputs.py: tracks of 2..97 nodes, so every packed class and every LDS class holds components
+ALLCLASSES = dict(seed=20, n_images=100, n_tracks=80, len_dist="uniform", len_lo=2, len_hi=97, eps_out=0.0)
+
+
+def _bits(x):
+    return np.ascontiguousarray(x, np.float64).view(np.uint64)
+
+
+@pytest.mark.parametrize("kind", ["host", "fused"])
+def test_passes_crossed_on_one_batch_equal_each_alone(lfr_lib, kind):
+    """solve, covariance, backward, set_inputs, solve, backward, covariance on ONE batch; each of the four pass results must equal, bit
+    for bit, the same pass run alone on a fresh batch built from the same inputs (host-assembled, and device-assembled with the fused gather)."""
+    ma = synthetic.generate(**ALLCLASSES)
+    rng = np.random.default_rng(106)
+    lo, hi = min(ma.disp1.min(), ma.disp2.min()), max(ma.disp1.max(), ma.disp2.max())
+    d1, d2 = (np.clip(d + rng.normal(0.0, 0.02, size=d.shape).astype(np.float32), lo, hi).astype(np.float32) for d in (ma.disp1, ma.disp2))
+    mb = dataclasses.replace(ma, disp1=d1, disp2=d2)
+    alive = []
+
+    def fresh(m):
+        g = capi.Graph.from_arrays(m)
+        p = capi.Problem(g, device_graph_stage=0) if kind == "fused" else capi.Problem(g)
+        b = capi.Batch(p, 0)
+        b.solve()
+        alive.append((g, p, b))
+        return g, b
+
+    def cov(b):
+        return [b.covariance(f64=True).cpu().numpy(), b.covariance_status()]
+
+    def bwd(b):
+        return [t.cpu().numpy() for t in b.backward(gp, f64=True)] + [b.backward_status()]
+
+    def same(got, want, what):
+        for k, (x, y) in enumerate(zip(got[:-1], want[:-1])):
+            assert np.array_equal(_bits(x), _bits(y)), "%s/%s: result %d differs, max %.3g" % (kind, what, k, np.abs(x - y).max())
+        assert any(np.any(y != 0) for y in want[:-1]), what
+        assert np.array_equal(got[-1], want[-1]), "%s/%s: status" % (kind, what)
+
+    g, b = fresh(ma)
+    gp = torch.as_tensor(np.random.default_rng(8).standard_normal((g.n_nodes, 2)), device=DEV)
+    rows = 2 * b.component_info()["n_var_nodes"]
+    assert (rows <= 32).any() and ((rows > 32) & (rows <= 88)).any() and ((rows > 88) & (rows <= 130)).any() and (rows > 130).any()
+    want = {}
+    for tag, m in (("first", ma), ("second", mb)):             # every pass alone on a batch of its own
+        (_, bc), (_, bb) = fresh(m), fresh(m)
+        want[tag] = (bc.download().copy(), cov(bc), bwd(bb))
+        assert np.array_equal(_bits(bb.download()), _bits(want[tag][0]))
+    assert not np.array_equal(want["first"][0], want["second"][0])
+
+    assert np.array_equal(_bits(b.download()), _bits(want["first"][0]))
+    same(cov(b), want["first"][1], "covariance, first solve")
+    same(bwd(b), want["first"][2], "backward after covariance, first solve")
+    b.set_inputs(torch.as_tensor(d1.reshape(-1, 18)).to(DEV), torch.as_tensor(d2.reshape(-1, 18)).to(DEV))
+    for call in (lambda: b.backward(gp, f64=True), lambda: b.covariance(f64=True)):
+        with pytest.raises(capi.LfrError) as e:
+            call()
+        assert e.value.code == -1                              # LFR_ERR_ARG
+    b.solve()
+    assert np.array_equal(_bits(b.download()), _bits(want["second"][0]))
+    same(bwd(b), want["second"][2], "backward, second solve")
+    same(cov(b), want["second"][1], "covariance after backward, second solve")
+    assert b.spin_timeouts() == 0
