@@ -14,6 +14,7 @@ constexpr double kBound = 1.0;
 constexpr double kCauchyB = 0.25 * 0.25;
 constexpr double kCauchyC = 1.0 / (0.25 * 0.25);
 constexpr double kTukeyA2 = 0.0625 * 0.0625;
+constexpr double kSqrtHalf = 0.70710678118654752440, kLn2Hi = 6.93147180369123816490e-01, kLn2Lo = 1.90821492927058770002e-10;   // log_ge1
 constexpr int kMaxIterations = 100;
 constexpr int kMaxInvalid = 10;
 constexpr double kFunctionTol = 1e-4, kGradientTol = 1e-8, kParameterTol = 1e-4;
@@ -79,10 +80,24 @@ struct LogCoef {
         for (int i = 0; i < 11; ++i) { c[i] = 1.0 / (23.0 - 2.0 * i); asm volatile("" : "+v"(c[i])); }     // opaque: not rematerialised per use
     }
 };
-__device__ __forceinline__ double log_ge1(double x, const LogCoef *lc = nullptr) {
+// The other fp64 literals of a Cauchy evaluation, for callers with eight more VGPRs to spare: sqrt(1/2), the two pieces of ln 2 and the
+// loss's 1 / b.  gfx9 VOP3 takes no 64-bit literal, so each is an s_mov_b32 pair per use inside the slot loop otherwise.  The arithmetic
+// sees the same operand values in the same instructions: nothing is re-associated.
+// (A struct of its own on purpose: as four more members of LogCoef behind a flag, the members left unwritten where the flag is off keep
+// the compiler from splitting the struct, and all of it goes to scratch memory - <8,1,3> 3845 -> 4781 static instructions, scratch 11 -> 133.)
+struct CauchyConst {
+    double sqrt_half, ln2_hi, ln2_lo, inv_b;
+    __device__ __forceinline__ void load() {
+        sqrt_half = kSqrtHalf; ln2_hi = kLn2Hi; ln2_lo = kLn2Lo; inv_b = kCauchyC;
+        asm volatile("" : "+v"(sqrt_half), "+v"(ln2_hi), "+v"(ln2_lo), "+v"(inv_b));
+    }
+};
+__device__ __forceinline__ double log_ge1(double x, const LogCoef *lc = nullptr, const CauchyConst *kc = nullptr) {
+    // (values, not references to the constants: a conditional between two lvalues would be a select of addresses and put *kc in memory)
+    const double sqrt_half = kc ? kc->sqrt_half : +kSqrtHalf, ln2_hi = kc ? kc->ln2_hi : +kLn2Hi, ln2_lo = kc ? kc->ln2_lo : +kLn2Lo;
     int e = __builtin_amdgcn_frexp_exp(x);             // x = f * 2^e, f in [0.5, 1)
     double m = __builtin_amdgcn_frexp_mant(x);
-    if (m < 0.70710678118654752440) { m *= 2.0; --e; }
+    if (m < sqrt_half) { m *= 2.0; --e; }
     const double z = (m - 1.0) * fast_rcp(m + 1.0);
     const double w = z * z;
     double p;
@@ -102,7 +117,7 @@ __device__ __forceinline__ double log_ge1(double x, const LogCoef *lc = nullptr)
     }
     const double lm = fma(2.0 * z * w, p, 2.0 * z);    // log(m)
     const double ed = (double)e;
-    return fma(ed, 6.93147180369123816490e-01, fma(ed, 1.90821492927058770002e-10, lm));
+    return fma(ed, ln2_hi, fma(ed, ln2_lo, lm));
 }
 
 struct EdgeOut {
@@ -126,7 +141,7 @@ struct EdgeOut {
 template <bool WANT_JAC>
 __device__ __forceinline__ void eval_edge(const float (&flow)[18], float simf, int kind, int tukey_variant,
                                           double x1r, double x1c, double x2r, double x2c, EdgeOut &o, const bool at_zero = false,
-                                          const LogCoef *lc = nullptr) {
+                                          const LogCoef *lc = nullptr, const CauchyConst *kc = nullptr) {
     double f0 = 0., f1 = 0., dr0 = 0., dr1 = 0., dc0 = 0., dc1 = 0.;
     if (at_zero) {
         f0 = cvt_pinned(flow[8]); f1 = cvt_pinned(flow[9]);
@@ -172,8 +187,8 @@ __device__ __forceinline__ void eval_edge(const float (&flow)[18], float simf, i
     // Cauchy edges (intra-track, kind 0) take a path of their own when the whole wave has no other kind: a wave-uniform branch
     // instead of the exec-mask bracket of a divergent if / else around every evaluation
     auto cauchy = [&]() {                                         // CauchyLoss(0.25)
-        const double sum = 1.0 + s * kCauchyC;
-        rho0 = kCauchyB * log_ge1(sum, lc);
+        const double sum = 1.0 + s * (kc ? kc->inv_b : +kCauchyC);
+        rho0 = kCauchyB * log_ge1(sum, lc, kc);
         if (WANT_JAC) {
             // Corrector (rho'' <= 0 branch): sqrt(w rho') = sqrt(w / sum) = w rsqrt(w sum): one reciprocal square root instead of a
             // reciprocal and a square root.  Outside the positive normal range (w <= 0, a non-finite residual) the two-step form

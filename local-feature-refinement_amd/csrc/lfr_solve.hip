@@ -284,20 +284,18 @@ __device__ __forceinline__ void solve_group_body(const KernelArgs &a, const int 
     float flow[RES][18];
     float sim[RES];
     uint32_t idx[RES];          // src | (dst|kind<<15) << 16, decoded at every use (keeps 5 VGPRs/slot free)
+    // An absent slot (sl + S*k >= E) loads the group's first record (a valid address) and keeps whatever that gave: every use of a slot
+    // below is gated by sl + S*k < E, so nothing reads it.
 #pragma unroll
     for (int k = 0; k < RES; ++k) {
         const int e = sl + S * k;
-        const bool on = e < E;
-        load_packed_edge<FUSED>(a, d.edge_off + (on ? e : 0), flow[k], sim[k], idx[k]);
-        if (!on) {
-#pragma unroll
-            for (int i = 0; i < 18; ++i) flow[k][i] = 0.f;
-            sim[k] = 0.f; idx[k] = 0u;
-        }
+        load_packed_edge<FUSED>(a, d.edge_off + (e < E ? e : 0), flow[k], sim[k], idx[k]);
     }
     if (sl < NV) L.x[sl] = 0.0;
     if (sl < 2) L.x[NV + sl] = 0.0;
-    for (int i = sl; i < NV * LD; i += S) L.A[i] = 0.0;           // rows >= nv2 stay zero for the whole solve (the sweeps re-zero rows < nv2)
+    // rows >= nv2 stay zero for the whole solve (the sweeps re-zero rows < nv2; the first one finds them zero from here).  16-byte stores.
+    static_assert((NV * LD) % 2 == 0, "J^T J is cleared in pairs");
+    for (int i = sl; i < NV * LD / 2; i += S) reinterpret_cast<double2 *>(L.A)[i] = make_double2(0.0, 0.0);
 
     // ---- group state (uniform inside a group; 'row' values are identical in the LPR lanes of a row) ----
     int phase = have ? PH_EVAL_INIT : PH_DONE;
@@ -318,6 +316,11 @@ __device__ __forceinline__ void solve_group_body(const KernelArgs &a, const int 
     LogCoef logc;
     if constexpr (kLogRegs) logc.load();
     const LogCoef *lcp = kLogRegs ? &logc : nullptr;
+    // the Cauchy path's other four fp64 literals in 8 VGPRs: the 8-row class only (the 16-row class sits at 256 VGPRs and would spill 4)
+    constexpr bool kCauchyRegs = NV == 8 && LPR == 1;
+    CauchyConst cauchyc;
+    if constexpr (kCauchyRegs) cauchyc.load();
+    const CauchyConst *kcp = kCauchyRegs ? &cauchyc : nullptr;
     PROF_DECL
     PROF_MARK(0);                                     // 0: prologue (edge load)
     for (;;) {
@@ -391,8 +394,10 @@ __device__ __forceinline__ void solve_group_body(const KernelArgs &a, const int 
         const bool jac = !cost_only;                  // (cost_only is only ever set in PH_EVAL_LS)
         if (pe && jac) {
             // rows >= nv2 are never touched.  16-byte stores: as many LDS instructions went into this zeroing as into the atomics
+            // (the first sweep - at_zero, wave-uniform - finds J^T J as the prologue cleared it)
             double2 *A2 = reinterpret_cast<double2 *>(L.A);
-            for (int i = sl; i < (nv2 * LD + 1) / 2; i += S) A2[i] = make_double2(0.0, 0.0);
+            if (!at_zero)
+                for (int i = sl; i < (nv2 * LD + 1) / 2; i += S) A2[i] = make_double2(0.0, 0.0);
             if (sl < NV / 2) reinterpret_cast<double2 *>(L.g)[sl] = make_double2(0.0, 0.0);
 #ifdef LFR_ABL_ZERO            // the zeroing twice
             wave_lds_sync();
@@ -402,7 +407,8 @@ __device__ __forceinline__ void solve_group_body(const KernelArgs &a, const int 
         wave_lds_sync();
         PROF_MARK(6);                                 // 6: zero J^T J
         double cost_l = 0.0;
-        if (__any(pe && jac)) {
+        const bool full_sweep = __any(pe && jac);     // wave-uniform
+        if (full_sweep) {
             ISA_MARK("sweep_setup");
             // full sweep (a cost-only group riding in this wave evaluates in full too, but assembles nothing)
 #pragma unroll
@@ -422,13 +428,13 @@ __device__ __forceinline__ void solve_group_body(const KernelArgs &a, const int 
                 const int ra = es < n_var ? 2 * es : -1, rb = ed < n_var ? 2 * ed : -1;
                 EdgeOut o;
                 ISA_MARK("eval");
-                eval_edge<true>(flow_k, sim_k, ekind, tv, L.x[xa], L.x[xa + 1], L.x[xb], L.x[xb + 1], o, at_zero, lcp);
+                eval_edge<true>(flow_k, sim_k, ekind, tv, L.x[xa], L.x[xa + 1], L.x[xb], L.x[xb + 1], o, at_zero, lcp, kcp);
 #ifdef LFR_ABL_EVAL            // the evaluation twice (the second on opaque copies of the positions), results averaged (= unchanged)
                 {
                     double y0 = L.x[xa], y1 = L.x[xa + 1], y2 = L.x[xb], y3 = L.x[xb + 1];
                     asm volatile("" : "+v"(y0), "+v"(y1), "+v"(y2), "+v"(y3));
                     EdgeOut o2;
-                    eval_edge<true>(flow_k, sim_k, ekind, tv, y0, y1, y2, y3, o2, at_zero, lcp);
+                    eval_edge<true>(flow_k, sim_k, ekind, tv, y0, y1, y2, y3, o2, at_zero, lcp, kcp);
                     o.cost = 0.5 * (o.cost + o2.cost); o.r0 = 0.5 * (o.r0 + o2.r0); o.r1 = 0.5 * (o.r1 + o2.r1); o.sq = 0.5 * (o.sq + o2.sq);
                     o.j00 = 0.5 * (o.j00 + o2.j00); o.j01 = 0.5 * (o.j01 + o2.j01); o.j10 = 0.5 * (o.j10 + o2.j10); o.j11 = 0.5 * (o.j11 + o2.j11);
                 }
@@ -483,7 +489,7 @@ __device__ __forceinline__ void solve_group_body(const KernelArgs &a, const int 
                 EdgeOut o;
                 (void)ra; (void)rb;
                 ISA_MARK("eval_cost_only");
-                eval_edge<false>(flow_k, sim_k, ekind, tv, L.x[xa], L.x[xa + 1], L.x[xb], L.x[xb + 1], o, false, lcp);
+                eval_edge<false>(flow_k, sim_k, ekind, tv, L.x[xa], L.x[xa + 1], L.x[xb], L.x[xb + 1], o, false, lcp, kcp);
                 ISA_MARK("cost_only_loop");
                 cost_l += o.cost;
             }
@@ -497,8 +503,13 @@ __device__ __forceinline__ void solve_group_body(const KernelArgs &a, const int 
 #endif
         const double cost_e = group_sum<S>(cost_l);
         const double xe = (phase == PH_EVAL_INIT || phase == PH_REEVAL) ? xi : xt;     // row: the evaluated point
-        const double gnew = is_row ? L.g[row] : 0.0;
-        const double gmax_new = group_max<S>(is_row ? fabs(xe - clampb(xe - gnew)) : 0.0);
+        // After a cost-only sweep of the whole wave only the two "converged, candidate discarded" outcomes can follow, and neither reads the
+        // gradient: its LDS read and the projected-gradient butterfly belong to the full sweep.
+        double gnew = 0.0, gmax_new = 0.0;
+        if (full_sweep) {
+            gnew = is_row ? L.g[row] : 0.0;
+            gmax_new = group_max<S>(is_row ? fabs(xe - clampb(xe - gnew)) : 0.0);
+        }
         const double step_norm2 = L.step_norm2, xnorm2_new = L.xnorm2;     // of the trial point (group-uniform LDS reads)
 
         PROF_MARK(3);                                 // 3: post-sweep reductions

@@ -2,17 +2,21 @@
 phase boundaries, no GPU needed), walks the ISA of the kernel in textual order and counts the instructions of every phase by kind, per
 packed class.  The counts are STATIC (one pass over the unrolled code: every edge slot, every elimination step, every instantiation of
 the elimination once); next to the s_memtime phase profile (-DLFR_PROFILE_PHASES) they say what a phase's cycles are spent on.
-usage: python scripts/isa_account.py [kernel-substring] > profiles/r04_isa_account_packed_kernel.txt"""
+usage: python scripts/isa_account.py [kernel-substring [existing.s]] > profiles/r04_isa_account_packed_kernel.txt
+(an existing ISA file given as the second argument is read instead of compiling)"""
 import collections, os, re, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 C = os.path.join(ROOT, "local-feature-refinement_amd", "csrc")
 want = sys.argv[1] if len(sys.argv) > 1 else "solve_packed_kernelILb0E"
 out = "/tmp/lfr_solve_isa.s"
-subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-munsafe-fp-atomics", "-DLFR_ISA_MARKS", "-I", os.path.join(ROOT, "include"), "-I", C,
+if len(sys.argv) > 2: out = sys.argv[2]
+else: subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-munsafe-fp-atomics", "-DLFR_ISA_MARKS", "-I", os.path.join(ROOT, "include"), "-I", C,
                        "-S", "--cuda-device-only", os.path.join(C, "lfr_solve.hip"), "-o", out], stderr=subprocess.DEVNULL)
 lines = open(out).read().split("\n")
 start = [i for i, l in enumerate(lines) if re.match(r"^_Z\w*%s\w*:" % re.escape(want), l)][0]
-end = [i for i in range(start, len(lines)) if lines[i].strip().startswith("s_endpgm")][0]
+# the kernel has one s_endpgm per exit and the compiler lays blocks out in its own order (<16,1,6> sits behind the first exit): the
+# function ends at its .Lfunc_end label, not at the first s_endpgm
+end = [i for i in range(start, len(lines)) if lines[i].startswith(".Lfunc_end")][0]
 
 
 def kind(op):
