@@ -475,12 +475,6 @@ struct ArenaMark {                                 // temporaries: released at s
     explicit ArenaMark(DevArena &ar) : a(ar), m(ar.top) {}
     ~ArenaMark() { a.top = m; }
 };
-#define TAKE(ptr, T, count)                                                                                   \
-    T *ptr = arena.take_n<T>((size_t)(count));                                                                \
-    if (!ptr) { set_error("assembly: device arena exhausted (%s)", #ptr); return LFR_ERR_NOMEM; }
-#define TAKE_OUT(dst, T, count)                                                                               \
-    dst = slab.take_n<T>((size_t)(count));                                                                    \
-    if (!dst) { set_error("assembly: batch slab exhausted (%s)", #dst); return LFR_ERR_NOMEM; }
 
 template <class K, class V>
 int sort_pairs(DevArena &arena, const K *kin, K *kout, const V *vin, V *vout, int64_t n, int begin_bit, int end_bit, hipStream_t st) {
@@ -550,232 +544,344 @@ __global__ void k_fill_regions(FillRegions r) {
     }
 }
 
-int assemble_on_device(const Problem &p, const DevProblem &dp, int shard_rank, int shard_world, DevArena &slab, DeviceAssembly &out) {
-    const DevGraph &dg = *dp.graph;
-    DevCtx *ctx = dp.ctx;
-    hipStream_t st = ctx->s_main;
-    const int64_t N = dg.N, M = dg.M, E2 = 2 * M;
-    const int64_t C = p.stats.n_components, T = p.stats.n_tracks;
-    if (E2 >= ((int64_t)1 << 31) || N >= ((int64_t)1 << 31)) { set_error("graph too large for the device assembly"); return LFR_ERR_UNSUPPORTED; }
-    LFR_HIP_TRY(hipSetDevice(ctx->device));
+namespace {
 
-    DevArena arena;                                   // temporaries of this call
-    if (!arena.init(ctx, (size_t)96 * M + (size_t)52 * N + (size_t)128 * (C + 1) + ((size_t)32 << 20))) return LFR_ERR_NOMEM;
-    size_t pin_bytes = 0;
-    AsmSummary *h_sum = (AsmSummary *)ctx->pinned_acquire(sizeof(AsmSummary), &pin_bytes);
-    if (!h_sum) return LFR_ERR_NOMEM;
-    struct PinGuard { DevCtx *c; void *p; size_t b; ~PinGuard() { c->pinned_release(p, b); } } pin_guard{ctx, h_sum, pin_bytes};
+constexpr char kAsmArena[] = "assembly: device arena", kAsmSlab[] = "assembly: batch slab";
 
-    const uint32_t *node1 = dg.n1, *node2 = dg.n2;
-    const int32_t *track = dp.track, *comp = dp.comp;
-    const int node_bits = nbits((uint64_t)std::max<int64_t>(N - 1, 0)), comp_bits = nbits((uint64_t)C);
-
-    // ---- outputs (capacities are upper bounds: every edge kept, every node in a solved component) ----
-    TAKE_OUT(out.d_descs, CompDesc, C + 1); TAKE_OUT(out.d_edges, EdgeRec, E2);
-    TAKE_OUT(out.d_node_ids, uint32_t, N); TAKE_OUT(out.d_node_inc, NodeInc, N); TAKE_OUT(out.d_in_idx, uint32_t, E2);
-    TAKE_OUT(out.d_ws_off, uint64_t, C + 1); TAKE_OUT(out.d_es_off, uint64_t, C + 1);
-    TAKE_OUT(out.d_desc_class, uint32_t, C + 1); TAKE_OUT(out.d_desc_tracks, uint32_t, C + 1); TAKE_OUT(out.d_desc_component, uint32_t, C + 1);
-    const bool aligned8 = (((uintptr_t)dg.disp1 | (uintptr_t)dg.disp2) & 7u) == 0;
+struct AsmPlan {                                   // the decisions of one assembly, made once from what the host knows before the first launch
+    // the flow displacements are 8-byte aligned: k_emit_edges<true>
+    bool aligned8;
     // Fused gather: a whole batch over flows that live in HBM lets the packed kernel read its edges from the graph's own arrays
     // (72-byte flow rows, 8-byte aligned) - the 400 MB of records for config 4 are neither written nor re-read.  Shards gather zero-copy
     // from pinned host memory (once, into records); LFR_FUSED_GATHER=0 switches the path off.
     // Caller-owned device flows (lfr_graph_from_arrays_device_flows) are only promised to live until the batch exists (lfr.h): such a
     // batch gathers its records now and never looks at the caller's memory again.
-    bool fused = shard_world == 1 && !dg.flows_zero_copy && !dg.flows_external && aligned8 && dg.disp1 && dg.disp2;
-    if (const char *e = getenv("LFR_FUSED_GATHER")) fused = fused && e[0] != '0';
-    out.fused = fused;
-    if (fused) { TAKE_OUT(out.d_edge_ref, uint32_t, E2); TAKE_OUT(out.d_edge_word, uint32_t, E2); }
+    bool fused;
+    // the graph stage's largest component says whether a workgroup class can exist (packed classes take up to 16 variable nodes).
+    // A small component with > 320 edges - duplicated matches - still lands in one: the summary has the last word
+    // (redo_for_unexpected_workgroup_classes)
+    bool expect_workgroup_classes;
+    // packed classes only: the matches go through their sort before the counts, by component id, and the runs are the edge counts
+    // (k_match_keys_comp; the later orders: profiles/r06_ab/trace_c4_match_sort_*.txt)
+    bool match_sort_first;
+    // the record words of the fused gather came with the match-level order (k_place_matches): no k_edge_words pass
+    bool words_done;
+    // both directions of a match are kept or dropped together by construction - k_count_edges - and the sort is stable on the edge
+    // id, so the pair check only runs on request (LFR_CHECK_PAIRS) or on the path that materialises records
+    bool check_pairs;
+    // records are written now (fused and no workgroup class expected: nothing to write)
+    bool emit;
+    // A connected-component shard (dg.parent) carries the PARENT's upload events and chunk bounds, but its match indices are compacted:
+    // match m of the shard reads flow row flow_row[m] >= m, which can lie in a later chunk than chunk_row[] says for m (ADVICE r5).
+    // It waits for every chunk and emits in one pass.
+    bool shard;
+    // staged flows arrive in chunks on the copy stream: the records of a chunk's rows are emitted when it has landed
+    bool chunked;
 
-    // ---- which edges are kept, which nodes are variables, per-component sizes ----
+    AsmPlan(const Problem &p, const DevGraph &dg, int shard_world) {
+        aligned8 = (((uintptr_t)dg.disp1 | (uintptr_t)dg.disp2) & 7u) == 0;
+        fused = shard_world == 1 && !dg.flows_zero_copy && !dg.flows_external && aligned8 && dg.disp1 && dg.disp2;
+        if (const char *e = getenv("LFR_FUSED_GATHER")) fused = fused && e[0] != '0';
+        expect_workgroup_classes = p.stats.max_component_size > 17;
+        match_sort_first = !expect_workgroup_classes;
+        words_done = match_sort_first && fused;
+        check_pairs = !fused || getenv("LFR_CHECK_PAIRS");
+        emit = !fused || expect_workgroup_classes;
+        shard = (bool)dg.parent;
+        chunked = dg.flows_staged && !shard;
+    }
+};
+
+struct Assembly {
+    const Problem &p;
+    const DevProblem &dp;
+    const DevGraph &dg;
+    const int shard_rank, shard_world;
+    DevArena &slab;
+    DeviceAssembly &out;
+    DevCtx *const ctx;
+    const hipStream_t st;
+    const int64_t N, M, E2, C, T;
+    const AsmPlan plan;
+    const uint32_t *const node1, *const node2;
+    const int32_t *const track, *const comp;
+    const int node_bits, comp_bits;
+    DevArena arena;                                // temporaries of this call
+    AsmSummary *h_sum = nullptr;                   // pinned
+    size_t pin_bytes = 0;
+    // ---- temporaries that more than one pass touches ----
+    AsmSummary *sum = nullptr;
+    uint32_t *cn = nullptr, *cv = nullptr, *ce = nullptr, *ct = nullptr, *ts = nullptr, *dn = nullptr, *de = nullptr;      // per component / track counts
+    unsigned long long *ws_size = nullptr, *scan_state = nullptr, *key64s = nullptr;
+    size_t scan_words = 0;                         // look-back states of the four prefix sums (exclusive_sum_one_launch)
+    uint32_t *run_begin = nullptr, *run_end = nullptr;                                      // (k_match_runs)
+    uint32_t *node_begin = nullptr, *node_var_end = nullptr, *node_end = nullptr;           // (k_node_runs)
+    uint8_t *kept = nullptr, *is_var = nullptr;
+    int32_t *tc = nullptr, *di = nullptr;
+    uint32_t *nk1 = nullptr, *ni1 = nullptr, *local = nullptr;
+    uint64_t *ek0 = nullptr, *ek1 = nullptr;       // edge keys / ids of the edge order
+    uint32_t *ei0 = nullptr, *ei1 = nullptr;
+    uint32_t *mkey_sorted = nullptr, *match_sorted = nullptr;
+    uint32_t *perm = nullptr, *class_sorted = nullptr;     // perm[i] = component of desc i
+    uint32_t *no = nullptr, *eo = nullptr;
+    const uint32_t *total_edges_p = nullptr;
+    int class_shift = 0;
+
+    Assembly(const Problem &p_, const DevProblem &dp_, int rank, int world, DevArena &slab_, DeviceAssembly &out_)
+        : p(p_), dp(dp_), dg(*dp_.graph), shard_rank(rank), shard_world(world), slab(slab_), out(out_), ctx(dp_.ctx), st(dp_.ctx->s_main),
+          N(dg.N), M(dg.M), E2(2 * dg.M), C(p_.stats.n_components), T(p_.stats.n_tracks), plan(p_, dg, world),
+          node1(dg.n1), node2(dg.n2), track(dp_.track), comp(dp_.comp),
+          node_bits(nbits((uint64_t)std::max<int64_t>(dg.N - 1, 0))), comp_bits(nbits((uint64_t)p_.stats.n_components)) {}
+    Assembly(const Assembly &) = delete;
+    ~Assembly() { if (h_sum) ctx->pinned_release(h_sum, pin_bytes); }
+
+    int prepare();
+    int mark_and_count();
+    int batch_order();
+    int sizes_and_offsets();
+    int sort_edges_by_source();
+    int order_edges();
+    int build_incidence();
+    int wait_all_flow_chunks();
+    void emit_records(int64_t lo, int64_t hi, const uint32_t *skip_below_p);
+    int emit_landed_chunks();
+    int redo_for_unexpected_workgroup_classes();
+};
+
+// arena, pinned summary, and the outputs (capacities are upper bounds: every edge kept, every node in a solved component)
+int Assembly::prepare() {
+    if (!arena.init(ctx, (size_t)96 * M + (size_t)52 * N + (size_t)128 * (C + 1) + ((size_t)32 << 20))) return LFR_ERR_NOMEM;
+    h_sum = (AsmSummary *)ctx->pinned_acquire(sizeof(AsmSummary), &pin_bytes);
+    if (!h_sum) return LFR_ERR_NOMEM;
+    LFR_TAKE(slab, kAsmSlab, out.d_descs, CompDesc, C + 1); LFR_TAKE(slab, kAsmSlab, out.d_edges, EdgeRec, E2);
+    LFR_TAKE(slab, kAsmSlab, out.d_node_ids, uint32_t, N); LFR_TAKE(slab, kAsmSlab, out.d_node_inc, NodeInc, N); LFR_TAKE(slab, kAsmSlab, out.d_in_idx, uint32_t, E2);
+    LFR_TAKE(slab, kAsmSlab, out.d_ws_off, uint64_t, C + 1); LFR_TAKE(slab, kAsmSlab, out.d_es_off, uint64_t, C + 1);
+    LFR_TAKE(slab, kAsmSlab, out.d_desc_class, uint32_t, C + 1); LFR_TAKE(slab, kAsmSlab, out.d_desc_tracks, uint32_t, C + 1);
+    LFR_TAKE(slab, kAsmSlab, out.d_desc_component, uint32_t, C + 1);
+    out.fused = plan.fused;
+    if (plan.fused) { LFR_TAKE(slab, kAsmSlab, out.d_edge_ref, uint32_t, E2); LFR_TAKE(slab, kAsmSlab, out.d_edge_word, uint32_t, E2); }
+    return LFR_OK;
+}
+
+// ---- which edges are kept, which nodes are variables, per-component sizes ----
+int Assembly::mark_and_count() {
     // (everything that starts at zero sits in one block: one memset instead of a dozen)
     const size_t zero_mark = arena.top;
-    TAKE(sum, AsmSummary, 1);
-    TAKE(opt, uint8_t, N);
-    TAKE(cn, uint32_t, C + 1); TAKE(cv, uint32_t, C + 1); TAKE(ce, uint32_t, C + 1); TAKE(ct, uint32_t, C + 1);
-    TAKE(ts, uint32_t, T + 1); TAKE(dn, uint32_t, C + 1); TAKE(de, uint32_t, C + 1);
-    TAKE(ws_size, unsigned long long, C + 1);
-    TAKE(run_begin, uint32_t, C + 1); TAKE(run_end, uint32_t, C + 1);       // (k_match_runs)
-    TAKE(node_begin, uint32_t, C + 1); TAKE(node_var_end, uint32_t, C + 1); TAKE(node_end, uint32_t, C + 1);      // (k_node_runs)
-    const size_t scan_words = scan_state_words(C + 1);                      // look-back states of the four prefix sums below (exclusive_sum_one_launch)
-    TAKE(scan_state, unsigned long long, 4 * scan_words);
+    uint8_t *opt;
+    uint32_t *nk0, *ni0;
+    LFR_TAKE(arena, kAsmArena, sum, AsmSummary, 1);
+    LFR_TAKE(arena, kAsmArena, opt, uint8_t, N);
+    LFR_TAKE(arena, kAsmArena, cn, uint32_t, C + 1); LFR_TAKE(arena, kAsmArena, cv, uint32_t, C + 1); LFR_TAKE(arena, kAsmArena, ce, uint32_t, C + 1);
+    LFR_TAKE(arena, kAsmArena, ct, uint32_t, C + 1); LFR_TAKE(arena, kAsmArena, ts, uint32_t, T + 1); LFR_TAKE(arena, kAsmArena, dn, uint32_t, C + 1);
+    LFR_TAKE(arena, kAsmArena, de, uint32_t, C + 1);
+    LFR_TAKE(arena, kAsmArena, ws_size, unsigned long long, C + 1);
+    LFR_TAKE(arena, kAsmArena, run_begin, uint32_t, C + 1); LFR_TAKE(arena, kAsmArena, run_end, uint32_t, C + 1);
+    LFR_TAKE(arena, kAsmArena, node_begin, uint32_t, C + 1); LFR_TAKE(arena, kAsmArena, node_var_end, uint32_t, C + 1); LFR_TAKE(arena, kAsmArena, node_end, uint32_t, C + 1);
+    scan_words = scan_state_words(C + 1);
+    LFR_TAKE(arena, kAsmArena, scan_state, unsigned long long, 4 * scan_words);
     {   FillRegions fr; fr.add(arena.base + zero_mark, arena.top - zero_mark, 0); LFR_HIP_TRY(fill_regions(fr, st)); }
-    TAKE(kept, uint8_t, E2); TAKE(is_var, uint8_t, N); TAKE(tc, int32_t, T + 1);
-    TAKE(nk0, uint32_t, N); TAKE(nk1, uint32_t, N); TAKE(ni0, uint32_t, N); TAKE(ni1, uint32_t, N); TAKE(local, uint32_t, N);
-    // Packed classes only (the graph stage's largest component says that no workgroup class can exist): the matches go through their
-    // sort now, by component id, and the runs are the edge counts (k_match_keys_comp; the later orders: profiles/r06_ab/trace_c4_match_sort_*.txt).
-    TAKE(ek0, uint64_t, E2); TAKE(ek1, uint64_t, E2); TAKE(ei0, uint32_t, E2); TAKE(ei1, uint32_t, E2);      // edge keys / ids of the edge order below
-    if (fused) ei1 = out.d_edge_ref;                  // the sorted edge ids ARE the packed kernel's gather list
-    const bool expect_workgroup_classes = p.stats.max_component_size > 17;
-    const bool match_sort_first = !expect_workgroup_classes;
-    // The nodes go through THEIR sort before the counts as well - by (component, variables first): the runs are the components' node and
-    // variable counts (k_mark_var's two atomics per node on 147 k counters were half of its 54 us), a node's position in its run is its
-    // local index (the later sort, by the component's rank in the batch: profiles/r06_ab/trace_c4_nsl.txt).
-    uint32_t *mkey_sorted = nullptr, *match_sorted = nullptr;
+    LFR_TAKE(arena, kAsmArena, kept, uint8_t, E2); LFR_TAKE(arena, kAsmArena, is_var, uint8_t, N); LFR_TAKE(arena, kAsmArena, tc, int32_t, T + 1);
+    LFR_TAKE(arena, kAsmArena, nk0, uint32_t, N); LFR_TAKE(arena, kAsmArena, nk1, uint32_t, N); LFR_TAKE(arena, kAsmArena, ni0, uint32_t, N);
+    LFR_TAKE(arena, kAsmArena, ni1, uint32_t, N); LFR_TAKE(arena, kAsmArena, local, uint32_t, N);
+    LFR_TAKE(arena, kAsmArena, ek0, uint64_t, E2); LFR_TAKE(arena, kAsmArena, ek1, uint64_t, E2);
+    LFR_TAKE(arena, kAsmArena, ei0, uint32_t, E2); LFR_TAKE(arena, kAsmArena, ei1, uint32_t, E2);
+    if (plan.fused) ei1 = out.d_edge_ref;          // the sorted edge ids ARE the packed kernel's gather list
     // (keys and ids of the M matches: the four quarters of the first 64-bit edge-key buffer)
     uint32_t *mk0 = reinterpret_cast<uint32_t *>(ek0), *mk1 = mk0 + M, *mi0 = mk1 + M, *mi1 = mi0 + M;
     int rc;
     hipLaunchKernelGGL(k_mark_kept, grid_for(E2), dim3(kThreads), 0, st, M, node1, node2, track, comp, kept, opt, (uint32_t)C,
-                       match_sort_first ? mk0 : nullptr);
+                       plan.match_sort_first ? mk0 : nullptr);
     hipLaunchKernelGGL(k_mark_var, grid_for(N), dim3(kThreads), 0, st, N, opt, dp.is_root, track, comp, is_var, ts, tc, nk0, ni0);
+    // The nodes go through THEIR sort before the counts as well - by (component, variables first): the runs are the components' node and
+    // variable counts (k_mark_var's two atomics per node on 147 k counters were half of its 54 us), a node's position in its run is its
+    // local index (the later sort, by the component's rank in the batch: profiles/r06_ab/trace_c4_nsl.txt).
     if ((rc = sort_pairs(arena, nk0, nk1, ni0, ni1, N, 0, std::min(32, nbits((uint64_t)2 * C)), st)) != LFR_OK) return rc;
     hipLaunchKernelGGL(k_node_runs, grid_for(N), dim3(kThreads), 0, st, N, nk1, node_begin, node_var_end, node_end);
-    if (match_sort_first) {
+    if (plan.match_sort_first) {
         hipLaunchKernelGGL(k_match_keys_comp, grid_for(M), dim3(kThreads), 0, st, M, node1, node2, is_var, kept, (uint32_t)C, mk0, mi0);
         if ((rc = sort_pairs(arena, mk0, mk1, mi0, mi1, M, 0, comp_bits, st)) != LFR_OK) return rc;
         hipLaunchKernelGGL(k_match_runs, grid_for(M), dim3(kThreads), 0, st, M, mk1, (uint32_t)C, run_begin, run_end);
         mkey_sorted = mk1; match_sorted = mi1;
-    } else if (M > 256 * C) {                         // (see k_count_edges_by_node)
-        TAKE(ne, uint32_t, N);
+    } else if (M > 256 * C) {                      // (see k_count_edges_by_node)
+        uint32_t *ne;
+        LFR_TAKE(arena, kAsmArena, ne, uint32_t, N);
         LFR_HIP_TRY(hipMemsetAsync(ne, 0, 4 * (size_t)N, st));
         hipLaunchKernelGGL(k_count_edges_by_node, grid_for(M), dim3(kThreads), 0, st, M, node1, node2, is_var, kept, ne);
         hipLaunchKernelGGL(k_sum_node_edges, grid_for(N), dim3(kThreads), 0, st, N, comp, ne, ce);
     } else {
         hipLaunchKernelGGL(k_count_edges, grid_for(M), dim3(kThreads), 0, st, M, node1, node2, comp, is_var, kept, ce);
     }
+    return LFR_OK;
+}
 
-    // ---- batch order of the components: class, then edges descending, then variables descending, then id ----
-    TAKE(key64, unsigned long long, C + 1); TAKE(key64s, unsigned long long, C + 1);
-    TAKE(id0, uint32_t, C + 1); TAKE(id1, uint32_t, C + 1); TAKE(k0, uint32_t, C + 1); TAKE(k1, uint32_t, C + 1);
+// ---- batch order of the components: class, then edges descending, then variables descending, then id ----
+int Assembly::batch_order() {
+    unsigned long long *key64;
+    uint32_t *id0, *id1, *k0, *k1;
+    LFR_TAKE(arena, kAsmArena, key64, unsigned long long, C + 1); LFR_TAKE(arena, kAsmArena, key64s, unsigned long long, C + 1);
+    LFR_TAKE(arena, kAsmArena, id0, uint32_t, C + 1); LFR_TAKE(arena, kAsmArena, id1, uint32_t, C + 1);
+    LFR_TAKE(arena, kAsmArena, k0, uint32_t, C + 1); LFR_TAKE(arena, kAsmArena, k1, uint32_t, C + 1);
     // field widths of the key from what the host knows: a component's matches are matches of ONE connected component of the match graph
     // (dp.max_cc_matches, from the graph stage; 0 = unknown: 32 bits), its variables are nodes of the component (stats.max_component_size)
     uint32_t e_max = 0xffffffffu, v_max = 0xffffu;
     if (dp.max_cc_matches > 0 && dp.max_cc_matches < (1u << 30)) e_max = 2u * dp.max_cc_matches;
     if (dp.max_cc_matches > 0 && p.stats.max_component_size > 0 && p.stats.max_component_size < 0xffff) v_max = (uint32_t)p.stats.max_component_size;   // (the same stage counted both)
-    int e_bits = 1, v_bits = 1;
+    int e_bits = 1, v_bits = 1, rc;
     while (e_bits < 32 && (e_max >> e_bits) != 0u) ++e_bits;
     while (v_bits < 16 && (v_max >> v_bits) != 0u) ++v_bits;
-    const int class_shift = e_bits + v_bits;
-    hipLaunchKernelGGL(k_comp_keys, grid_for(std::max(C, T)), dim3(kThreads), 0, st, C, cn, cv, ce, match_sort_first ? run_begin : nullptr, run_end,
+    class_shift = e_bits + v_bits;
+    hipLaunchKernelGGL(k_comp_keys, grid_for(std::max(C, T)), dim3(kThreads), 0, st, C, cn, cv, ce, plan.match_sort_first ? run_begin : nullptr, run_end,
                        node_begin, node_var_end, node_end, key64, id0, &sum->too_big, (uint32_t)block_max_rows(),
                        T, ts, tc, ct, e_max, v_max, e_bits, v_bits);
     if ((rc = sort_pairs(arena, key64, key64s, id0, id1, C, 0, class_shift + kClassBits, st)) != LFR_OK) return rc;
-    uint32_t *perm = id1;                  // perm[i] = component of desc i
-    uint32_t *class_sorted = k1;
+    perm = id1;
+    class_sorted = k1;
     if (shard_world > 1) {                 // keep this shard's components (same relative order), the rest becomes class 7
         hipLaunchKernelGGL(k_class_of_key, grid_for(C), dim3(kThreads), 0, st, C, key64s, k1, class_shift);
         hipLaunchKernelGGL(k_shard_class, grid_for(C), dim3(kThreads), 0, st, C, class_sorted, shard_rank, shard_world, k0);
         if ((rc = sort_pairs(arena, k0, k1, id1, id0, C, 0, kClassBits, st)) != LFR_OK) return rc;
         perm = id0; class_sorted = k1;     // (k1 is rewritten by the sort after k_shard_class has read it: stream ordered)
     }
+    return LFR_OK;
+}
 
-    TAKE(no, uint32_t, C + 1); TAKE(eo, uint32_t, C + 1); TAKE(di, int32_t, C + 1);
+// ---- descriptor sizes, launch geometry + workspace offsets, local node numbering: nodes by (desc, variable first, node id) ----
+int Assembly::sizes_and_offsets() {
+    unsigned long long *es_size, *es_scan, *ws_scan;
+    LFR_TAKE(arena, kAsmArena, no, uint32_t, C + 1); LFR_TAKE(arena, kAsmArena, eo, uint32_t, C + 1); LFR_TAKE(arena, kAsmArena, di, int32_t, C + 1);
     hipLaunchKernelGGL(k_desc_sizes, grid_for(C), dim3(kThreads), 0, st, C, perm, class_sorted, shard_world > 1 ? nullptr : key64s, cn, ce, dn, de, di, class_shift);
     LFR_HIP_TRY(exclusive_sum_one_launch(dn, no, C + 1, scan_state + 0 * scan_words, st));
     LFR_HIP_TRY(exclusive_sum_one_launch(de, eo, C + 1, scan_state + 1 * scan_words, st));
-    const uint32_t *total_edges_p = eo + C;
-
-    // ---- launch geometry + workspace offsets ----
-    TAKE(es_size, unsigned long long, C + 1); TAKE(es_scan, unsigned long long, C + 1); TAKE(ws_scan, unsigned long long, C + 1);
+    total_edges_p = eo + C;
+    LFR_TAKE(arena, kAsmArena, es_size, unsigned long long, C + 1); LFR_TAKE(arena, kAsmArena, es_scan, unsigned long long, C + 1);
+    LFR_TAKE(arena, kAsmArena, ws_scan, unsigned long long, C + 1);
     hipLaunchKernelGGL(k_summary, grid_for(C + 1), dim3(kThreads), 0, st, C, class_sorted, perm, cv, ce, ct, sum, es_size);
     hipLaunchKernelGGL(k_ws_sizes, grid_for(C), dim3(kThreads), 0, st, C, class_sorted, perm, cv, sum, ws_size);
     LFR_HIP_TRY(exclusive_sum_one_launch(es_size, es_scan, C + 1, scan_state + 2 * scan_words, st));
     LFR_HIP_TRY(exclusive_sum_one_launch(ws_size, ws_scan, C + 1, scan_state + 3 * scan_words, st));
     hipLaunchKernelGGL(k_offsets, grid_for(C + 1), dim3(kThreads), 0, st, C, class_sorted, es_scan, ws_scan, no, eo, sum, out.d_es_off, out.d_ws_off);
-
-    // ---- local node numbering: nodes by (desc, variable first, node id) ----
     hipLaunchKernelGGL(k_place_nodes, grid_for(N), dim3(kThreads), 0, st, N, nk1, ni1, di, no, node_begin, out.d_node_ids, local);
+    return LFR_OK;
+}
 
-    // ---- edge order: kept edges by (desc, source node, edge id); packed classes by (desc, edge id) ----
-    // Packed classes carry zeros in the source-node bits (their order is component, then edge id - the sort is stable).  When the graph
-    // stage's largest component says that no workgroup class can exist, the match-level order above places every match.  A small
-    // component with > 320 edges still lands in a workgroup class: the summary below has the last word and the full sort is redone then.
-    const bool words_done = match_sort_first && fused;      // the record words came with the match-level order
-    if (match_sort_first) {                           // (sorted before the counts: every match to its component's place)
+// kept edges by (desc, source node, edge id): what a workgroup class needs.  Packed classes carry zeros in the source-node bits
+// (their order is component, then edge id - the sort is stable).
+int Assembly::sort_edges_by_source() {
+    hipLaunchKernelGGL(k_edge_keys, grid_for(E2), dim3(kThreads), 0, st, E2, node1, node2, comp, di, class_sorted, kept, node_bits,
+                       (uint64_t)C << node_bits, ek0, ei0);
+    return sort_pairs(arena, ek0, ek1, ei0, ei1, E2, 0, node_bits + comp_bits, st);
+}
+
+// ---- edge order; the pair check and the record words of the fused gather where they are still due ----
+int Assembly::order_edges() {
+    if (plan.match_sort_first) {                   // (sorted before the counts: every match to its component's place)
         hipLaunchKernelGGL(k_place_matches, grid_for(M), dim3(kThreads), 0, st, M, mkey_sorted, match_sorted, (uint32_t)C, di, eo, run_begin, node1, node2,
-                           local, ei1, fused ? out.d_edge_word : nullptr);
+                           local, ei1, plan.fused ? out.d_edge_word : nullptr);
     } else {
-        hipLaunchKernelGGL(k_edge_keys, grid_for(E2), dim3(kThreads), 0, st, E2, node1, node2, comp, di, class_sorted, kept, node_bits,
-                           (uint64_t)C << node_bits, ek0, ei0);
-        if ((rc = sort_pairs(arena, ek0, ek1, ei0, ei1, E2, 0, node_bits + comp_bits, st)) != LFR_OK) return rc;
+        const int rc = sort_edges_by_source();
+        if (rc != LFR_OK) return rc;
     }
-    // (both directions of a match are kept or dropped together by construction - k_count_edges - and the sort is stable on the edge
-    // id, so the pair check only runs on request or on the path that materialises records)
-    if (!fused || getenv("LFR_CHECK_PAIRS"))
+    if (plan.check_pairs)
         hipLaunchKernelGGL(k_check_pairs, grid_for(E2), dim3(kThreads), 0, st, E2, total_edges_p, ei1, node1, node2, comp, di, class_sorted, eo, &sum->unpaired);
-    if (fused && !words_done) hipLaunchKernelGGL(k_edge_words, grid_for(E2), dim3(kThreads), 0, st, E2, total_edges_p, ei1, node1, node2, track, local, out.d_edge_word);
+    if (plan.fused && !plan.words_done) hipLaunchKernelGGL(k_edge_words, grid_for(E2), dim3(kThreads), 0, st, E2, total_edges_p, ei1, node1, node2, track, local, out.d_edge_word);
+    return LFR_OK;
+}
 
-    // ---- descriptors + the device copies behind the lazily fetched host mirrors ----
-    hipLaunchKernelGGL(k_fill_descs, grid_for(C), dim3(kThreads), 0, st, C, class_sorted, perm, eo, no, cn, cv, ce, ct, out.d_descs, out.d_desc_tracks,
-                       out.d_desc_class, out.d_desc_component);
+// ---- incidence lists: workgroup classes only ----
+int Assembly::build_incidence() {
+    LFR_HIP_TRY(hipMemsetAsync(out.d_node_inc, 0, std::max<size_t>(sizeof(NodeInc) * (size_t)N, 16), st));
+    hipLaunchKernelGGL(k_incidence, grid_for(E2), dim3(kThreads), 0, st, E2, total_edges_p, ek1, node_bits, plan.fused ? out.d_edge_word : nullptr,
+                       ei1, node1, node2, class_sorted, eo, no, local, out.d_node_inc, ek0, ei0);      // (the unsorted key buffers are free again)
+    // (component << 16 | destination: 16 + comp_bits bits; the padding key's ones in that range exceed every real component index)
+    const int r = sort_pairs(arena, ek0, ek1, ei0, out.d_in_idx, E2, 0, 16 + comp_bits, st);
+    if (r != LFR_OK) return r;
+    hipLaunchKernelGGL(k_in_begin, grid_for(E2), dim3(kThreads), 0, st, E2, total_edges_p, ek1, eo, no, out.d_node_inc);
+    hipLaunchKernelGGL(k_inc_counts, grid_for(N), dim3(kThreads), 0, st, N, out.d_node_inc);
+    return LFR_OK;
+}
 
-    // ---- incidence lists: workgroup classes only.  The graph stage's largest component tells whether such a class can
-    // exist (packed classes take up to 16 variable nodes); when it says no, the lists are skipped and the summary
-    // below has the last word (a small component with > 320 edges - duplicated matches - still lands there).
-    auto build_incidence = [&]() -> int {
-        LFR_HIP_TRY(hipMemsetAsync(out.d_node_inc, 0, std::max<size_t>(sizeof(NodeInc) * (size_t)N, 16), st));
-        hipLaunchKernelGGL(k_incidence, grid_for(E2), dim3(kThreads), 0, st, E2, total_edges_p, ek1, node_bits, fused ? out.d_edge_word : nullptr,
-                           ei1, node1, node2, class_sorted, eo, no, local, out.d_node_inc, ek0, ei0);      // (the unsorted key buffers are free again)
-        // (component << 16 | destination: 16 + comp_bits bits; the padding key's ones in that range exceed every real component index)
-        const int r = sort_pairs(arena, ek0, ek1, ei0, out.d_in_idx, E2, 0, 16 + comp_bits, st);
-        if (r != LFR_OK) return r;
-        hipLaunchKernelGGL(k_in_begin, grid_for(E2), dim3(kThreads), 0, st, E2, total_edges_p, ek1, eo, no, out.d_node_inc);
-        hipLaunchKernelGGL(k_inc_counts, grid_for(N), dim3(kThreads), 0, st, N, out.d_node_inc);
-        return LFR_OK;
-    };
-    if (expect_workgroup_classes && (rc = build_incidence()) != LFR_OK) return rc;
-
-    // ---- records: gather the flows (their first consumer); staged flows arrive in chunks on the copy stream ----
-    // Every launch walks the whole edge list and keeps the edges of its rows, so chunks whose upload has already finished
-    // (all of them when the graph is resident) go out as ONE launch: four filtered passes were 40 % of the gather.
-    // A connected-component shard (dg.parent) carries the PARENT's upload events and chunk bounds, but its match indices are compacted:
-    // match m of the shard reads flow row flow_row[m] >= m, which can lie in a later chunk than chunk_row[] says for m (ADVICE r5).
-    // It waits for every chunk and emits in one pass.
-    const bool shard = (bool)dg.parent;
-    const bool chunked = dg.flows_staged && !shard;
-    const int n_chunks = chunked ? kFlowChunks : 1;
-    const bool emit = !fused || expect_workgroup_classes;          // (fused and no workgroup class expected: nothing to write; the summary has the last word)
-    if ((!emit || shard) && dg.flows_staged)                          // the solve reads the flows themselves / a shard gathers any row: every chunk must have landed
+int Assembly::wait_all_flow_chunks() {             // staged flows: every chunk's upload ordered before what follows on the stream
+    if (dg.flows_staged)
         for (int c = 0; c < kFlowChunks; ++c) if (dg.ev_flows[c]) LFR_HIP_TRY(hipStreamWaitEvent(st, dg.ev_flows[c], 0));
-    for (int c = 0; emit && c < n_chunks;) {
+    return LFR_OK;
+}
+
+// records of the edges whose flow rows lie in [lo, hi): one walk over the whole edge list (skip_below_p: see k_emit_edges, or null)
+void Assembly::emit_records(int64_t lo, int64_t hi, const uint32_t *skip_below_p) {
+    auto *kernel = plan.aligned8 ? k_emit_edges<true> : k_emit_edges<false>;
+    hipLaunchKernelGGL(kernel, grid_for(5 * E2), dim3(kThreads), 0, st, E2, total_edges_p, ei1, node1, node2,
+                       dg.sim, dg.disp1, dg.disp2, track, local, dg.flow_row, lo, hi, reinterpret_cast<uint4 *>(out.d_edges), skip_below_p, plan.fused ? out.d_edge_word : nullptr);
+}
+
+// ---- records: gather the flows (their first consumer); staged flows arrive in chunks on the copy stream ----
+// Every launch walks the whole edge list and keeps the edges of its rows, so chunks whose upload has already finished
+// (all of them when the graph is resident) go out as ONE launch: four filtered passes were 40 % of the gather.
+int Assembly::emit_landed_chunks() {
+    const int n_chunks = plan.chunked ? kFlowChunks : 1;
+    if (!plan.emit || plan.shard) {                // the solve reads the flows themselves / a shard gathers any row: every chunk must have landed
+        const int rc = wait_all_flow_chunks();
+        if (rc != LFR_OK) return rc;
+    }
+    auto landed = [&](int k) {
+        if (!dg.ev_flows[k]) return true;
+        const hipError_t q = hipEventQuery(dg.ev_flows[k]);
+        if (q != hipSuccess && q != hipErrorNotReady) (void)hipGetLastError();
+        return q == hipSuccess;
+    };
+    for (int c = 0; plan.emit && c < n_chunks;) {
         int c2 = c + 1;
-        if (chunked) {
-            auto landed = [&](int k) {
-                if (!dg.ev_flows[k]) return true;
-                const hipError_t q = hipEventQuery(dg.ev_flows[k]);
-                if (q != hipSuccess && q != hipErrorNotReady) (void)hipGetLastError();
-                return q == hipSuccess;
-            };
+        if (plan.chunked) {
             if (landed(c)) while (c2 < n_chunks && landed(c2)) ++c2;
             else if (dg.ev_flows[c]) LFR_HIP_TRY(hipStreamWaitEvent(st, dg.ev_flows[c], 0));
         }
-        const int64_t lo = chunked ? dg.chunk_row[c] : 0, hi = chunked ? dg.chunk_row[c2] : M;
-        if (hi > lo || (c == 0 && n_chunks == 1)) {
-            if (aligned8)
-                hipLaunchKernelGGL(k_emit_edges<true>, grid_for(5 * E2), dim3(kThreads), 0, st, E2, total_edges_p, ei1, node1, node2,
-                                   dg.sim, dg.disp1, dg.disp2, track, local, dg.flow_row, lo, hi, reinterpret_cast<uint4 *>(out.d_edges), fused ? &sum->packed_edges : nullptr, fused ? out.d_edge_word : nullptr);
-            else
-                hipLaunchKernelGGL(k_emit_edges<false>, grid_for(5 * E2), dim3(kThreads), 0, st, E2, total_edges_p, ei1, node1, node2,
-                                   dg.sim, dg.disp1, dg.disp2, track, local, dg.flow_row, lo, hi, reinterpret_cast<uint4 *>(out.d_edges), fused ? &sum->packed_edges : nullptr, fused ? out.d_edge_word : nullptr);
-        }
+        const int64_t lo = plan.chunked ? dg.chunk_row[c] : 0, hi = plan.chunked ? dg.chunk_row[c2] : M;
+        if (hi > lo || (c == 0 && n_chunks == 1)) emit_records(lo, hi, plan.fused ? &sum->packed_edges : nullptr);
         c = c2;
     }
     LFR_HIP_TRY(hipGetLastError());
+    return LFR_OK;
+}
+
+// The summary found workgroup classes that the graph stage's largest component did not announce: they need their edges by source
+// node - the 64-bit keys and the full sort (packed classes keep their order) -, the words again, the incidence lists, and the records
+// again, in the new order (fused: the unexpected workgroup classes' only).
+int Assembly::redo_for_unexpected_workgroup_classes() {
+    int rc;
+    if ((rc = sort_edges_by_source()) != LFR_OK) return rc;
+    if (plan.fused) hipLaunchKernelGGL(k_edge_words, grid_for(E2), dim3(kThreads), 0, st, E2, total_edges_p, ei1, node1, node2, track, local, out.d_edge_word);
+    if ((rc = build_incidence()) != LFR_OK) return rc;
+    // (a shard used to wait for its first chunk alone here; emit_landed_chunks has made the stream wait for all of a shard's already)
+    if ((rc = wait_all_flow_chunks()) != LFR_OK) return rc;
+    emit_records(0, M, &sum->packed_edges);
+    LFR_HIP_TRY(stream_wait(st));                  // the temporaries go back to the cache at return
+    return LFR_OK;
+}
+
+}  // namespace
+
+int assemble_on_device(const Problem &p, const DevProblem &dp, int shard_rank, int shard_world, DevArena &slab, DeviceAssembly &out) {
+    Assembly a(p, dp, shard_rank, shard_world, slab, out);
+    if (a.E2 >= ((int64_t)1 << 31) || a.N >= ((int64_t)1 << 31)) { set_error("graph too large for the device assembly"); return LFR_ERR_UNSUPPORTED; }
+    LFR_HIP_TRY(hipSetDevice(a.ctx->device));
+    int rc;
+    if ((rc = a.prepare()) != LFR_OK) return rc;
+    if ((rc = a.mark_and_count()) != LFR_OK) return rc;
+    if ((rc = a.batch_order()) != LFR_OK) return rc;
+    if ((rc = a.sizes_and_offsets()) != LFR_OK) return rc;
+    if ((rc = a.order_edges()) != LFR_OK) return rc;
+    // descriptors + the device copies behind the lazily fetched host mirrors
+    hipLaunchKernelGGL(k_fill_descs, grid_for(a.C), dim3(kThreads), 0, a.st, a.C, a.class_sorted, a.perm, a.eo, a.no, a.cn, a.cv, a.ce, a.ct, out.d_descs, out.d_desc_tracks,
+                       out.d_desc_class, out.d_desc_component);
+    if (a.plan.expect_workgroup_classes && (rc = a.build_incidence()) != LFR_OK) return rc;
+    if ((rc = a.emit_landed_chunks()) != LFR_OK) return rc;
 
     // the one read-back of the stage
-    LFR_HIP_TRY(hipMemcpyAsync(h_sum, sum, sizeof(AsmSummary), hipMemcpyDeviceToHost, st));
-    LFR_HIP_TRY(stream_wait(st));
-    out.summary = *h_sum;
+    LFR_HIP_TRY(hipMemcpyAsync(a.h_sum, a.sum, sizeof(AsmSummary), hipMemcpyDeviceToHost, a.st));
+    LFR_HIP_TRY(stream_wait(a.st));
+    out.summary = *a.h_sum;
     if (out.summary.too_big) { set_error("a component exceeds the 32767-node batch limit"); return LFR_ERR_UNSUPPORTED; }
     if (out.summary.unpaired) { set_error("internal: a kept edge without its opposite direction"); return LFR_ERR_UNSUPPORTED; }
-    if (!expect_workgroup_classes && out.summary.class_begin[KC_BLOCK] < out.summary.n_desc) {
-        // the unexpected workgroup classes need their edges by source node: the 64-bit keys and the full sort (packed classes keep their
-        // order), the words again
-        hipLaunchKernelGGL(k_edge_keys, grid_for(E2), dim3(kThreads), 0, st, E2, node1, node2, comp, di, class_sorted, kept, node_bits,
-                           (uint64_t)C << node_bits, ek0, ei0);
-        if ((rc = sort_pairs(arena, ek0, ek1, ei0, ei1, E2, 0, node_bits + comp_bits, st)) != LFR_OK) return rc;
-        if (fused) hipLaunchKernelGGL(k_edge_words, grid_for(E2), dim3(kThreads), 0, st, E2, total_edges_p, ei1, node1, node2, track, local, out.d_edge_word);
-        if ((rc = build_incidence()) != LFR_OK) return rc;
-        {                                         // the records again, in the new order (fused: the unexpected workgroup classes' only)
-            if (dg.flows_staged) for (int c = 0; c < n_chunks; ++c) if (dg.ev_flows[c]) LFR_HIP_TRY(hipStreamWaitEvent(st, dg.ev_flows[c], 0));
-            if (aligned8)
-                hipLaunchKernelGGL(k_emit_edges<true>, grid_for(5 * E2), dim3(kThreads), 0, st, E2, total_edges_p, ei1, node1, node2,
-                                   dg.sim, dg.disp1, dg.disp2, track, local, dg.flow_row, (int64_t)0, M, reinterpret_cast<uint4 *>(out.d_edges), &sum->packed_edges, fused ? out.d_edge_word : nullptr);
-            else
-                hipLaunchKernelGGL(k_emit_edges<false>, grid_for(5 * E2), dim3(kThreads), 0, st, E2, total_edges_p, ei1, node1, node2,
-                                   dg.sim, dg.disp1, dg.disp2, track, local, dg.flow_row, (int64_t)0, M, reinterpret_cast<uint4 *>(out.d_edges), &sum->packed_edges, fused ? out.d_edge_word : nullptr);
-        }
-        LFR_HIP_TRY(stream_wait(st));         // the temporaries go back to the cache at return
-    }
+    if (!a.plan.expect_workgroup_classes && out.summary.class_begin[KC_BLOCK] < out.summary.n_desc) return a.redo_for_unexpected_workgroup_classes();
     return LFR_OK;
 }
 

@@ -78,10 +78,6 @@ static inline void host_trace(const char *what) {
     fprintf(stderr, "lfr-host %10.1f us  %s\n", std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count(), what);
 }
 
-#define TAKE_B(dst, T, count)                                                                                 \
-    b->dst = b->slab.take_n<T>((size_t)(count));                                                              \
-    if (!b->dst) { lfr::set_error("batch slab exhausted (%s)", #dst); return LFR_ERR_NOMEM; }
-
 }  // namespace
 
 // host mirrors of a device-assembled batch (descriptors, component ids, classes, node ids): 2-6 MB, fetched once
@@ -236,9 +232,9 @@ int create_on_device(lfr_batch *b, const lfr::Problem &p, int shard_rank, int sh
     const size_t fixed = sizeof(double) * 2 * (size_t)std::max<int64_t>(N, 1) + sizeof(CompInfoDev) * (size_t)(C + 1) +
                          kProfWords * sizeof(unsigned long long) + ((size_t)1 << 16);
     if (!b->slab.init(b->ctx, lfr::assembly_output_bytes(N, M, C) + fixed)) return LFR_ERR_NOMEM;
-    TAKE_B(d_positions, double, 2 * std::max<int64_t>(N, 1));
-    TAKE_B(d_infos, CompInfoDev, C + 1);
-    TAKE_B(d_prof, unsigned long long, kProfWords);
+    LFR_TAKE(b->slab, "batch slab", b->d_positions, double, 2 * std::max<int64_t>(N, 1));
+    LFR_TAKE(b->slab, "batch slab", b->d_infos, CompInfoDev, C + 1);
+    LFR_TAKE(b->slab, "batch slab", b->d_prof, unsigned long long, kProfWords);
     // Roots, constants and nodes outside every solved component stay at 0 for the life of the batch
     // (solve.cc:609-612); the kernels overwrite every variable on every solve, so no per-solve memset.
     HIP_TRY(hipMemsetAsync(b->d_positions, 0, sizeof(double) * 2 * (size_t)std::max<int64_t>(N, 1), st));
@@ -319,10 +315,12 @@ int create_from_host(lfr_batch *b, const lfr::Problem &p, int shard_rank, int sh
     const size_t bytes = nd * (sizeof(CompDesc) + sizeof(CompInfoDev) + 16) + ne * (sizeof(EdgeRec) + 4) + nn * (4 + sizeof(lfr::NodeInc)) +
                          npos * sizeof(double) + kProfWords * sizeof(unsigned long long) + ((size_t)1 << 16);
     if (!b->slab.init(b->ctx, bytes)) return LFR_ERR_NOMEM;
-    TAKE_B(d_descs, CompDesc, nd); TAKE_B(d_edges, EdgeRec, ne); TAKE_B(d_node_ids, uint32_t, nn);
-    TAKE_B(d_node_inc, lfr::NodeInc, nn); TAKE_B(d_in_idx, uint32_t, ne);
-    TAKE_B(d_positions, double, npos); TAKE_B(d_infos, CompInfoDev, nd);
-    TAKE_B(d_ws_off, uint64_t, nd); TAKE_B(d_es_off, uint64_t, nd); TAKE_B(d_prof, unsigned long long, kProfWords);
+    LFR_TAKE(b->slab, "batch slab", b->d_descs, CompDesc, nd); LFR_TAKE(b->slab, "batch slab", b->d_edges, EdgeRec, ne);
+    LFR_TAKE(b->slab, "batch slab", b->d_node_ids, uint32_t, nn);
+    LFR_TAKE(b->slab, "batch slab", b->d_node_inc, lfr::NodeInc, nn); LFR_TAKE(b->slab, "batch slab", b->d_in_idx, uint32_t, ne);
+    LFR_TAKE(b->slab, "batch slab", b->d_positions, double, npos); LFR_TAKE(b->slab, "batch slab", b->d_infos, CompInfoDev, nd);
+    LFR_TAKE(b->slab, "batch slab", b->d_ws_off, uint64_t, nd); LFR_TAKE(b->slab, "batch slab", b->d_es_off, uint64_t, nd);
+    LFR_TAKE(b->slab, "batch slab", b->d_prof, unsigned long long, kProfWords);
     HIP_TRY(hipMemsetAsync(b->d_positions, 0, npos * sizeof(double), st));        // solve.cc:609-612, see create_on_device
     HIP_TRY(hipMemsetAsync(b->d_prof, 0, kProfWords * sizeof(unsigned long long), st));
     if (!b->descs.empty()) {

@@ -125,5 +125,12 @@ struct DevArena {
     }
     template <class T> T *take_n(size_t n) { return (T *)take((n ? n : 1) * sizeof(T)); }
 };
+// The checked take: dst = `count` elements of T from `arena`; an arena without the room leaves the calling function with
+// LFR_ERR_NOMEM and the error "<what> exhausted (<dst>)" (what: which arena or slab, e.g. "graph stage: device arena").
+#define LFR_TAKE(arena, what, dst, T, count)                                                                  \
+    do {                                                                                                      \
+        (dst) = (arena).template take_n<T>((size_t)(count));                                                  \
+        if (!(dst)) { ::lfr::set_error("%s exhausted (%s)", what, #dst); return LFR_ERR_NOMEM; }              \
+    } while (0)
 
 }  // namespace lfr

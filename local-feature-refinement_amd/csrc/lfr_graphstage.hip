@@ -26,7 +26,7 @@
 // by its upper bound (N or M).  One 64-byte read-back at the end delivers the counts for the stdout lines
 // (a second one, mid-way, tells whether large connected components exist and whether a long tie asks for the three sorts).  A component above the size cap
 // needs the graph cut: the sequential priority-queue bisection stays on the host, fed with the device's tracks
-// (lfr_graph.cpp: components_from_tracks), and the labels go back to HBM.
+// (lfr_graph.cpp: cut_components_from_pairs, the same recursive_cut as the host stage's components_from_tracks), and the labels go back to HBM.
 // Integer work throughout; the only floating-point accumulation (root scores, sums of float32
 // similarities in fp64) is exact for any realistic input, hence order independent.
 #include <hip/hip_runtime.h>
@@ -59,9 +59,6 @@ struct ArenaMark {                                 // temporaries: released at s
     explicit ArenaMark(DevArena &ar) : a(ar), m(ar.top) {}
     ~ArenaMark() { a.top = m; }
 };
-#define TAKE(ptr, T, count)                                                                                   \
-    T *ptr = arena.take_n<T>((size_t)(count));                                                                \
-    if (!ptr) { set_error("graph stage: device arena exhausted (%s)", #ptr); return LFR_ERR_NOMEM; }
 
 template <class K, class V>
 int sort_pairs(DevArena &arena, const K *kin, K *kout, const V *vin, V *vout, int64_t n, int begin_bit, int end_bit, hipStream_t st) {
@@ -256,8 +253,10 @@ __global__ void k_seg_flags_hi(int64_t M, const uint64_t *keys, uint32_t *flags)
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < M) flags[i] = (i == 0 || (keys[i] >> 32) != (keys[i - 1] >> 32)) ? 1u : 0u;
 }
-// counts[] layout (device): what the host reads back at the end of the stage
-enum { CNT_SEG = 0, CNT_TRACKS, CNT_COMPS, CNT_MAX_TRACK, CNT_MAX_COMP, CNT_MAX_SEG, CNT_LONG_TIE, CNT_WORDS = 16 };
+// counts[] layout (device): what the host reads back at the end of the stage.  The host's pinned copy is longer and has two more uses
+// between read-backs: the cut's two counters in words no kernel writes, and the counters of a batch of union-find rounds behind the block.
+enum { CNT_SEG = 0, CNT_TRACKS, CNT_COMPS, CNT_MAX_TRACK, CNT_MAX_COMP, CNT_MAX_SEG, CNT_LONG_TIE, CNT_WORDS = 16,
+       CNT_HOST_CUT_EDGES = 8, CNT_HOST_CUT_PAIRS = 9, CNT_HOST_ROUNDS = CNT_WORDS, CNT_HOST_WORDS = CNT_WORDS + 16 };
 // Runs of equal (component, similarity) in the one-sort order: the reference's order inside a run is descending (n1, n2) (solve.cc:489,
 // std::sort + reverse of (sim, n1, n2) tuples; equal triples are the same union whichever comes first - match id ascending, as the
 // stable three-sort scheme leaves them).  The head of a run sorts it by insertion; a run above max_run (quantized similarities in a
@@ -1028,437 +1027,525 @@ static int shard_dev_graph(const std::shared_ptr<DevGraph> &full, int rank, int 
     return LFR_OK;
 }
 
-int graph_stage_on_device(const Graph &g, int64_t max_nodes, int device, bool stage_flows, Problem &p, int shard_rank, int shard_world) {
-    const int64_t N = g.n_nodes();
-    int64_t M = g.n_matches();
-    const char *vb = getenv("LFR_VERBOSE");
-    const int trace = vb ? atoi(vb) >= 2 ? atoi(vb) : 0 : 0;      // LFR_VERBOSE=2: lap times, 3: + every round of the parallel greedy
-    const auto tr0 = std::chrono::steady_clock::now();
-    auto lap = [&](const char *what) {
-        if (trace) fprintf(stderr, "lfr graph stage: %8.3f ms  %s\n", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tr0).count(), what);
+namespace {
+
+// =================================================================================================
+// the stage: its knobs, its state, and the passes of graph_stage_on_device in the order they run
+// =================================================================================================
+struct StageKnobs {                                // every environment knob of the stage; read per call (the tests change them between calls)
+    bool say_hand_back = false;                    // LFR_VERBOSE or LFR_TIMING set: a hand-back to the host stage says why
+    int trace = 0;                                 // LFR_VERBOSE=2: lap times, 3: + every round of the parallel greedy
+    int max_tie_run = kMaxTieRun;                  // LFR_MAX_TIE_RUN (tests: 0 = always the three sorts)
+    bool one_sort_order = false;                   // LFR_ONE_SORT_ORDER: skip the counting road
+    int64_t serial_limit = kSerialSegmentEdges;    // LFR_SERIAL_SEGMENT_EDGES
+    int64_t rounds_first_block = 0;                // LFR_ROUNDS_FIRST_BLOCK (0: the default, 2 N positions)
+    const char *debug_dump = nullptr;              // LFR_DEBUG_DUMP: folder for the intermediates of the stage as raw files
+    static StageKnobs read() {
+        StageKnobs k;
+        const char *vb = getenv("LFR_VERBOSE");
+        k.say_hand_back = vb || getenv("LFR_TIMING");
+        k.trace = vb ? atoi(vb) >= 2 ? atoi(vb) : 0 : 0;
+        if (const char *e = getenv("LFR_MAX_TIE_RUN")) k.max_tie_run = std::max(0, atoi(e));
+        k.one_sort_order = getenv("LFR_ONE_SORT_ORDER") != nullptr;
+        if (const char *e = getenv("LFR_SERIAL_SEGMENT_EDGES")) k.serial_limit = std::max<int64_t>(0, atoll(e));
+        if (const char *e = getenv("LFR_ROUNDS_FIRST_BLOCK")) k.rounds_first_block = std::max<int64_t>(1, atoll(e));
+        k.debug_dump = getenv("LFR_DEBUG_DUMP");
+        return k;
+    }
+};
+
+// how the matches of a connected component got into the reference's order (step 2)
+enum class MatchOrder {
+    counted_streamed,                              // grouped by component, ranked by counting: sorted records (srec), no ties to repair
+    one_sort_tie_repair,                           // one sort over (component | ~similarity) + k_tie_fix
+    three_sorts                                    // the exact order of round 3: by n2, by (similarity, n1), by component
+};
+
+struct Stage {
+    // ---- the call: dimensions, stream, arena, pinned counters, events ----
+    const Graph &g;
+    Problem &p;
+    const int device;
+    const StageKnobs knobs = StageKnobs::read();
+    const std::chrono::steady_clock::time_point tr0 = std::chrono::steady_clock::now();
+    int64_t N, M, max_nodes = 0, seg_cap = 0;      // seg_cap: a segment has >= 1 match and >= 2 nodes
+    int node_bits = 1;
+    lfr_problem_stats stats{};                     // -> p.stats in publish()
+    std::shared_ptr<DevGraph> dg;
+    std::shared_ptr<DevProblem> dp;
+    DevCtx *ctx = nullptr;
+    hipStream_t st = nullptr;
+    const uint32_t *n1 = nullptr, *n2 = nullptr;
+    const float *sim = nullptr;
+    DevArena arena;                                // temporaries of this call
+    uint32_t *h_counts = nullptr;                  // pinned: CNT_HOST_WORDS words
+    size_t pin_bytes = 0;
+    enum { EV_FILLED, EV_TRACKS, EV_ROOTS, EV_COMPS, EV_BEGIN, EV_CUT_BEGIN, EV_CUT_END, EV_COUNT };
+    hipEvent_t ev[EV_COUNT] = {};                  // (EV_BEGIN: only under LFR_VERBOSE>=2; the cut's pair: only when it runs)
+    // ---- device arrays, by what they are ----
+    uint32_t *counts = nullptr;                    // CNT_WORDS, first in the zero block
+    size_t zero_bytes = 0, scan_words_m = 0, scan_words_n = 0;
+    unsigned long long *scan_state = nullptr;      // look-back states of the three one-launch prefix sums: segments, tracks, components
+    struct { uint32_t *parent = nullptr, *label = nullptr; } cc;                           // connected components of the match graph
+    struct {                                       // order and segments
+        uint4 *rec = nullptr, *srec = nullptr;     // counting road: the records, and the records in the reference's order
+        uint64_t *khi = nullptr, *khi2 = nullptr;  // (the 64-bit keys of the sorting roads share rec's 16 M bytes)
+        uint32_t *klo = nullptr, *klo2 = nullptr, *id0 = nullptr, *id1 = nullptr, *ck0 = nullptr, *ck1 = nullptr;
+        uint32_t *flags = nullptr, *segid = nullptr, *starts = nullptr, *order = nullptr;
+    } ord;
+    struct { int32_t *par = nullptr, *next = nullptr, *tail = nullptr, *cnt = nullptr; ulonglong2 *sig = nullptr; } uf;     // constrained union-find
+    struct {                                       // tracks and roots
+        uint32_t *rflag = nullptr, *rrank = nullptr, *tsize = nullptr;
+        double *score = nullptr; unsigned long long *best = nullptr; int32_t *bnode = nullptr;
+    } trk;
+    struct {                                       // component labelling (mp_parent: smallest track per connected component, starts at ~0)
+        uint32_t *mp_parent = nullptr, *mp = nullptr, *cflag = nullptr, *crank = nullptr, *csize = nullptr;
+        int32_t *gc = nullptr;                     // after a cut: subset of every track inside its component
+    } lab;
+
+    Stage(const Graph &g_, Problem &p_, int device_) : g(g_), p(p_), device(device_), N(g_.n_nodes()), M(g_.n_matches()) {}
+    Stage(const Stage &) = delete;
+    ~Stage() {
+        for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
+        if (h_counts) ctx->pinned_release(h_counts, pin_bytes);
+    }
+    void lap(const char *what) const {
+        if (knobs.trace) fprintf(stderr, "lfr graph stage: %8.3f ms  %s\n", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tr0).count(), what);
+    }
+    // (every hand-back to the host graph stage says why under LFR_VERBOSE / LFR_TIMING: results are the same, the time is not - ADVICE r4)
+    int use_host(const char *why) const {
+        if (knobs.say_hand_back) fprintf(stderr, "lfr graph stage: handed back to the host (%s)\n", why);
+        return LFR_GRAPHSTAGE_USE_HOST;
+    }
+    bool has_large_components() const { return (int64_t)h_counts[CNT_MAX_SEG] > knobs.serial_limit; }
+
+    int shard_if_balanced(int shard_rank, int shard_world);
+    int prepare();
+    int connected_components();
+    int three_sorts();
+    int segments(bool states_fresh);
+    int order_matches(MatchOrder &kind);
+    int union_find_small(MatchOrder kind);
+    int union_find_rounds();
+    int tracks_and_roots(MatchOrder kind);
+    int label_components(bool after_cut);
+    int read_counts(const char *what);
+    void trace_fill_time() const;
+    void debug_dump() const;
+    int cut_oversized();
+    int publish();
+};
+constexpr char kStageArena[] = "graph stage: device arena";
+
+int Stage::shard_if_balanced(int shard_rank, int shard_world) {
+    p.cc_sharded = false;
+    if (!(shard_world > 1 && shard_world <= 64 && M > 0)) return LFR_OK;
+    std::shared_ptr<DevGraph> dgs;
+    std::vector<unsigned long long> per_rank;
+    const int rc = shard_dev_graph(dg, shard_rank, shard_world, dgs, per_rank);
+    if (rc != LFR_OK) return rc;
+    unsigned long long mx = 0;
+    for (int r = 0; r < shard_world; ++r) mx = std::max(mx, per_rank[r]);
+    // balanced enough (every rank decides the same from the same counts): the largest rank within 5/4 of the mean
+    if (4ull * mx * (unsigned long long)shard_world <= 5ull * (unsigned long long)M + 4096ull * shard_world) {
+        dg = dgs; M = dg->M;
+        p.cc_sharded = true; p.shard_matches = M; p.shard_matches_max = (int64_t)mx;
+    }
+    lap(p.cc_sharded ? "sharded by connected component" : "one connected component dominates: the whole graph on every rank");
+    return LFR_OK;
+}
+
+// slabs, pinned block, events, and everything that starts at zero in one block: one fill instead of a dozen memsets
+int Stage::prepare() {
+    dp.reset(new DevProblem());
+    dp->ctx = ctx; dp->graph = dg; dp->N = N;
+    if (!dp->slab.init(ctx, (size_t)9 * N + 4096)) return LFR_ERR_NOMEM;
+    dp->track = dp->slab.take_n<int32_t>(N); dp->comp = dp->slab.take_n<int32_t>(N); dp->is_root = dp->slab.take_n<uint8_t>(N);
+    if (!arena.init(ctx, (size_t)112 * M + (size_t)112 * N + ((size_t)32 << 20))) return LFR_ERR_NOMEM;
+    h_counts = (uint32_t *)ctx->pinned_acquire(4 * CNT_HOST_WORDS, &pin_bytes);
+    if (!h_counts) return LFR_ERR_NOMEM;
+    for (int i = EV_FILLED; i <= EV_COMPS; ++i) LFR_HIP_TRY(hipEventCreate(&ev[i]));
+    lap("slabs, pinned block, events");
+
+    n1 = dg->n1; n2 = dg->n2; sim = dg->sim;
+    while (((int64_t)1 << node_bits) < N) ++node_bits;
+    seg_cap = std::min(N, M) + 1;
+    if (knobs.trace) { LFR_HIP_TRY(hipEventCreate(&ev[EV_BEGIN])); LFR_HIP_TRY(hipEventRecord(ev[EV_BEGIN], st)); }
+    const size_t zero_mark = arena.top;
+    LFR_TAKE(arena, kStageArena, counts, uint32_t, CNT_WORDS);
+    LFR_TAKE(arena, kStageArena, ord.flags, uint32_t, M + 1); LFR_TAKE(arena, kStageArena, trk.rflag, uint32_t, N + 1);
+    LFR_TAKE(arena, kStageArena, trk.tsize, uint32_t, N); LFR_TAKE(arena, kStageArena, trk.score, double, N);
+    LFR_TAKE(arena, kStageArena, trk.best, unsigned long long, N);
+    LFR_TAKE(arena, kStageArena, lab.cflag, uint32_t, N + 1); LFR_TAKE(arena, kStageArena, lab.csize, uint32_t, N);
+    // look-back states of the stage's prefix sums (exclusive_sum_one_launch: no init launch for states that start in the zero block)
+    scan_words_m = scan_state_words(M + 1); scan_words_n = scan_state_words(N + 1);
+    LFR_TAKE(arena, kStageArena, scan_state, unsigned long long, scan_words_m + 2 * scan_words_n);
+    zero_bytes = arena.top - zero_mark;
+    LFR_TAKE(arena, kStageArena, trk.bnode, int32_t, N); LFR_TAKE(arena, kStageArena, lab.mp_parent, uint32_t, N);      // (next to each other: one region of -1 / of "no track yet")
+    // the stage's initial values in one launch (the memsets were 5 launches before the first kernel, 2 more before the meta-components)
+    FillRegions fr;
+    fr.add(arena.base + zero_mark, zero_bytes, 0);
+    fr.add(dp->is_root, (size_t)N, 0);
+    fr.add(trk.bnode, (size_t)(reinterpret_cast<char *>(lab.mp_parent + N) - reinterpret_cast<char *>(trk.bnode)), 0xff);
+    LFR_HIP_TRY(fill_regions(fr, st));
+    LFR_HIP_TRY(hipEventRecord(ev[EV_FILLED], st));
+    return LFR_OK;
+}
+
+// 1. connected components of the match graph (conflicts ignored)
+int Stage::connected_components() {
+    LFR_TAKE(arena, kStageArena, cc.parent, uint32_t, N); LFR_TAKE(arena, kStageArena, cc.label, uint32_t, N);
+    hipLaunchKernelGGL(k_iota, grid_for(N), dim3(kThreads), 0, st, N, cc.parent);
+    for (int i = 0, done = 0; i < kUnionStages; done = kUnionStrides[i], ++i) {
+        if (i) hipLaunchKernelGGL(k_uf_flatten, grid_for(N), dim3(kThreads), 0, st, N, cc.parent);
+        hipLaunchKernelGGL(k_cc_union, grid_for((M + kUnionStrides[i] - 1) / kUnionStrides[i]), dim3(kThreads), 0, st, M, kUnionStrides[i], done, n1, n2, cc.parent);
+    }
+    hipLaunchKernelGGL(k_cc_labels, grid_for(N), dim3(kThreads), 0, st, N, cc.parent, cc.label);
+    return LFR_OK;
+}
+
+int Stage::three_sorts() {                         // -> ord.order (= id1)
+    int r;
+    hipLaunchKernelGGL(k_match_keys, grid_for(M), dim3(kThreads), 0, st, M, (uint32_t)(N - 1), node_bits, n1, n2, sim, ord.khi, ord.klo, ord.id0);
+    if ((r = sort_pairs(arena, ord.klo, ord.klo2, ord.id0, ord.id1, M, 0, node_bits, st)) != LFR_OK) return r;
+    hipLaunchKernelGGL(k_gather_u64, grid_for(M), dim3(kThreads), 0, st, M, ord.id1, ord.khi, ord.khi2);
+    if ((r = sort_pairs(arena, ord.khi2, ord.khi, ord.id1, ord.id0, M, 0, 32 + node_bits, st)) != LFR_OK) return r;
+    hipLaunchKernelGGL(k_cc_keys, grid_for(M), dim3(kThreads), 0, st, M, ord.id0, n1, cc.label, ord.ck0);
+    return sort_pairs(arena, ord.ck0, ord.ck1, ord.id0, ord.id1, M, 0, node_bits, st);   // stable
+}
+
+// flags -> segment ids, starts, longest segment
+int Stage::segments(bool states_fresh) {
+    // (the one long prefix sum of the stage: rocPRIM's larger tiles keep the look-back chain short - 20.6 us with its init launch
+    // against 26.9 us for the one-launch kernel at 2.5 M flags; the short sums below are the other way round.  The one-launch sum's
+    // states are good for one use: a second pass over the segments takes the library's.)
+    if (M + 1 > (int64_t)1 << 20 || !states_fresh) { const int r = exclusive_sum(arena, ord.flags, ord.segid, M + 1, st); if (r != LFR_OK) return r; }
+    else LFR_HIP_TRY(exclusive_sum_one_launch(ord.flags, ord.segid, M + 1, scan_state, st));
+    hipLaunchKernelGGL(k_seg_starts, grid_for(std::max<int64_t>(M, 1)), dim3(kThreads), 0, st, M, ord.flags, ord.segid, ord.starts, counts);
+    hipLaunchKernelGGL(k_seg_maxlen, grid_few(seg_cap), dim3(kThreads), 0, st, seg_cap, ord.starts, counts);
+    return LFR_OK;
+}
+
+// 2. matches grouped by connected component, inside a component in the reference's order: descending (sim, n1, n2).
+// The counting road (k_rank_sort) first: group by component, look at the longest segment (the stage's first read-back), count inside
+// the segments.  A giant component (or LFR_ONE_SORT_ORDER=1) takes one sort over (component | ~similarity) + the tie repair; the
+// tests' LFR_MAX_TIE_RUN=0 takes the three sorts at once (a long tie found by the repair takes them later: graph_stage_on_device).
+int Stage::order_matches(MatchOrder &kind) {
+    int rc;
+    LFR_TAKE(arena, kStageArena, ord.rec, uint4, M);
+    ord.khi = reinterpret_cast<uint64_t *>(ord.rec); ord.khi2 = ord.khi + M;
+    LFR_TAKE(arena, kStageArena, ord.klo, uint32_t, M); LFR_TAKE(arena, kStageArena, ord.klo2, uint32_t, M);
+    LFR_TAKE(arena, kStageArena, ord.srec, uint4, M);
+    LFR_TAKE(arena, kStageArena, ord.id0, uint32_t, M); LFR_TAKE(arena, kStageArena, ord.id1, uint32_t, M);
+    LFR_TAKE(arena, kStageArena, ord.ck0, uint32_t, M); LFR_TAKE(arena, kStageArena, ord.ck1, uint32_t, M);
+    LFR_TAKE(arena, kStageArena, ord.segid, uint32_t, M + 1);
+    LFR_TAKE(arena, kStageArena, ord.starts, uint32_t, std::min(N, M) + 2);
+    ord.order = ord.id1;
+    const bool try_counting = knobs.max_tie_run > 0 && !knobs.one_sort_order;
+    if (try_counting) {
+        hipLaunchKernelGGL(k_match_records, grid_for(M), dim3(kThreads), 0, st, M, n1, n2, sim, cc.label, ord.rec, ord.ck0, ord.id0);
+        if ((rc = sort_pairs(arena, ord.ck0, ord.ck1, ord.id0, ord.id1, M, 0, node_bits, st)) != LFR_OK) return rc;
+        hipLaunchKernelGGL(k_seg_flags, grid_for(M), dim3(kThreads), 0, st, M, ord.ck1, ord.flags);
+        if ((rc = segments(true)) != LFR_OK) return rc;
+        lap("grouped by connected component");
+        if ((rc = read_counts("first read-back")) != LFR_OK) return rc;
+        if ((int64_t)h_counts[CNT_MAX_SEG] <= kRankSortMax) {
+            const size_t window = sizeof(uint4) * ((size_t)kThreads + 2 * (size_t)h_counts[CNT_MAX_SEG]);     // (8 KB for config 4's 136: eight workgroups per CU)
+            hipLaunchKernelGGL(k_rank_sort, grid_for(M), dim3(kThreads), window, st, M, ord.id1, ord.rec, ord.flags, ord.segid, ord.starts, ord.id0, ord.srec);
+            ord.order = ord.id0;
+            kind = MatchOrder::counted_streamed;
+            return LFR_OK;
+        }
+    }
+    if (knobs.max_tie_run > 0) {
+        hipLaunchKernelGGL(k_cc_sim_keys, grid_for(M), dim3(kThreads), 0, st, M, n1, sim, cc.label, ord.khi, ord.id0);
+        if ((rc = sort_pairs(arena, ord.khi, ord.khi2, ord.id0, ord.id1, M, 0, 32 + node_bits, st)) != LFR_OK) return rc;
+        hipLaunchKernelGGL(k_tie_fix, grid_for(M), dim3(kThreads), 0, st, M, ord.khi2, ord.order, n1, n2, knobs.max_tie_run, counts);
+        hipLaunchKernelGGL(k_seg_flags_hi, grid_for(M), dim3(kThreads), 0, st, M, ord.khi2, ord.flags);
+        kind = MatchOrder::one_sort_tie_repair;
+    } else {
+        if ((rc = three_sorts()) != LFR_OK) return rc;
+        hipLaunchKernelGGL(k_seg_flags, grid_for(M), dim3(kThreads), 0, st, M, ord.ck1, ord.flags);
+        kind = MatchOrder::three_sorts;
+    }
+    return segments(!try_counting);
+}
+
+// 3. greedy constrained union-find per connected component: the small ones, one thread each (from scratch: also after a re-order)
+int Stage::union_find_small(MatchOrder kind) {
+    if (!uf.par) {
+        LFR_TAKE(arena, kStageArena, uf.par, int32_t, N); LFR_TAKE(arena, kStageArena, uf.next, int32_t, N); LFR_TAKE(arena, kStageArena, uf.tail, int32_t, N);
+        LFR_TAKE(arena, kStageArena, uf.cnt, int32_t, N); LFR_TAKE(arena, kStageArena, uf.sig, ulonglong2, N);
+    }
+    hipLaunchKernelGGL(k_init_nodes, grid_for(N), dim3(kThreads), 0, st, N, dg->node_image, uf.par, uf.next, uf.tail, uf.cnt, uf.sig);
+    if (kind == MatchOrder::counted_streamed)      // (the matches as a stream of sorted records)
+        hipLaunchKernelGGL(k_kruskal_stream, grid_for(seg_cap), dim3(kThreads), 0, st, seg_cap, knobs.serial_limit, counts, ord.starts, ord.srec, dg->node_image,
+                           uf.par, uf.next, uf.tail, uf.cnt, uf.sig);
+    else
+        hipLaunchKernelGGL(k_kruskal, grid_for(seg_cap), dim3(kThreads), 0, st, seg_cap, knobs.serial_limit, counts, ord.starts, ord.order, n1, n2,
+                           dg->node_image, uf.par, uf.next, uf.tail, uf.cnt, uf.sig);
+    return LFR_OK;
+}
+
+// 4. ... the large ones in parallel rounds
+int Stage::union_find_rounds() {
+    const int W = (int)((g.image_names.size() + 63) / 64);
+    const size_t bits_bytes = (size_t)N * W * 8;
+    if (bits_bytes > kMaxBitsetBytes) return use_host("image bitsets above the cap");
+    // Rounds run in batches of kRoundBatch without a host round trip: every round takes its input count from the device
+    // (the launches are sized by the count of the last read-back: counts only shrink), a round with nothing pending is two
+    // empty launches.  Round 2 read the count back after every round: 76 synchronisations for config 5's giant component.
+    constexpr int kRoundBatch = 8;
+    static_assert(CNT_HOST_ROUNDS + kRoundBatch + 1 <= CNT_HOST_WORDS, "the rounds' counters fit behind the counts");
+    constexpr char kRoundsArena[] = "graph stage: rounds arena";
+    DevArena rounds_arena;
+    if (!rounds_arena.init(ctx, bits_bytes + 2 * (size_t)M * sizeof(Pending) + 8 * (size_t)N + 65536)) return LFR_ERR_NOMEM;
+    unsigned long long *bits, *minpos;
+    Pending *pa, *pb;
+    uint32_t *ctr, *rc_;
+    LFR_TAKE(rounds_arena, kRoundsArena, bits, unsigned long long, (size_t)N * W); LFR_TAKE(rounds_arena, kRoundsArena, minpos, unsigned long long, N);
+    LFR_TAKE(rounds_arena, kRoundsArena, pa, Pending, M); LFR_TAKE(rounds_arena, kRoundsArena, pb, Pending, M);
+    LFR_TAKE(rounds_arena, kRoundsArena, ctr, uint32_t, 64);
+    LFR_HIP_TRY(hipMemsetAsync(bits, 0, bits_bytes, st));
+    LFR_HIP_TRY(hipMemsetAsync(minpos, 0xff, 8 * (size_t)N, st));
+    LFR_HIP_TRY(hipMemsetAsync(ctr, 0, 4 * 64, st));
+    uint32_t *h_ctr = h_counts + CNT_HOST_ROUNDS;
+    // The ordered list goes through the rounds in PREFIX BLOCKS (2 N positions, then doubling): the sequential rule finishes
+    // a prefix before it looks at the rest, so rounds over a block alone are exact, and a match is only carried through the
+    // rounds of its own block.  With the whole list pending at once every match was re-evaluated each round until its
+    // endpoints had met - 1.2e8 evaluations for config 5's 5.3 M matches (58 rounds); the tracks assemble from the first
+    // few hundred thousand matches and what comes later retires in its block's first round: a twelfth of the work in a
+    // simulation of this schedule, a few rounds more.
+    const int64_t first_block = knobs.rounds_first_block ? knobs.rounds_first_block : std::max<int64_t>(2 * N, 1024);
+    int64_t rounds = 0, launched = 0;
+    // (one launch per round: grid-barrier and one-XCD forms measured slower - profiles/r03_rounds_cooperative.txt, r06_ab/rounds_tail.txt)
+    LFR_TAKE(rounds_arena, kRoundsArena, rc_, uint32_t, kRoundBatch + 2);
+    LFR_HIP_TRY(hipMemsetAsync(rc_, 0, 4 * (kRoundBatch + 2), st));
+    for (int64_t k_lo = 0, size = first_block; k_lo < M; k_lo += size, size *= 2) {
+        const int64_t k_hi = std::min(M, k_lo + size);
+        LFR_HIP_TRY(hipMemsetAsync(rc_ + kRoundBatch, 0, 4, st));
+        hipLaunchKernelGGL(k_large_pending, grid_for_items(k_hi - k_lo, kAppendItems), dim3(kThreads), 0, st, k_lo, k_hi, knobs.serial_limit, ord.flags, ord.segid, ord.starts,
+                           ord.order, n1, n2, dg->node_image, W, bits, pa, rc_ + kRoundBatch);
+        LFR_HIP_TRY(hipMemcpyAsync(h_ctr, rc_ + kRoundBatch, 4, hipMemcpyDeviceToHost, st));
+        LFR_HIP_TRY(stream_wait(st));
+        uint32_t bound = h_ctr[0];
+        while (bound > 0) {
+            if (launched + kRoundBatch > kMaxRounds) return use_host("round limit");   // a path-shaped dependency chain: sequential anyway
+            hipLaunchKernelGGL(k_round_counters_shift, dim3(1), dim3(64), 0, st, rc_, kRoundBatch);
+            for (int j = 0; j < kRoundBatch; ++j, ++launched) {
+                const unsigned long long round_hi = (unsigned long long)(kMaxRounds - launched) << 32;
+                hipLaunchKernelGGL(k_round_eval, grid_for_items(bound, kEvalItems), dim3(kThreads), 0, st, rc_ + j, pa, uf.par, bits, W, round_hi, minpos, pb, rc_ + j + 1);
+                hipLaunchKernelGGL(k_round_accept, grid_for(bound), dim3(kThreads), 0, st, rc_ + j + 1, pb, round_hi, minpos, uf.par, uf.cnt, bits, W, ctr + 3);
+                std::swap(pa, pb);
+            }
+            LFR_HIP_TRY(hipMemcpyAsync(h_ctr, rc_, 4 * (kRoundBatch + 1), hipMemcpyDeviceToHost, st));
+            LFR_HIP_TRY(stream_wait(st));
+            for (int j = 0; j < kRoundBatch; ++j) rounds += h_ctr[j] > 0 ? 1 : 0;
+            if (knobs.trace > 2) fprintf(stderr, "lfr graph stage:   block [%lld, %lld) rounds ..%lld: pending %u -> %u\n", (long long)k_lo, (long long)k_hi, (long long)rounds, h_ctr[0], h_ctr[kRoundBatch]);
+            bound = h_ctr[kRoundBatch];
+        }
+    }
+    stats.kruskal_rounds = (double)rounds;
+    return LFR_OK;                                 // (every round has been waited for: the rounds' arena goes back to the cache)
+}
+
+// 5. track ids (roots in ascending node index), sizes; then the roots
+int Stage::tracks_and_roots(MatchOrder kind) {
+    LFR_TAKE(arena, kStageArena, trk.rrank, uint32_t, N + 1);
+    hipLaunchKernelGGL(k_root_flags, grid_for(N), dim3(kThreads), 0, st, N, uf.par, trk.rflag);
+    LFR_HIP_TRY(exclusive_sum_one_launch(trk.rflag, trk.rrank, N + 1, scan_state + scan_words_m, st));
+    hipLaunchKernelGGL(k_track_ids, grid_for(N), dim3(kThreads), 0, st, N, uf.par, trk.rrank, dp->track, trk.tsize, counts);
+    LFR_HIP_TRY(hipEventRecord(ev[EV_TRACKS], st));
+    // (small connected components only: in the ordered list of a giant one a wave's matches share no nodes - config 5: 0.40 ms grouped, 0.12 plain)
+    if (has_large_components()) hipLaunchKernelGGL(k_scores, grid_for(M), dim3(kThreads), 0, st, M, n1, n2, sim, dp->track, trk.score);
+    else hipLaunchKernelGGL(k_scores_grouped, grid_for(M), dim3(kThreads), 0, st, M, kind == MatchOrder::counted_streamed ? ord.srec : nullptr, ord.order, n1, n2, sim,
+                            dp->track, trk.score);
+    hipLaunchKernelGGL(k_best_score, grid_for(N), dim3(kThreads), 0, st, N, dp->track, trk.score, trk.best);
+    hipLaunchKernelGGL(k_best_node, grid_for(N), dim3(kThreads), 0, st, N, dp->track, trk.score, trk.best, trk.bnode);
+    hipLaunchKernelGGL(k_mark_roots, grid_for(N), dim3(kThreads), 0, st, N, counts, trk.bnode, dp->is_root);
+    LFR_HIP_TRY(hipEventRecord(ev[EV_ROOTS], st));
+    return LFR_OK;
+}
+
+// components of the track meta-graph, numbered by their smallest track (solve.cc:292-300).  The first time they ARE the connected
+// components of step 1 and everything starts in the zero block; after a cut a union-find over the kept meta edges finds them
+// (solve.cc:345-372), what the first pass filled is cleared and the prefix sum is the library's (the one-launch states are used up).
+int Stage::label_components(bool after_cut) {
+    if (!after_cut) {
+        LFR_TAKE(arena, kStageArena, lab.mp, uint32_t, N); LFR_TAKE(arena, kStageArena, lab.crank, uint32_t, N + 1);
+        hipLaunchKernelGGL(k_cc_min_track, grid_for(N), dim3(kThreads), 0, st, N, cc.label, dp->track, lab.mp_parent);
+        hipLaunchKernelGGL(k_track_label, grid_for(N), dim3(kThreads), 0, st, N, cc.label, dp->track, lab.mp_parent, lab.mp);
+    } else {
+        hipLaunchKernelGGL(k_iota, grid_for(N), dim3(kThreads), 0, st, N, lab.mp_parent);
+        hipLaunchKernelGGL(k_meta_union_cut, grid_for(M), dim3(kThreads), 0, st, M, n1, n2, dp->track, lab.gc, lab.mp_parent);
+        hipLaunchKernelGGL(k_cc_labels, grid_for(N), dim3(kThreads), 0, st, N, lab.mp_parent, lab.mp);
+        LFR_HIP_TRY(hipMemsetAsync(lab.cflag, 0, 4 * (size_t)(N + 1), st));
+        LFR_HIP_TRY(hipMemsetAsync(lab.csize, 0, 4 * (size_t)N, st));
+        LFR_HIP_TRY(hipMemsetAsync(counts + CNT_MAX_COMP, 0, 4, st));
+    }
+    hipLaunchKernelGGL(k_comp_flags, grid_for(N), dim3(kThreads), 0, st, N, counts, lab.mp, lab.cflag);
+    if (after_cut) { const int rc = exclusive_sum(arena, lab.cflag, lab.crank, N + 1, st); if (rc != LFR_OK) return rc; }
+    else LFR_HIP_TRY(exclusive_sum_one_launch(lab.cflag, lab.crank, N + 1, scan_state + scan_words_m + scan_words_n, st));
+    hipLaunchKernelGGL(k_comp_sizes, grid_few(N), dim3(kThreads), 0, st, N, counts, lab.mp, lab.crank, trk.tsize, lab.csize);
+    hipLaunchKernelGGL(k_max_csize, grid_few(N), dim3(kThreads), 0, st, N, counts, lab.csize);
+    hipLaunchKernelGGL(k_node_comp, grid_for(N), dim3(kThreads), 0, st, N, dp->track, lab.mp, lab.crank, dp->comp);
+    LFR_HIP_TRY(hipGetLastError());
+    LFR_HIP_TRY(hipEventRecord(ev[after_cut ? EV_CUT_END : EV_COMPS], st));
+    return LFR_OK;
+}
+
+int Stage::read_counts(const char *what) {         // the device's counts into the pinned block, waited for
+    LFR_HIP_TRY(hipMemcpyAsync(h_counts, counts, 4 * CNT_WORDS, hipMemcpyDeviceToHost, st));
+    LFR_HIP_TRY(stream_wait(st));
+    lap(what);
+    return LFR_OK;
+}
+
+void Stage::trace_fill_time() const {
+    if (!knobs.trace) return;
+    float a = 0.f;
+    (void)hipEventElapsedTime(&a, ev[EV_BEGIN], ev[EV_FILLED]);
+    fprintf(stderr, "lfr graph stage: device time of the memsets before the first kernel: %.3f ms (zero block %zu bytes)\n", a, zero_bytes);
+}
+
+void Stage::debug_dump() const {                   // LFR_DEBUG_DUMP: intermediates of the stage as raw files (debugging aid)
+    if (!knobs.debug_dump) return;
+    auto dump = [&](const char *name, const void *dptr, size_t bytes) {
+        std::vector<char> h(bytes);
+        (void)hipMemcpy(h.data(), dptr, bytes, hipMemcpyDeviceToHost);
+        const std::string path = std::string(knobs.debug_dump) + "/" + name + ".bin";
+        if (FILE *f = fopen(path.c_str(), "wb")) { fwrite(h.data(), 1, bytes, f); fclose(f); }
     };
+    dump("order", ord.order, 4 * (size_t)M); dump("cc", cc.label, 4 * (size_t)N); dump("starts", ord.starts, 4 * (size_t)(std::min(N, M) + 2));
+    dump("par", uf.par, 4 * (size_t)N); dump("track", dp->track, 4 * (size_t)N); dump("counts", counts, 64);
+    dump("segid", ord.segid, 4 * (size_t)(M + 1)); dump("cnt", uf.cnt, 4 * (size_t)N);
+}
+
+// The size cap (solve.cc:311-343).  The deterministic bisection grows a region with a priority queue - sequential, and the meta
+// graph is tiny next to the match graph - so it runs on the host (lfr_graph.cpp: cut_components_from_pairs), but only on what
+// it needs: the device compacts the inter-track matches of the oversized components (a few per cent of a per cent
+// of the matches), the host cuts, the subset of every affected track goes back, and the device re-labels.
+int Stage::cut_oversized() {
+    constexpr char kCutArena[] = "graph stage: cut arena";
+    int rc;
+    LFR_HIP_TRY(hipEventCreate(&ev[EV_CUT_BEGIN])); LFR_HIP_TRY(hipEventCreate(&ev[EV_CUT_END]));
+    LFR_HIP_TRY(hipEventRecord(ev[EV_CUT_BEGIN], st));
+    const int64_t T = h_counts[CNT_TRACKS];
+    int32_t *tcomp;
+    uint32_t *cut_n;
+    LFR_TAKE(arena, kStageArena, tcomp, int32_t, T + 1); LFR_TAKE(arena, kStageArena, cut_n, uint32_t, 16); LFR_TAKE(arena, kStageArena, lab.gc, int32_t, T + 1);
+    DevArena cut_arena;                            // (pair, similarity) of every inter-track match of an oversized component
+    if (!cut_arena.init(ctx, 16 * (size_t)M + 65536)) return LFR_ERR_NOMEM;
+    unsigned long long *pair_key;
+    double *pair_sim;
+    LFR_TAKE(cut_arena, kCutArena, pair_key, unsigned long long, M); LFR_TAKE(cut_arena, kCutArena, pair_sim, double, M);
+    LFR_HIP_TRY(hipMemsetAsync(cut_n, 0, 64, st));
+    hipLaunchKernelGGL(k_track_comp, grid_for(T), dim3(kThreads), 0, st, T, counts, lab.mp, lab.crank, tcomp);
+    hipLaunchKernelGGL(k_cut_edges, grid_for_items(M, kAppendItems), dim3(kThreads), 0, st, M, n1, n2, sim, dp->track, tcomp, lab.csize, (uint32_t)max_nodes, pair_key, pair_sim, cut_n);
+    LFR_HIP_TRY(hipMemcpyAsync(h_counts + CNT_HOST_CUT_EDGES, cut_n, 4, hipMemcpyDeviceToHost, st));
+    LFR_HIP_TRY(stream_wait(st));
+    const size_t n_cut_edges = h_counts[CNT_HOST_CUT_EDGES];
+    // Meta edges (solve.cc:268-289,322-332): per unordered track pair the sum of the similarities -> int weight 100 * sum.
+    // Sorted and summed on the device (radix sort + reduce-by-key: 0.7 M matches of config 5 took a host std::sort 60 ms);
+    // sums of float32 values in fp64 are exact here, hence independent of the order of the additions.
+    DevArena sum_arena;
+    std::vector<unsigned long long> h_pair;
+    std::vector<double> h_sum;
+    std::vector<int32_t> h_tcomp((size_t)T), h_gc;
+    std::vector<uint32_t> h_tsize((size_t)T);
+    if (n_cut_edges) {
+        if (!sum_arena.init(ctx, 64 * n_cut_edges + ((size_t)16 << 20))) return LFR_ERR_NOMEM;
+        unsigned long long *key_s, *key_u;
+        double *sim_s, *sim_u;
+        LFR_TAKE(sum_arena, kCutArena, key_s, unsigned long long, n_cut_edges); LFR_TAKE(sum_arena, kCutArena, key_u, unsigned long long, n_cut_edges);
+        LFR_TAKE(sum_arena, kCutArena, sim_s, double, n_cut_edges); LFR_TAKE(sum_arena, kCutArena, sim_u, double, n_cut_edges);
+        int tbits = 1;
+        while (((int64_t)1 << tbits) < T) ++tbits;
+        if ((rc = sort_pairs(sum_arena, pair_key, key_s, pair_sim, sim_s, (int64_t)n_cut_edges, 0, 32 + tbits, st)) != LFR_OK) return rc;
+        if ((rc = sum_by_key(sum_arena, key_s, key_u, sim_s, sim_u, cut_n + 1, (int64_t)n_cut_edges, st)) != LFR_OK) return rc;
+        LFR_HIP_TRY(hipMemcpyAsync(h_counts + CNT_HOST_CUT_PAIRS, cut_n + 1, 4, hipMemcpyDeviceToHost, st));
+        LFR_HIP_TRY(stream_wait(st));
+        const size_t n_pairs = h_counts[CNT_HOST_CUT_PAIRS];
+        h_pair.resize(n_pairs); h_sum.resize(n_pairs);
+        LFR_HIP_TRY(hipMemcpyAsync(h_pair.data(), key_u, 8 * n_pairs, hipMemcpyDeviceToHost, st));
+        LFR_HIP_TRY(hipMemcpyAsync(h_sum.data(), sim_u, 8 * n_pairs, hipMemcpyDeviceToHost, st));
+    }
+    LFR_HIP_TRY(hipMemcpyAsync(h_tcomp.data(), tcomp, 4 * (size_t)T, hipMemcpyDeviceToHost, st));
+    LFR_HIP_TRY(hipMemcpyAsync(h_tsize.data(), trk.tsize, 4 * (size_t)T, hipMemcpyDeviceToHost, st));
+    LFR_HIP_TRY(stream_wait(st));
+    lap("cut: meta edges of the oversized components on the host");
+    stats.n_cut_components = cut_components_from_pairs(h_tcomp, h_tsize, h_pair, h_sum, max_nodes, h_gc);
+    lap("cut: recursive bisection");
+    LFR_HIP_TRY(hipMemcpyAsync(lab.gc, h_gc.data(), 4 * (size_t)T, hipMemcpyHostToDevice, st));
+    // drop the cut edges and re-label (solve.cc:345-372), the tail of the first labelling again
+    if ((rc = label_components(true)) != LFR_OK) return rc;
+    if ((rc = read_counts("cut: re-labelled")) != LFR_OK) return rc;      // (the staging vectors above die at scope end)
+    return LFR_OK;
+}
+
+// stats and labels into the Problem: last, once every step has succeeded
+int Stage::publish() {
+    float ms = 0.f;
+    LFR_HIP_TRY(hipEventElapsedTime(&ms, ev[EV_FILLED], ev[EV_TRACKS])); stats.tracks_ms = ms;
+    LFR_HIP_TRY(hipEventElapsedTime(&ms, ev[EV_TRACKS], ev[EV_ROOTS])); stats.roots_ms = ms;
+    LFR_HIP_TRY(hipEventElapsedTime(&ms, ev[EV_ROOTS], ev[EV_COMPS])); stats.graph_cut_ms = ms;
+    if (ev[EV_CUT_END]) { LFR_HIP_TRY(hipEventElapsedTime(&ms, ev[EV_CUT_BEGIN], ev[EV_CUT_END])); stats.graph_cut_ms += ms; }
+    stats.n_tracks = h_counts[CNT_TRACKS]; stats.max_track_size = h_counts[CNT_MAX_TRACK];
+    stats.n_components = h_counts[CNT_COMPS]; stats.max_component_size = h_counts[CNT_MAX_COMP];
+    dp->max_cc_matches = h_counts[CNT_MAX_SEG];
+    p.stats = stats;
+    std::lock_guard<std::mutex> lk(p.label_mu);
+    p.track.clear(); p.comp.clear(); p.is_root.clear();
+    p.host_labels_valid = false;                   // fetched from HBM on demand
+    p.devs.assign((size_t)device + 1, nullptr);
+    p.devs[device] = dp;
+    return LFR_OK;
+}
+
+}  // namespace
+
+int graph_stage_on_device(const Graph &g, int64_t max_nodes, int device, bool stage_flows, Problem &p, int shard_rank, int shard_world) {
+    Stage s(g, p, device);
     p.g = &g;
     p.stats = lfr_problem_stats{};
     p.host_batch = false;
     { std::lock_guard<std::mutex> lk(p.label_mu); p.devs.clear(); }
-    if (N == 0) { p.track.clear(); p.comp.clear(); p.is_root.clear(); p.host_labels_valid = true; return LFR_OK; }
-    // (every hand-back to the host graph stage says why under LFR_VERBOSE / LFR_TIMING: results are the same, the time is not - ADVICE r4)
-    auto use_host = [&](const char *why) {
-        if (vb || getenv("LFR_TIMING")) fprintf(stderr, "lfr graph stage: handed back to the host (%s)\n", why);
-        return LFR_GRAPHSTAGE_USE_HOST;
-    };
-    if (N >= ((int64_t)1 << 31) || M >= ((int64_t)1 << 30)) return use_host("2^31 nodes / 2^30 matches or more");
-    if (!g.sims_sum_exactly) return use_host("similarity sums would round");      // atomics would round in an order-dependent way: the reference's sequential sums run on the host
-    if (max_nodes <= 0) max_nodes = (int64_t)g.image_names.size();
-    std::shared_ptr<DevGraph> dg;
-    int rc = ensure_dev_graph(g, device, stage_flows, dg);       // endpoints on s_main now; the flows start travelling on s_copy
+    if (s.N == 0) { p.track.clear(); p.comp.clear(); p.is_root.clear(); p.host_labels_valid = true; return LFR_OK; }
+    if (s.N >= ((int64_t)1 << 31) || s.M >= ((int64_t)1 << 30)) return s.use_host("2^31 nodes / 2^30 matches or more");
+    if (!g.sims_sum_exactly) return s.use_host("similarity sums would round");      // atomics would round in an order-dependent way: the reference's sequential sums run on the host
+    s.max_nodes = max_nodes > 0 ? max_nodes : (int64_t)g.image_names.size();
+    int rc = ensure_dev_graph(g, device, stage_flows, s.dg);     // endpoints on s_main now; the flows start travelling on s_copy
     if (rc != LFR_OK) return rc;
-    DevCtx *ctx = dg->ctx;
+    s.ctx = s.dg->ctx;
     LFR_HIP_TRY(hipSetDevice(device));
-    hipStream_t st = ctx->s_main;
-    lap("device graph ready");
-    p.cc_sharded = false;
-    if (shard_world > 1 && shard_world <= 64 && M > 0) {
-        std::shared_ptr<DevGraph> dgs;
-        std::vector<unsigned long long> per_rank;
-        if ((rc = shard_dev_graph(dg, shard_rank, shard_world, dgs, per_rank)) != LFR_OK) return rc;
-        unsigned long long mx = 0;
-        for (int r = 0; r < shard_world; ++r) mx = std::max(mx, per_rank[r]);
-        // balanced enough (every rank decides the same from the same counts): the largest rank within 5/4 of the mean
-        if (4ull * mx * (unsigned long long)shard_world <= 5ull * (unsigned long long)M + 4096ull * shard_world) {
-            dg = dgs; M = dg->M;
-            p.cc_sharded = true; p.shard_matches = M; p.shard_matches_max = (int64_t)mx;
-        }
-        lap(p.cc_sharded ? "sharded by connected component" : "one connected component dominates: the whole graph on every rank");
-    }
-
-    std::shared_ptr<DevProblem> dp(new DevProblem());
-    dp->ctx = ctx; dp->graph = dg; dp->N = N;
-    if (!dp->slab.init(ctx, (size_t)9 * N + 4096)) return LFR_ERR_NOMEM;
-    dp->track = dp->slab.take_n<int32_t>(N); dp->comp = dp->slab.take_n<int32_t>(N); dp->is_root = dp->slab.take_n<uint8_t>(N);
-
-    DevArena arena;                                   // temporaries of this call
-    if (!arena.init(ctx, (size_t)112 * M + (size_t)112 * N + ((size_t)32 << 20))) return LFR_ERR_NOMEM;
-    size_t pin_bytes = 0;
-    uint32_t *h_counts = (uint32_t *)ctx->pinned_acquire(4 * (CNT_WORDS + 16), &pin_bytes);     // + the counters of a batch of union-find rounds
-    if (!h_counts) return LFR_ERR_NOMEM;
-    struct PinGuard { DevCtx *c; void *p; size_t b; ~PinGuard() { c->pinned_release(p, b); } } pin_guard{ctx, h_counts, pin_bytes};
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-    struct EvGuard { hipEvent_t *e; ~EvGuard() { for (int i = 0; i < 4; ++i) if (e[i]) (void)hipEventDestroy(e[i]); } } ev_guard{ev};
-    for (auto &e : ev) LFR_HIP_TRY(hipEventCreate(&e));
-    lap("slabs, pinned block, events");
-
-    const uint32_t *n1 = dg->n1, *n2 = dg->n2;
-    const float *sim = dg->sim;
-    int node_bits = 1;
-    while (((int64_t)1 << node_bits) < N) ++node_bits;
-    hipEvent_t ev_begin = nullptr;
-    if (trace) { LFR_HIP_TRY(hipEventCreate(&ev_begin)); LFR_HIP_TRY(hipEventRecord(ev_begin, st)); }
-    // everything that starts at zero sits in one block: one memset instead of a dozen
-    const size_t zero_mark = arena.top;
-    TAKE(counts, uint32_t, CNT_WORDS);
-    TAKE(flags, uint32_t, M + 1); TAKE(rflag, uint32_t, N + 1); TAKE(tsize, uint32_t, N);
-    TAKE(score, double, N); TAKE(best, unsigned long long, N); TAKE(cflag, uint32_t, N + 1); TAKE(csize, uint32_t, N);
-    // look-back states of the stage's prefix sums (exclusive_sum_one_launch: no init launch for states that start in the zero block)
-    const size_t scan_words_m = scan_state_words(M + 1), scan_words_n = scan_state_words(N + 1);
-    TAKE(scan_state, unsigned long long, scan_words_m + 2 * scan_words_n);
-    const size_t zero_bytes = arena.top - zero_mark;
-    TAKE(bnode, int32_t, N); TAKE(mp_parent, uint32_t, N);                // (next to each other: one region of -1 / of "no track yet")
-    {   // the stage's initial values in one launch (the memsets were 5 launches before the first kernel, 2 more before the meta-components)
-        FillRegions fr;
-        fr.add(arena.base + zero_mark, zero_bytes, 0);
-        fr.add(dp->is_root, (size_t)N, 0);
-        fr.add(bnode, (size_t)(reinterpret_cast<char *>(mp_parent + N) - reinterpret_cast<char *>(bnode)), 0xff);
-        LFR_HIP_TRY(fill_regions(fr, st));
-    }
-    LFR_HIP_TRY(hipEventRecord(ev[0], st));
-
-    // 1. connected components of the match graph (conflicts ignored)
-    TAKE(cc_parent, uint32_t, N); TAKE(cc, uint32_t, N);
-    hipLaunchKernelGGL(k_iota, grid_for(N), dim3(kThreads), 0, st, N, cc_parent);
-    {
-        for (int i = 0, done = 0; i < kUnionStages; done = kUnionStrides[i], ++i) {
-            if (i) hipLaunchKernelGGL(k_uf_flatten, grid_for(N), dim3(kThreads), 0, st, N, cc_parent);
-            hipLaunchKernelGGL(k_cc_union, grid_for((M + kUnionStrides[i] - 1) / kUnionStrides[i]), dim3(kThreads), 0, st, M, kUnionStrides[i], done, n1, n2, cc_parent);
-        }
-    }
-    hipLaunchKernelGGL(k_cc_labels, grid_for(N), dim3(kThreads), 0, st, N, cc_parent, cc);
-
-    // 2. matches grouped by connected component, inside a component in the reference's order: descending (sim, n1, n2).
-    //    One sort over (component | ~sim) + the tie fix; the exact three-sort order only if a run of equal similarities is too long for it
-    TAKE(rec, uint4, M);                              // (the 64-bit keys of the one-sort road share these 16 M bytes with the records of the counting road)
-    uint64_t *const khi = reinterpret_cast<uint64_t *>(rec), *const khi2 = khi + M;
-    TAKE(klo, uint32_t, M); TAKE(klo2, uint32_t, M);
-    TAKE(srec, uint4, M);                             // counting road: the records in the reference's order
-    TAKE(id0, uint32_t, M); TAKE(id1, uint32_t, M);
-    TAKE(ck0, uint32_t, M); TAKE(ck1, uint32_t, M); TAKE(segid, uint32_t, M + 1);
-    TAKE(starts, uint32_t, std::min(N, M) + 2);
-    uint32_t *order = id1;
-    int max_tie_run = kMaxTieRun;
-    if (const char *e = getenv("LFR_MAX_TIE_RUN")) max_tie_run = std::max(0, atoi(e));     // (tests: 0 = always the three sorts)
-    auto three_sorts = [&]() -> int {
-        int r;
-        hipLaunchKernelGGL(k_match_keys, grid_for(M), dim3(kThreads), 0, st, M, (uint32_t)(N - 1), node_bits, n1, n2, sim, khi, klo, id0);
-        if ((r = sort_pairs(arena, klo, klo2, id0, id1, M, 0, node_bits, st)) != LFR_OK) return r;
-        hipLaunchKernelGGL(k_gather_u64, grid_for(M), dim3(kThreads), 0, st, M, id1, khi, khi2);
-        if ((r = sort_pairs(arena, khi2, khi, id1, id0, M, 0, 32 + node_bits, st)) != LFR_OK) return r;
-        hipLaunchKernelGGL(k_cc_keys, grid_for(M), dim3(kThreads), 0, st, M, id0, n1, cc, ck0);
-        return sort_pairs(arena, ck0, ck1, id0, id1, M, 0, node_bits, st);                // stable: -> order
-    };
-    const int64_t seg_cap = std::min(N, M) + 1;       // a segment has >= 1 match and >= 2 nodes
-    bool scan_state_used = false;
-    auto segments = [&]() -> int {                    // flags -> segment ids, starts, longest segment
-        // (the one long prefix sum of the stage: rocPRIM's larger tiles keep the look-back chain short - 20.6 us with its init launch
-        // against 26.9 us for the one-launch kernel at 2.5 M flags; the short sums below are the other way round.  The one-launch sum's
-        // states are good for one use: a second pass over the segments takes the library's.)
-        if (M + 1 > (int64_t)1 << 20 || scan_state_used) { const int r = exclusive_sum(arena, flags, segid, M + 1, st); if (r != LFR_OK) return r; }
-        else { LFR_HIP_TRY(exclusive_sum_one_launch(flags, segid, M + 1, scan_state, st)); scan_state_used = true; }
-        hipLaunchKernelGGL(k_seg_starts, grid_for(std::max<int64_t>(M, 1)), dim3(kThreads), 0, st, M, flags, segid, starts, counts);
-        hipLaunchKernelGGL(k_seg_maxlen, grid_few(seg_cap), dim3(kThreads), 0, st, seg_cap, starts, counts);
-        return LFR_OK;
-    };
-    // The counting road (k_rank_sort) first: group by component, look at the longest segment (the stage's first read-back, which used to
-    // follow the small-component union-find), count inside the segments.  A giant component (or LFR_ONE_SORT_ORDER=1, or the tests'
-    // LFR_MAX_TIE_RUN=0) takes the roads of rounds 3-5: one sort over (component | ~similarity) + tie repair, or the three sorts.
-    bool counts_on_host = false, order_done = false;
-    if (max_tie_run > 0 && !getenv("LFR_ONE_SORT_ORDER")) {
-        hipLaunchKernelGGL(k_match_records, grid_for(M), dim3(kThreads), 0, st, M, n1, n2, sim, cc, rec, ck0, id0);
-        if ((rc = sort_pairs(arena, ck0, ck1, id0, id1, M, 0, node_bits, st)) != LFR_OK) return rc;
-        hipLaunchKernelGGL(k_seg_flags, grid_for(M), dim3(kThreads), 0, st, M, ck1, flags);
-        if ((rc = segments()) != LFR_OK) return rc;
-        lap("grouped by connected component");
-        LFR_HIP_TRY(hipMemcpyAsync(h_counts, counts, 4 * CNT_WORDS, hipMemcpyDeviceToHost, st));
-        LFR_HIP_TRY(stream_wait(st));
-        lap("first read-back");
-        if ((int64_t)h_counts[CNT_MAX_SEG] <= kRankSortMax) {
-            const size_t window = sizeof(uint4) * ((size_t)kThreads + 2 * (size_t)h_counts[CNT_MAX_SEG]);     // (8 KB for config 4's 136: eight workgroups per CU)
-            hipLaunchKernelGGL(k_rank_sort, grid_for(M), dim3(kThreads), window, st, M, id1, rec, flags, segid, starts, id0, srec);
-            order = id0;
-            counts_on_host = true; order_done = true;
-        }
-    }
-    if (!order_done) {
-        if (max_tie_run > 0) {
-            hipLaunchKernelGGL(k_cc_sim_keys, grid_for(M), dim3(kThreads), 0, st, M, n1, sim, cc, khi, id0);
-            if ((rc = sort_pairs(arena, khi, khi2, id0, id1, M, 0, 32 + node_bits, st)) != LFR_OK) return rc;
-            hipLaunchKernelGGL(k_tie_fix, grid_for(M), dim3(kThreads), 0, st, M, khi2, order, n1, n2, max_tie_run, counts);
-            hipLaunchKernelGGL(k_seg_flags_hi, grid_for(M), dim3(kThreads), 0, st, M, khi2, flags);
-        } else {
-            if ((rc = three_sorts()) != LFR_OK) return rc;
-            hipLaunchKernelGGL(k_seg_flags, grid_for(M), dim3(kThreads), 0, st, M, ck1, flags);
-        }
-        if ((rc = segments()) != LFR_OK) return rc;
-    }
-
-    // 3. greedy constrained union-find per connected component: small ones one thread each ...
-    TAKE(par, int32_t, N); TAKE(next, int32_t, N); TAKE(tail, int32_t, N); TAKE(cnt, int32_t, N); TAKE(sig, ulonglong2, N);
-    hipLaunchKernelGGL(k_init_nodes, grid_for(N), dim3(kThreads), 0, st, N, dg->node_image, par, next, tail, cnt, sig);
-    int64_t serial_limit = kSerialSegmentEdges;
-    if (const char *e = getenv("LFR_SERIAL_SEGMENT_EDGES")) serial_limit = std::max<int64_t>(0, atoll(e));
-    // (counting road: the matches as a stream of sorted records - k_kruskal_stream)
-    const bool streamed = counts_on_host && order_done;
-    if (streamed)
-        hipLaunchKernelGGL(k_kruskal_stream, grid_for(seg_cap), dim3(kThreads), 0, st, seg_cap, serial_limit, counts, starts, srec, dg->node_image, par, next, tail, cnt, sig);
-    else
-        hipLaunchKernelGGL(k_kruskal, grid_for(seg_cap), dim3(kThreads), 0, st, seg_cap, serial_limit, counts, starts, order, n1, n2,
-                           dg->node_image, par, next, tail, cnt, sig);
-    // ... large ones in parallel rounds (first read-back: is there any? - the counting road has read the counts already)
-    lap("sorts / connected components / small-component union-find enqueued");
-    if (!counts_on_host) {
-        LFR_HIP_TRY(hipMemcpyAsync(h_counts, counts, 4 * CNT_WORDS, hipMemcpyDeviceToHost, st));
-        LFR_HIP_TRY(stream_wait(st));
-        lap("first read-back");
-    }
-    if (h_counts[CNT_LONG_TIE]) {
+    s.st = s.ctx->s_main;
+    s.lap("device graph ready");
+    if ((rc = s.shard_if_balanced(shard_rank, shard_world)) != LFR_OK) return rc;
+    if ((rc = s.prepare()) != LFR_OK) return rc;
+    if ((rc = s.connected_components()) != LFR_OK) return rc;
+    MatchOrder order;
+    if ((rc = s.order_matches(order)) != LFR_OK) return rc;
+    if ((rc = s.union_find_small(order)) != LFR_OK) return rc;
+    s.lap("sorts / connected components / small-component union-find enqueued");
+    // (first read-back: are there large components? - the counting road has read the counts already)
+    if (order != MatchOrder::counted_streamed && (rc = s.read_counts("first read-back")) != LFR_OK) return rc;
+    if (s.h_counts[CNT_LONG_TIE]) {
         // a long run of equal similarities: the exact order from the three sorts (the segments - which matches, where - are the same:
         // flags, segment ids and starts stay), the union-find of the small components again from scratch
-        if ((rc = three_sorts()) != LFR_OK) return rc;
-        hipLaunchKernelGGL(k_init_nodes, grid_for(N), dim3(kThreads), 0, st, N, dg->node_image, par, next, tail, cnt, sig);
-        hipLaunchKernelGGL(k_kruskal, grid_for(seg_cap), dim3(kThreads), 0, st, seg_cap, serial_limit, counts, starts, order, n1, n2,
-                           dg->node_image, par, next, tail, cnt, sig);
-        p.stats.tie_resorts = 1.0;
-        lap("three-sort order after a long tie");
+        order = MatchOrder::three_sorts;
+        if ((rc = s.three_sorts()) != LFR_OK || (rc = s.union_find_small(order)) != LFR_OK) return rc;
+        s.stats.tie_resorts = 1.0;
+        s.lap("three-sort order after a long tie");
     }
-    if (trace && ev_begin) {
-        float a = 0.f;
-        (void)hipEventElapsedTime(&a, ev_begin, ev[0]);
-        fprintf(stderr, "lfr graph stage: device time of the memsets before the first kernel: %.3f ms (zero block %zu bytes)\n", a, zero_bytes);
-        (void)hipEventDestroy(ev_begin);
-    }
-    DevArena rounds_arena;
-    if ((int64_t)h_counts[CNT_MAX_SEG] > serial_limit) {
-        const int W = (int)((g.image_names.size() + 63) / 64);
-        const size_t bits_bytes = (size_t)N * W * 8;
-        if (bits_bytes > kMaxBitsetBytes) return use_host("image bitsets above the cap");
-        if (!rounds_arena.init(ctx, bits_bytes + 2 * (size_t)M * sizeof(Pending) + 8 * (size_t)N + 65536)) return LFR_ERR_NOMEM;
-        unsigned long long *bits = rounds_arena.take_n<unsigned long long>((size_t)N * W);
-        unsigned long long *minpos = rounds_arena.take_n<unsigned long long>(N);
-        Pending *pa = rounds_arena.take_n<Pending>(M), *pb = rounds_arena.take_n<Pending>(M);
-        uint32_t *ctr = rounds_arena.take_n<uint32_t>(64);
-        if (!bits || !minpos || !pa || !pb || !ctr) { set_error("graph stage: rounds arena exhausted"); return LFR_ERR_NOMEM; }
-        LFR_HIP_TRY(hipMemsetAsync(bits, 0, bits_bytes, st));
-        LFR_HIP_TRY(hipMemsetAsync(minpos, 0xff, 8 * (size_t)N, st));
-        LFR_HIP_TRY(hipMemsetAsync(ctr, 0, 4 * 64, st));
-        uint32_t *h_ctr = h_counts + CNT_WORDS;        // (16 more words behind the counts proper)
-        // The ordered list goes through the rounds in PREFIX BLOCKS (2 N positions, then doubling): the sequential rule finishes
-        // a prefix before it looks at the rest, so rounds over a block alone are exact, and a match is only carried through the
-        // rounds of its own block.  With the whole list pending at once every match was re-evaluated each round until its
-        // endpoints had met - 1.2e8 evaluations for config 5's 5.3 M matches (58 rounds); the tracks assemble from the first
-        // few hundred thousand matches and what comes later retires in its block's first round: a twelfth of the work in a
-        // simulation of this schedule, a few rounds more.
-        int64_t first_block = std::max<int64_t>(2 * N, 1024);
-        if (const char *e = getenv("LFR_ROUNDS_FIRST_BLOCK")) first_block = std::max<int64_t>(1, atoll(e));
-        int64_t rounds = 0;
-        // (one launch per round: grid-barrier and one-XCD forms measured slower - profiles/r03_rounds_cooperative.txt, r06_ab/rounds_tail.txt)
-        // Rounds run in batches of kRoundBatch without a host round trip: every round takes its input count from the device
-        // (the launches are sized by the count of the last read-back: counts only shrink), a round with nothing pending is two
-        // empty launches.  Round 2 read the count back after every round: 76 synchronisations for config 5's giant component.
-        constexpr int kRoundBatch = 8;
-        uint32_t *rc_ = rounds_arena.take_n<uint32_t>(kRoundBatch + 2);
-        if (!rc_) { set_error("graph stage: rounds arena exhausted"); return LFR_ERR_NOMEM; }
-        int64_t launched = 0;
-        LFR_HIP_TRY(hipMemsetAsync(rc_, 0, 4 * (kRoundBatch + 2), st));
-        for (int64_t k_lo = 0, size = first_block; k_lo < M; k_lo += size, size *= 2) {
-            const int64_t k_hi = std::min(M, k_lo + size);
-            LFR_HIP_TRY(hipMemsetAsync(rc_ + kRoundBatch, 0, 4, st));
-            hipLaunchKernelGGL(k_large_pending, grid_for_items(k_hi - k_lo, kAppendItems), dim3(kThreads), 0, st, k_lo, k_hi, serial_limit, flags, segid, starts, order, n1, n2,
-                               dg->node_image, W, bits, pa, rc_ + kRoundBatch);
-            LFR_HIP_TRY(hipMemcpyAsync(h_ctr, rc_ + kRoundBatch, 4, hipMemcpyDeviceToHost, st));
-            LFR_HIP_TRY(stream_wait(st));
-            uint32_t bound = h_ctr[0];
-            while (bound > 0) {
-                if (launched + kRoundBatch > kMaxRounds) return use_host("round limit");   // a path-shaped dependency chain: sequential anyway
-                hipLaunchKernelGGL(k_round_counters_shift, dim3(1), dim3(64), 0, st, rc_, kRoundBatch);
-                for (int j = 0; j < kRoundBatch; ++j, ++launched) {
-                    const unsigned long long round_hi = (unsigned long long)(kMaxRounds - launched) << 32;
-                    hipLaunchKernelGGL(k_round_eval, grid_for_items(bound, kEvalItems), dim3(kThreads), 0, st, rc_ + j, pa, par, bits, W, round_hi, minpos, pb, rc_ + j + 1);
-                    hipLaunchKernelGGL(k_round_accept, grid_for(bound), dim3(kThreads), 0, st, rc_ + j + 1, pb, round_hi, minpos, par, cnt, bits, W, ctr + 3);
-                    std::swap(pa, pb);
-                }
-                LFR_HIP_TRY(hipMemcpyAsync(h_ctr, rc_, 4 * (kRoundBatch + 1), hipMemcpyDeviceToHost, st));
-                LFR_HIP_TRY(stream_wait(st));
-                for (int j = 0; j < kRoundBatch; ++j) rounds += h_ctr[j] > 0 ? 1 : 0;
-                if (trace > 2) fprintf(stderr, "lfr graph stage:   block [%lld, %lld) rounds ..%lld: pending %u -> %u\n", (long long)k_lo, (long long)k_hi, (long long)rounds, h_ctr[0], h_ctr[kRoundBatch]);
-                bound = h_ctr[kRoundBatch];
-            }
-        }
-        p.stats.kruskal_rounds = (double)rounds;
-    }
-
-    // 5. track ids (roots in ascending node index), sizes
-    TAKE(rrank, uint32_t, N + 1);
-    hipLaunchKernelGGL(k_root_flags, grid_for(N), dim3(kThreads), 0, st, N, par, rflag);
-    LFR_HIP_TRY(exclusive_sum_one_launch(rflag, rrank, N + 1, scan_state + scan_words_m, st));
-    hipLaunchKernelGGL(k_track_ids, grid_for(N), dim3(kThreads), 0, st, N, par, rrank, dp->track, tsize, counts);
-    LFR_HIP_TRY(hipEventRecord(ev[1], st));
-
-    // roots
-    // (small connected components only: in the ordered list of a giant one a wave's matches share no nodes - config 5: 0.40 ms grouped, 0.12 plain)
-    if ((int64_t)h_counts[CNT_MAX_SEG] > serial_limit) hipLaunchKernelGGL(k_scores, grid_for(M), dim3(kThreads), 0, st, M, n1, n2, sim, dp->track, score);
-    else hipLaunchKernelGGL(k_scores_grouped, grid_for(M), dim3(kThreads), 0, st, M, streamed ? srec : nullptr, order, n1, n2, sim, dp->track, score);
-    hipLaunchKernelGGL(k_best_score, grid_for(N), dim3(kThreads), 0, st, N, dp->track, score, best);
-    hipLaunchKernelGGL(k_best_node, grid_for(N), dim3(kThreads), 0, st, N, dp->track, score, best, bnode);
-    hipLaunchKernelGGL(k_mark_roots, grid_for(N), dim3(kThreads), 0, st, N, counts, bnode, dp->is_root);
-    LFR_HIP_TRY(hipEventRecord(ev[2], st));
-
-    // components of the track meta-graph, numbered by their smallest track (solve.cc:292-300)
-    TAKE(mp, uint32_t, N); TAKE(crank, uint32_t, N + 1);                                 // (mp_parent - here: smallest track per connected component - starts at ~0: the stage's first fill)
-    hipLaunchKernelGGL(k_cc_min_track, grid_for(N), dim3(kThreads), 0, st, N, cc, dp->track, mp_parent);
-    hipLaunchKernelGGL(k_track_label, grid_for(N), dim3(kThreads), 0, st, N, cc, dp->track, mp_parent, mp);
-    hipLaunchKernelGGL(k_comp_flags, grid_for(N), dim3(kThreads), 0, st, N, counts, mp, cflag);
-    LFR_HIP_TRY(exclusive_sum_one_launch(cflag, crank, N + 1, scan_state + scan_words_m + scan_words_n, st));
-    hipLaunchKernelGGL(k_comp_sizes, grid_few(N), dim3(kThreads), 0, st, N, counts, mp, crank, tsize, csize);
-    hipLaunchKernelGGL(k_max_csize, grid_few(N), dim3(kThreads), 0, st, N, counts, csize);
-    hipLaunchKernelGGL(k_node_comp, grid_for(N), dim3(kThreads), 0, st, N, dp->track, mp, crank, dp->comp);
-    LFR_HIP_TRY(hipGetLastError());
-    LFR_HIP_TRY(hipEventRecord(ev[3], st));
-
-    // the one read-back of the stage
-    lap("tracks / roots / components enqueued");
-    LFR_HIP_TRY(hipMemcpyAsync(h_counts, counts, 4 * CNT_WORDS, hipMemcpyDeviceToHost, st));
-    LFR_HIP_TRY(stream_wait(st));
-    lap("final read-back");
-    const bool needs_cut = (int64_t)h_counts[CNT_MAX_COMP] > max_nodes;      // solve.cc:311-343
-    if (const char *dd = getenv("LFR_DEBUG_DUMP")) {      // intermediates of the stage as raw files (debugging aid)
-        auto dump = [&](const char *name, const void *dptr, size_t bytes) {
-            std::vector<char> h(bytes);
-            (void)hipMemcpy(h.data(), dptr, bytes, hipMemcpyDeviceToHost);
-            const std::string path = std::string(dd) + "/" + name + ".bin";
-            if (FILE *f = fopen(path.c_str(), "wb")) { fwrite(h.data(), 1, bytes, f); fclose(f); }
-        };
-        dump("order", order, 4 * (size_t)M); dump("cc", cc, 4 * (size_t)N); dump("starts", starts, 4 * (size_t)(std::min(N, M) + 2));
-        dump("par", par, 4 * (size_t)N); dump("track", dp->track, 4 * (size_t)N); dump("counts", counts, 64);
-        dump("segid", segid, 4 * (size_t)(M + 1)); dump("cnt", cnt, 4 * (size_t)N);
-    }
-    float ms = 0.f;
-    LFR_HIP_TRY(hipEventElapsedTime(&ms, ev[0], ev[1])); p.stats.tracks_ms = ms;
-    LFR_HIP_TRY(hipEventElapsedTime(&ms, ev[1], ev[2])); p.stats.roots_ms = ms;
-    LFR_HIP_TRY(hipEventElapsedTime(&ms, ev[2], ev[3])); p.stats.graph_cut_ms = ms;
-    p.stats.n_tracks = h_counts[CNT_TRACKS]; p.stats.max_track_size = h_counts[CNT_MAX_TRACK];
-    p.stats.n_components = h_counts[CNT_COMPS]; p.stats.max_component_size = h_counts[CNT_MAX_COMP];
-    dp->max_cc_matches = h_counts[CNT_MAX_SEG];
-    {
-        std::lock_guard<std::mutex> lk(p.label_mu);
-        p.track.clear(); p.comp.clear(); p.is_root.clear();
-        p.host_labels_valid = false;                  // fetched from HBM on demand
-        p.devs.assign((size_t)device + 1, nullptr);
-        p.devs[device] = dp;
-    }
-    if (needs_cut) {
-        // The size cap.  The deterministic bisection grows a region with a priority queue - sequential, and the meta
-        // graph is tiny next to the match graph - so it runs on the host (lfr_graph.cpp: recursive_cut), but only on what
-        // it needs: the device compacts the inter-track matches of the oversized components (a few per cent of a per cent
-        // of the matches), the host cuts, the subset of every affected track goes back, and the device re-labels.
-        hipEvent_t c0 = nullptr, c1 = nullptr;
-        struct EvPair { hipEvent_t &a, &b; ~EvPair() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); } } evp{c0, c1};
-        LFR_HIP_TRY(hipEventCreate(&c0)); LFR_HIP_TRY(hipEventCreate(&c1));
-        LFR_HIP_TRY(hipEventRecord(c0, st));
-        const int64_t T = h_counts[CNT_TRACKS];
-        TAKE(tcomp, int32_t, T + 1); TAKE(cut_n, uint32_t, 16); TAKE(gc_dev, int32_t, T + 1);
-        DevArena cut_arena;                               // (pair, similarity) of every inter-track match of an oversized component
-        if (!cut_arena.init(ctx, 16 * (size_t)M + 65536)) return LFR_ERR_NOMEM;
-        unsigned long long *pair_key = cut_arena.take_n<unsigned long long>(M);
-        double *pair_sim = cut_arena.take_n<double>(M);
-        if (!pair_key || !pair_sim) { set_error("graph stage: cut arena exhausted"); return LFR_ERR_NOMEM; }
-        LFR_HIP_TRY(hipMemsetAsync(cut_n, 0, 64, st));
-        hipLaunchKernelGGL(k_track_comp, grid_for(T), dim3(kThreads), 0, st, T, counts, mp, crank, tcomp);
-        hipLaunchKernelGGL(k_cut_edges, grid_for_items(M, kAppendItems), dim3(kThreads), 0, st, M, n1, n2, sim, dp->track, tcomp, csize, (uint32_t)max_nodes, pair_key, pair_sim, cut_n);
-        uint32_t *h_n = h_counts + 8;
-        LFR_HIP_TRY(hipMemcpyAsync(h_n, cut_n, 4, hipMemcpyDeviceToHost, st));
-        LFR_HIP_TRY(stream_wait(st));
-        const size_t n_cut_edges = h_n[0];
-        // Meta edges (solve.cc:268-289,322-332): per unordered track pair the sum of the similarities -> int weight 100 * sum.
-        // Sorted and summed on the device (radix sort + reduce-by-key: 0.7 M matches of config 5 took a host std::sort 60 ms);
-        // sums of float32 values in fp64 are exact here, hence independent of the order of the additions.
-        DevArena sum_arena;
-        size_t n_pairs = 0;
-        std::vector<unsigned long long> h_pair;
-        std::vector<double> h_sum;
-        std::vector<int32_t> h_tcomp((size_t)T), h_gc((size_t)T, -1);
-        std::vector<uint32_t> h_tsize((size_t)T);
-        if (n_cut_edges) {
-            if (!sum_arena.init(ctx, 64 * n_cut_edges + ((size_t)16 << 20))) return LFR_ERR_NOMEM;
-            unsigned long long *key_s = sum_arena.take_n<unsigned long long>(n_cut_edges), *key_u = sum_arena.take_n<unsigned long long>(n_cut_edges);
-            double *sim_s = sum_arena.take_n<double>(n_cut_edges), *sim_u = sum_arena.take_n<double>(n_cut_edges);
-            if (!key_s || !key_u || !sim_s || !sim_u) { set_error("graph stage: cut arena exhausted"); return LFR_ERR_NOMEM; }
-            int tbits = 1;
-            while (((int64_t)1 << tbits) < T) ++tbits;
-            if ((rc = sort_pairs(sum_arena, pair_key, key_s, pair_sim, sim_s, (int64_t)n_cut_edges, 0, 32 + tbits, st)) != LFR_OK) return rc;
-            if ((rc = sum_by_key(sum_arena, key_s, key_u, sim_s, sim_u, cut_n + 1, (int64_t)n_cut_edges, st)) != LFR_OK) return rc;
-            LFR_HIP_TRY(hipMemcpyAsync(h_n + 1, cut_n + 1, 4, hipMemcpyDeviceToHost, st));
-            LFR_HIP_TRY(stream_wait(st));
-            n_pairs = h_n[1];
-            h_pair.resize(n_pairs); h_sum.resize(n_pairs);
-            LFR_HIP_TRY(hipMemcpyAsync(h_pair.data(), key_u, 8 * n_pairs, hipMemcpyDeviceToHost, st));
-            LFR_HIP_TRY(hipMemcpyAsync(h_sum.data(), sim_u, 8 * n_pairs, hipMemcpyDeviceToHost, st));
-        }
-        LFR_HIP_TRY(hipMemcpyAsync(h_tcomp.data(), tcomp, 4 * (size_t)T, hipMemcpyDeviceToHost, st));
-        LFR_HIP_TRY(hipMemcpyAsync(h_tsize.data(), tsize, 4 * (size_t)T, hipMemcpyDeviceToHost, st));
-        LFR_HIP_TRY(stream_wait(st));
-        lap("cut: meta edges of the oversized components on the host");
-        {
-            // the pairs arrive sorted by (t, u); group them by component, keeping that order (what the host stage feeds the cut): a counting
-            // sort over the component ids (a std::stable_sort through two indirections was 2-3 ms of config 5's cut for 105 k pairs)
-            int32_t n_comp_ids = 0;
-            for (int64_t t = 0; t < T; ++t) n_comp_ids = std::max(n_comp_ids, h_tcomp[t] + 1);
-            std::vector<uint32_t> first((size_t)n_comp_ids + 1, 0u), order(n_pairs);
-            for (size_t k = 0; k < n_pairs; ++k) ++first[(size_t)h_tcomp[h_pair[k] >> 32] + 1];
-            for (int32_t c = 0; c < n_comp_ids; ++c) first[c + 1] += first[c];
-            {
-                std::vector<uint32_t> next(first.begin(), first.end() - 1);
-                for (size_t k = 0; k < n_pairs; ++k) order[next[h_tcomp[h_pair[k] >> 32]]++] = (uint32_t)k;
-            }
-            std::vector<int64_t> tsize64((size_t)T);
-            for (int64_t t = 0; t < T; ++t) tsize64[t] = h_tsize[t];
-            std::vector<std::pair<int, int>> e;
-            std::vector<int> w;
-            for (int32_t c = 0; c < n_comp_ids; ++c) {
-                const size_t lo = first[c], hi = first[c + 1];
-                if (hi == lo) continue;
-                e.clear(); w.clear();
-                e.reserve(hi - lo); w.reserve(hi - lo);
-                for (size_t q = lo; q < hi; ++q) {
-                    const unsigned long long key = h_pair[order[q]];
-                    e.push_back({(int)(key >> 32), (int)(key & 0xffffffffull)});
-                    w.push_back(static_cast<int>(100 * h_sum[order[q]]));          // solve.cc:329
-                }
-                const auto split = recursive_cut(e, w, tsize64, max_nodes);
-                for (auto &it : split) h_gc[it.first] = it.second;
-            }
-            lap("cut: recursive bisection");
-            // (an oversized component without any meta edge is a single track: nothing to cut, it stays whole)
-            p.stats.n_cut_components = 0;
-            {   // count the components above the cap the way the host stage does (with or without meta edges)
-                std::vector<int64_t> csz;
-                for (int64_t t = 0; t < T; ++t) { if ((size_t)h_tcomp[t] >= csz.size()) csz.resize(h_tcomp[t] + 1, 0); csz[h_tcomp[t]] += h_tsize[t]; }
-                for (int64_t c : csz) if (c > max_nodes) ++p.stats.n_cut_components;
-            }
-        }
-        LFR_HIP_TRY(hipMemcpyAsync(gc_dev, h_gc.data(), 4 * (size_t)T, hipMemcpyHostToDevice, st));
-        // drop the cut edges and re-label (solve.cc:345-372), same kernels as the first labelling
-        hipLaunchKernelGGL(k_iota, grid_for(N), dim3(kThreads), 0, st, N, mp_parent);
-        hipLaunchKernelGGL(k_meta_union_cut, grid_for(M), dim3(kThreads), 0, st, M, n1, n2, dp->track, gc_dev, mp_parent);
-        hipLaunchKernelGGL(k_cc_labels, grid_for(N), dim3(kThreads), 0, st, N, mp_parent, mp);
-        LFR_HIP_TRY(hipMemsetAsync(cflag, 0, 4 * (size_t)(N + 1), st));
-        LFR_HIP_TRY(hipMemsetAsync(csize, 0, 4 * (size_t)N, st));
-        LFR_HIP_TRY(hipMemsetAsync(counts + CNT_MAX_COMP, 0, 4, st));
-        hipLaunchKernelGGL(k_comp_flags, grid_for(N), dim3(kThreads), 0, st, N, counts, mp, cflag);
-        if ((rc = exclusive_sum(arena, cflag, crank, N + 1, st)) != LFR_OK) return rc;
-        hipLaunchKernelGGL(k_comp_sizes, grid_few(N), dim3(kThreads), 0, st, N, counts, mp, crank, tsize, csize);
-        hipLaunchKernelGGL(k_max_csize, grid_few(N), dim3(kThreads), 0, st, N, counts, csize);
-        hipLaunchKernelGGL(k_node_comp, grid_for(N), dim3(kThreads), 0, st, N, dp->track, mp, crank, dp->comp);
-        LFR_HIP_TRY(hipGetLastError());
-        LFR_HIP_TRY(hipEventRecord(c1, st));
-        LFR_HIP_TRY(hipMemcpyAsync(h_counts, counts, 4 * CNT_WORDS, hipMemcpyDeviceToHost, st));
-        LFR_HIP_TRY(stream_wait(st));          // (the staging vectors above die at scope end)
-        lap("cut: re-labelled");
-        p.stats.n_components = h_counts[CNT_COMPS]; p.stats.max_component_size = h_counts[CNT_MAX_COMP];
-    dp->max_cc_matches = h_counts[CNT_MAX_SEG];
-        float cms = 0.f;
-        LFR_HIP_TRY(hipEventElapsedTime(&cms, c0, c1));
-        p.stats.graph_cut_ms += cms;
-    }
-    return LFR_OK;
+    s.trace_fill_time();
+    if (s.has_large_components() && (rc = s.union_find_rounds()) != LFR_OK) return rc;
+    if ((rc = s.tracks_and_roots(order)) != LFR_OK) return rc;
+    if ((rc = s.label_components(false)) != LFR_OK) return rc;
+    s.lap("tracks / roots / components enqueued");
+    if ((rc = s.read_counts("final read-back")) != LFR_OK) return rc;      // the one read-back of the stage
+    s.debug_dump();
+    if ((int64_t)s.h_counts[CNT_MAX_COMP] > s.max_nodes && (rc = s.cut_oversized()) != LFR_OK) return rc;
+    return s.publish();
 }
 
 int graph_make_resident(const Graph &g, int device) {

@@ -204,6 +204,13 @@ void components_from_tracks(const Graph &g, const std::vector<int64_t> &track, i
 std::unordered_map<int, int> recursive_cut(const std::vector<std::pair<int, int>> &edges, const std::vector<int> &weights,
                                            const std::vector<int64_t> &node_weights, int64_t max_weight);
 
+// The host part of the DEVICE graph stage's cut (lfr_graphstage.hip: cut_oversized).  tcomp / tsize: component and size of every
+// track; pair / sum: the meta edges of the oversized components as keys (t << 32 | u), t < u, ascending, with the sums of their
+// similarities.  gc[t] = subset of track t after the recursive cut of its component (-1: not cut).  Returns the number of
+// components above the cap, counted the way components_from_tracks counts them (with or without meta edges).
+int64_t cut_components_from_pairs(const std::vector<int32_t> &tcomp, const std::vector<uint32_t> &tsize, const std::vector<unsigned long long> &pair,
+                                  const std::vector<double> &sum, int64_t max_nodes, std::vector<int32_t> &gc);
+
 // deterministic substitute for colmap::ComputeNormalizedMinGraphCut(edges, weights, 2)
 // (solve.cc:192): returns part (0/1) per node id appearing in `edges`.
 void bisect_graph(const std::vector<std::pair<int, int>> &edges, const std::vector<int> &weights,
