@@ -6,6 +6,7 @@ import pytest
 
 import lfr_oracle as O
 from lfr_amd import capi, synthetic
+from lm_decision_cases import kernel_class          # the class-by-rows rule, in one place
 
 pytestmark = pytest.mark.gpu
 TOL_UNITS = 6.25e-6
@@ -192,9 +193,7 @@ def test_every_kernel_class_is_exercised(lfr_lib):
         info = b.component_info()
         rows, edges = 2 * info["n_var_nodes"], info["n_edges"]
         for r, e in zip(rows, edges):
-            cls = ("G8" if r <= 8 and e <= 24 else "G16" if r <= 16 and e <= 48 else "G16_streamed" if r <= 16 and e <= 96 else
-                   "G64_2" if r <= 24 and e <= 192 else "G64_4" if r <= 32 and e <= 320 else "BLOCK_S" if r <= 88 else "BLOCK_M" if r <= 130 else "BLOCK_L" if r <= 192 else "GLOBAL")
-            seen.add(cls)
+            seen.add(kernel_class(r, e))
     assert seen == {"G8", "G16", "G16_streamed", "G64_2", "G64_4", "BLOCK_S", "BLOCK_M", "BLOCK_L", "GLOBAL"}, seen   # every kernel path, resident and re-read slots
 
 
