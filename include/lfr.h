@@ -16,7 +16,13 @@
  *   - similarity < 0, +-inf or NaN, or a flow entry that is not finite, makes the evaluation of ITS component non-finite: no LM
  *     step of that component is ever valid, it terminates LFR_TERM_FAILURE after ten invalid steps and keeps zero displacements
  *     (Ceres: a non-finite evaluation fails, IsSolutionUsable() is false and solve.cc:609-612 left the positions at 0).  Every other
- *     component - also one packed into the same wavefront - is solved exactly as if the bad match were not there;
+ *     component - also one packed into the same wavefront - is solved exactly as if the bad match were not there.
+ *     One difference from Ceres in the packed classes (components of up to 32 rows): their first evaluation, at the origin, reads
+ *     only the centre of the 3 x 3 flow grid and its four neighbours (entries 2, 3, 6..11, 14, 15 of the 18).  A non-finite value
+ *     in one of the eight corner entries (0, 1, 4, 5, 12, 13, 16, 17) is seen one evaluation later: the first step is taken, the
+ *     re-evaluation fails the component.  Termination and the zero displacements are the same; the component reports one iteration
+ *     more than Ceres, and more evaluations.  (Seeing it at once costs the solve more than it is worth: tests/
+ *     test_gpu_undefined_inputs.py pins exactly this);
  *   - a NaN similarity additionally leaves the order-dependent graph stage (tracks and roots sort by similarity, solve.cc:489-582)
  *     undefined in the reference itself; the library never emits a non-finite displacement, but which node of a tie becomes a
  *     root may differ from a given Ceres build;

@@ -15,6 +15,7 @@ import numpy as np
 import pytest
 
 import lfr_oracle as O
+from class_limit_cases import tracks
 from lfr_amd import capi, synthetic
 
 pytestmark = pytest.mark.gpu
@@ -22,50 +23,6 @@ TOL_UNITS = 6.25e-6          # tests/test_gpu_parity.py
 
 # (on the CPU the oracle converges on all 60 components of this batch, rejects a step in 2 and contracts a step in 4)
 HARD = dict(seed=200, n_images=12, n_tracks=60, len_dist="uniform", len_lo=3, len_hi=6, sigma_p=0.7, sigma_noise=0.3, sigma_A=0.8)
-
-
-def tracks(seed, lengths, dups=(), wrong=(), sigma_p=0.15, sigma_noise=0.02, sigma_A=0.05):
-    """MatchArrays of complete tracks: track t has lengths[t] nodes, node i of every track in image i.  dups: (track, n) gives the first
-    n matches of the track twice; wrong: (track a, node i, track b, node j), i != j - a match the track stage cannot merge
-    (the joined component must not exceed the graph stage's size cap, the number of images: max(lengths))."""
-    rng = np.random.Generator(np.random.PCG64(seed))
-    n_images = max(lengths)
-    off = np.r_[0, np.cumsum(lengths)]
-    img = np.concatenate([np.arange(n) for n in lengths])
-    feat = np.concatenate([np.full(n, t) for t, n in enumerate(lengths)])      # feature index inside an image = track number
-    pos = np.clip(rng.normal(0.0, sigma_p, size=(off[-1], 2)), -0.45, 0.45)
-    a, b, bad = [], [], []
-    for t, n in enumerate(lengths):
-        iu, ju = np.triu_indices(n, k=1)
-        a += list(off[t] + iu); b += list(off[t] + ju); bad += [False] * iu.size
-        for (td, nd) in dups:
-            if td == t:
-                a += list(off[t] + iu[:nd]); b += list(off[t] + ju[:nd]); bad += [False] * nd
-    for (ta, i, tb, j) in wrong:
-        assert i < j
-        a.append(off[ta] + i); b.append(off[tb] + j); bad.append(True)
-    a, b, bad = np.array(a), np.array(b), np.array(bad)
-    M = a.size
-    grid = synthetic.GRID.astype(np.float32)
-
-    def flow(src, dst):
-        base = np.where(bad[:, None], rng.normal(0.0, 0.3, size=(M, 2)), pos[dst] - pos[src]).astype(np.float32)
-        A = rng.standard_normal(size=(M, 2, 2), dtype=np.float32) * np.float32(sigma_A)
-        out = rng.standard_normal(size=(M, 9, 2), dtype=np.float32) * np.float32(sigma_noise) + base[:, None, :]
-        out += A[:, None, :, 0] * grid[None, :, 0, None]
-        out += A[:, None, :, 1] * grid[None, :, 1, None]
-        return out
-
-    disp2, disp1 = flow(a, b), flow(b, a)
-    sim = rng.uniform(0.8, 1.0, size=M).astype(np.float32)
-    i1, i2 = img[a], img[b]
-    o = np.lexsort((np.arange(M), i2, i1))
-    a, b, i1, i2, sim, disp1, disp2 = a[o], b[o], i1[o], i2[o], sim[o], disp1[o], disp2[o]
-    key = i1 * n_images + i2
-    starts = np.nonzero(np.r_[True, key[1:] != key[:-1]])[0]
-    return synthetic.MatchArrays(["%06d.png" % i for i in range(n_images)], np.ones(n_images, np.float32),
-                                 i1[starts].astype(np.int32), i2[starts].astype(np.int32), np.r_[starts, M].astype(np.int64),
-                                 feat[a].astype(np.uint32), feat[b].astype(np.uint32), sim, disp1, disp2)
 
 
 # name: (MatchArrays, expected (variable nodes, directed edges) of its components, sorted)

@@ -147,3 +147,138 @@ def test_all_zero_flow_grids_at_config2_size(lfr_lib):
     _, st2, pos2, info2, ref2 = run_both(ms, True)
     assert (pos2 == 0).all() and (ref2["positions"] == 0).all()
     assert (ref2["infos"][info2["component"]]["iterations"] == info2["iterations"]).all()
+
+
+# the first evaluation of a solve in the packed classes takes eval_edge's origin shortcut, which reads 10 of the 18 flow values (the
+# centre of the grid and its four neighbours); the other 8, the corners, only the general form reads.  include/lfr.h, "Undefined
+# inputs": a non-finite corner is seen one evaluation later - the first step is taken, the re-evaluation fails the component: the same
+# termination and zeros, one iteration more than the oracle (Ceres).
+READ_AT_ORIGIN = (2, 3, 6, 7, 8, 9, 10, 11, 14, 15)
+_wave = {}
+
+
+def _check_flow_position(k, st, info, ref, r, st8, info8):
+    """iterations and evaluation counts of a batch whose component in row r holds a non-finite flow value at position k, as
+    include/lfr.h states them; st8, info8: the same batch with the value at position 8, which every evaluation reads"""
+    oi = ref["infos"][info["component"]]
+    ne = info["n_edges"].astype(np.int64)
+    others = np.arange(len(ne)) != r
+    assert (info["iterations"][others] == oi["iterations"][others]).all()
+    if k in READ_AT_ORIGIN:
+        assert info["iterations"][r] == oi["iterations"][r]
+        assert st["ref_jacobian_passes_edges"] == int((oi["n_jac_evals"] * ne).sum())
+        assert st["ref_cost_passes_edges"] == int((oi["n_cost_evals"] * ne).sum())
+        for f in ("component", "iterations", "termination", "n_var_nodes", "n_edges"):
+            assert np.array_equal(info[f], info8[f]), f
+        for f in ("n_converged", "n_failed", "sum_iterations", "ref_jacobian_passes_edges", "ref_cost_passes_edges"):
+            assert st[f] == st8[f], f
+    else:
+        assert info["iterations"][r] == oi["iterations"][r] + 1          # the first step is taken, the re-evaluation fails the component
+        assert st["ref_jacobian_passes_edges"] > int((oi["n_jac_evals"] * ne).sum())
+        for f in ("component", "termination", "n_var_nodes", "n_edges"):
+            assert np.array_equal(info[f], info8[f]), f
+        for f in ("n_converged", "n_failed"):
+            assert st[f] == st8[f], f
+
+
+def _k5_wave(k=None, value=None):
+    """Eight 8-row components (the `k5` shape of tests/class_limit_cases.py from eight seeds): one wave of the packed kernel.  With k:
+    flow value k of the first match of the fourth one (its edge node1 -> node2) set to `value`.  -> (MatchArrays, that match, batch
+    stats, positions, info, oracle result, component of the fourth), computed once per (k, value)"""
+    import class_limit_cases as CL
+    key = (k, None if value is None else str(value))
+    if key not in _wave:
+        ma, first = CL.merge([CL.part("k5", CL.SEED + 50 * i) for i in range(8)])
+        m = int(np.nonzero(ma.feat1 == first[3])[0][0])
+        if k is not None:
+            ma.disp2.reshape(-1, 18)[m, k] = value
+        p, st, pos, info, ref = run_both(ma, False)
+        victim = int(ref["comp"][np.nonzero(ref["node_feat"] == first[3])[0][0]])
+        _wave[key] = (ma, m, p, st, pos, info, ref, victim)
+    return _wave[key]
+
+
+@pytest.mark.parametrize("value", [np.inf, np.nan], ids=["inf", "nan"])
+@pytest.mark.parametrize("k", range(18))
+def test_non_finite_flow_at_every_grid_position(lfr_lib, k, value):
+    """include/lfr.h: a flow entry that is not finite fails its component with zero displacements, wherever it sits in the grid.
+    Against the oracle: termination and zero positions at all 18 positions; iterations and the batch's evaluation counts equal to the
+    oracle's at the ten positions the first evaluation reads and equal among them, one iteration more at the eight corners (the
+    contract's text); the seven components that share the wave bitwise what they are without the poison."""
+    _, _, p0, st0, pos0, info0, ref0, victim = _k5_wave()
+    assert st0["n_failed"] == 0 and st0["n_components"] == 8 and (info0["n_var_nodes"] == 4).all() and (info0["n_edges"] == 20).all()
+    ma, m, p, st, pos, info, ref, v = _k5_wave(k, value)
+    assert v == victim and not np.isfinite(ma.disp2.reshape(-1, 18)[m, k])
+    check_against_oracle(p, st, pos, info, ref)
+    comp = p.labels()[2]
+    r = int(np.nonzero(info["component"] == victim)[0][0])
+    oi = ref["infos"][info["component"]]
+    print("flow[%d] = %s: iterations %d (oracle %d), jacobian passes x edges %d (oracle %d), cost passes x edges %d (oracle %d)"
+          % (k, value, info["iterations"][r], oi["iterations"][r], st["ref_jacobian_passes_edges"], int((oi["n_jac_evals"] * info["n_edges"]).sum()),
+             st["ref_cost_passes_edges"], int((oi["n_cost_evals"] * info["n_edges"]).sum())))
+    assert st["n_failed"] == 1 and info["termination"][r] == oi["termination"][r] == capi.TERM_FAILURE
+    assert (pos[comp == victim] == 0).all() and (ref["positions"][comp == victim] == 0).all()
+    _, _, _, st8, pos8, info8, _, _ = _k5_wave(8, value)
+    _check_flow_position(k, st, info, ref, r, st8, info8)
+    # the seven neighbours in the wave: bitwise what they were
+    assert (pos[comp != victim] == pos0[comp != victim]).all() and pos0[comp != victim].any()
+    others = np.arange(8) != r
+    for f in ("iterations", "termination"):
+        assert np.array_equal(info[f][others], info0[f][others]), f
+    assert np.array_equal(info["final_cost"][others].view(np.uint64), info0["final_cost"][others].view(np.uint64))
+
+
+G16_WAVE = ("k7_first_reread", "k9_full", "k6", "k7_resident_full")      # four components of the 16-row class: one wave
+_wave16 = {}
+
+
+def _g16_wave(victim=None, k=None, value=None):
+    """The four shapes of G16_WAVE (tests/class_limit_cases.py).  With victim: flow value k of its LAST match's edge node2 -> node1 set
+    to `value` - the packed classes hold their records in edge order, so that is the component's last record, edge 49 of 50 or 95 of 96:
+    slot 3 or 5 of the 16-lane group, beyond the three resident slots, re-read from memory by every sweep."""
+    import class_limit_cases as CL
+    key = (victim, k, None if value is None else str(value))
+    if key not in _wave16:
+        ma, first = CL.merge([CL.part(n) for n in G16_WAVE])
+        feat = first[G16_WAVE.index(victim or G16_WAVE[0])]
+        m = int(np.nonzero(ma.feat1 == feat)[0][-1])
+        if victim is not None:
+            ma.disp1.reshape(-1, 18)[m, k] = value
+        p, st, pos, info, ref = run_both(ma, False)
+        c = int(ref["comp"][np.nonzero(ref["node_feat"] == feat)[0][0]])
+        _wave16[key] = (ma, m, p, st, pos, info, ref, c)
+    return _wave16[key]
+
+
+@pytest.mark.parametrize("value", [np.inf, np.nan], ids=["inf", "nan"])
+@pytest.mark.parametrize("k", range(18))
+@pytest.mark.parametrize("victim", G16_WAVE[:2])
+def test_non_finite_flow_in_a_reread_record(lfr_lib, victim, k, value):
+    """the same for a record the packed kernel does not keep in registers but re-reads in every sweep: the oracle's termination and
+    zeros at all 18 positions, iterations and evaluation counts as include/lfr.h states them, the three neighbours of the wave bitwise
+    unchanged."""
+    import class_limit_cases as CL
+    _, _, p0, st0, pos0, info0, ref0, _ = _g16_wave()
+    assert st0["n_failed"] == 0 and st0["n_components"] == 4
+    assert sorted(zip((2 * info0["n_var_nodes"]).tolist(), info0["n_edges"].tolist())) == sorted((CL.SHAPES[n]["rows"], CL.SHAPES[n]["edges"]) for n in G16_WAVE)
+    ma, m, p, st, pos, info, ref, c = _g16_wave(victim, k, value)
+    check_against_oracle(p, st, pos, info, ref)
+    comp = p.labels()[2]
+    r = int(np.nonzero(info["component"] == c)[0][0])
+    E = CL.SHAPES[victim]["edges"]
+    assert info["n_edges"][r] == E and (E - 1) // 16 >= 3          # the last record lies beyond the resident slots
+    # (it is the last record: no later match of the graph belongs to the component)
+    oi = ref["infos"][info["component"]]
+    ne = info["n_edges"].astype(np.int64)
+    print("%s flow[%d] = %s: iterations %d (oracle %d), jacobian passes x edges %d (oracle %d), cost passes x edges %d (oracle %d)"
+          % (victim, k, value, info["iterations"][r], oi["iterations"][r], st["ref_jacobian_passes_edges"], int((oi["n_jac_evals"] * ne).sum()),
+             st["ref_cost_passes_edges"], int((oi["n_cost_evals"] * ne).sum())))
+    assert st["n_failed"] == 1 and info["termination"][r] == oi["termination"][r] == capi.TERM_FAILURE
+    assert (pos[comp == c] == 0).all() and (ref["positions"][comp == c] == 0).all()
+    _, _, _, st8, _, info8, _, _ = _g16_wave(victim, 8, value)
+    _check_flow_position(k, st, info, ref, r, st8, info8)
+    assert (pos[comp != c] == pos0[comp != c]).all() and pos0[comp != c].any()
+    others = np.arange(4) != r
+    for f in ("iterations", "termination"):
+        assert np.array_equal(info[f][others], info0[f][others]), f
+    assert np.array_equal(info["final_cost"][others].view(np.uint64), info0["final_cost"][others].view(np.uint64))
