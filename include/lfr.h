@@ -342,11 +342,29 @@ typedef struct lfr_backward_stats {
 } lfr_backward_stats;
 
 #define LFR_BACKWARD_F64 1         /* outputs are double instead of float32 */
+/* Gauss-Newton mode (may be combined with LFR_BACKWARD_F64; any other bit: LFR_ERR_ARG).  The contract above with one change:
+ *   - H = J^T J over the free coordinates at x^, J the loss-corrected Jacobian of the component's kept directed edges (corrector
+ *     sqrt(rho'), the similarity as the loss scale, the interpolant's derivative zeroed outside [-0.5, 0.5]): per edge
+ *     w rho' [[P^T P, -P^T], [-P, I]], P = I + df/dx_src - no rho'' term, no second derivatives of the interpolant.  It is the matrix
+ *     of the LM loop and of lfr_batch_covariance, but the bounds are honoured as in the exact mode: coordinates with |x^| >= 1, roots
+ *     and constant nodes are constant (identity rows and columns, zero right-hand side);
+ *   - v = H^-1 ubar, and the vector-Jacobian sweep -d/dtheta_e [v . grad F_e(x^; theta_e)] is the EXACT one above (it keeps its rho''
+ *     and mixed-derivative terms): only H changes.
+ * The result is the implicit gradient under the Gauss-Newton approximation of the Hessian; it equals the exact one where the
+ * residuals vanish.  J^T J is positive definite for every connected component that has a root and positive weights, so components
+ * whose exact Hessian is indefinite (where the robust loss is at work) get a gradient.  Status codes and lfr_backward_stats keep their
+ * numbers and fields: status 2 / n_indefinite now mean SINGULAR (a pivot was not positive: a node tied in only by edges of weight 0
+ * or by saturated Tukey edges), again with a zero gradient.  Outputs are bitwise repeatable from call to call, float32 is the float64
+ * result rounded once, and host- and device-assembled batches give identical results, as in the exact mode.
+ * Kernels: the classes of up to 32 rows run ONE launch in the covariance's packed layout (2-8 components per wave64, J^T J inverted in
+ * registers, v = C ubar); the workgroup classes run the exact mode's kernel with the Gauss-Newton assembly. */
+#define LFR_BACKWARD_GAUSS_NEWTON 2
 
 /* Stream-ordered device copy of the latest solve's positions (2 * n_nodes doubles of the whole graph; nodes outside the shard: 0). */
 int lfr_batch_positions_to_device(lfr_batch *b, double *dst_device, void *hip_stream);
 /* The gradient above.  grad_positions_device: 2 * n_nodes doubles (dL/dx of the whole graph); grad_disp1/2_device: n_matches x 18,
- * grad_sim_device: n_matches, float32 (double with LFR_BACKWARD_F64); whole arrays are overwritten.  Runs on `hip_stream` after the
+ * grad_sim_device: n_matches, float32 (double with LFR_BACKWARD_F64); whole arrays are overwritten.  flags: LFR_BACKWARD_F64 and / or
+ * LFR_BACKWARD_GAUSS_NEWTON (0: the exact Hessian, float32 outputs); any other bit: LFR_ERR_ARG.  Runs on `hip_stream` after the
  * latest solve; asynchronous unless stats != NULL.  LFR_ERR_ARG before the first solve, and between an lfr_batch_set_inputs and the
  * next solve.  The first call sets up its workspace and, for batches whose records do not carry their directed-edge ids, maps records to
  * edges from the graph (which must still be alive; lfr_batch_set_inputs shares the map). */

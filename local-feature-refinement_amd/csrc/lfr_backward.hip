@@ -11,6 +11,13 @@
 //      marks the component indefinite: its gradient stays zero;
 //   3. the vector-Jacobian sweep: one thread per record writes -d/dtheta_e [v . grad F_e] into the match layout of the graph.
 // The packed lower triangle of H lives in LDS for the classes of up to 192 rows (<= 148 KB) and in an HBM workspace above.
+//
+// Gauss-Newton mode (LFR_BACKWARD_GAUSS_NEWTON): H = J^T J of the loss-corrected Jacobian over the free coordinates - the matrix of the LM
+// loop and of the covariance, positive definite wherever the exact Hessian is not - and everything else as above.  The workgroup
+// classes run the same kernel with the other assembly; the packed classes (<= 32 rows) run backward_gn_packed_kernel: ONE launch in
+// the covariance's layout (lfr_packed_normal_device.hpp: 64/S components per wave64, one-wave workgroups, no barriers), its sweep and
+// its in-register inversion with the bound rows and columns replaced by the identity's, v = C ubar as one dot product per lane, then the
+// vector-Jacobian sweep over the re-read records.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -18,15 +25,46 @@
 
 #include "lfr_batch.hpp"
 #include "lfr_hessian_device.hpp"
+#include "lfr_packed_normal_device.hpp"
 
 using namespace lfrdev;
+using lfr::PackedRanges;
 
 namespace {
 
-constexpr int kBwdThreadsSmall = 64;         // packed classes (<= 32 rows): one wave per component
+constexpr int kBwdThreadsSmall = 64;         // exact mode, packed classes (<= 32 rows): one wave per component (Gauss-Newton mode: backward_gn_packed_kernel)
 constexpr int kBwdThreads = 256;             // workgroup classes
 
-template <int T, bool LDS_MATRIX>
+// The vector-Jacobian sweep of one record: -d/dtheta_e [v . grad F_e(x^; theta_e)] to the edge's match row and its directed-edge slot
+// of dL/dsim.  (xs, xd), (vs, vd): x^ and v = H^-1 ubar at the record's source and destination (0 for constants); id: its directed edge.
+__device__ __forceinline__ void bwd_sweep_edge(const BwdArgs &a, const EdgeRec &e, const int kind, const double xs0, const double xs1,
+                                               const double xd0, const double xd1, const double vs0, const double vs1, const double vd0,
+                                               const double vd1, const uint32_t id) {
+    BwdEdge o;
+    bwd_eval(e, kind, a.tukey_variant, xs0, xs1, xd0, xd1, o);
+    const double a0 = vd0 - (1.0 + o.fr[0]) * vs0 - o.fc[0] * vs1;      // a = J v = v_dst - P v_src
+    const double a1 = vd1 - o.fr[1] * vs0 - (1.0 + o.fc[1]) * vs1;
+    const double ra = o.r[0] * a0 + o.r[1] * a1;
+    if ((id >> 1) >= a.n_matches) return;                 // (cannot happen: every record maps to an edge of the graph)
+    const size_t row = 18 * (size_t)(id >> 1);
+    void *out = (id & 1u) ? a.g_disp1 : a.g_disp2;
+    a.g_sim_dir[id] = -o.rho1 * ra;
+    const double q2 = 2.0 * o.w * o.rho2 * ra, q1 = o.w * o.rho1;
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+            const double A = o.lr[i] * o.lc[j], B = o.dlr[i] * o.lc[j] * vs0 + o.lr[i] * o.dlc[j] * vs1;
+            const double g0 = q2 * o.r[0] * A + q1 * (A * a0 + o.r[0] * B);
+            const double g1 = q2 * o.r[1] * A + q1 * (A * a1 + o.r[1] * B);
+            const size_t at = row + 2 * (3 * i + j);
+            if (a.f64) { static_cast<double *>(out)[at] = g0; static_cast<double *>(out)[at + 1] = g1; }
+            else { static_cast<float *>(out)[at] = (float)g0; static_cast<float *>(out)[at + 1] = (float)g1; }
+        }
+}
+
+// GN: H is the loss-corrected Gauss-Newton matrix (bwd_assemble<T, false, true>) instead of the exact Hessian
+template <int T, bool LDS_MATRIX, bool GN>
 __global__ __launch_bounds__(T) void backward_kernel(const BwdArgs a) {
     extern __shared__ double bsh[];
     const int di = a.desc_begin + blockIdx.x, tid = threadIdx.x;
@@ -62,7 +100,7 @@ __global__ __launch_bounds__(T) void backward_kernel(const BwdArgs a) {
 
     // 2. assembly (owner computes, deterministic)
     auto xof = [&](int m, int c) -> double { return m < nv ? a.positions[2 * (size_t)ids[m] + c] : 0.0; };
-    bwd_assemble<T, true>(a, d, nv, E, ids, H, fr, tid);
+    bwd_assemble<T, !GN, true>(a, d, nv, E, ids, H, fr, tid);
     __syncthreads();
 
     // 3. LDL^T over the nonzeros of each column
@@ -91,30 +129,104 @@ __global__ __launch_bounds__(T) void backward_kernel(const BwdArgs a) {
         const int s = e.src, m = e.dst_kind & 0x7fff, kind = e.dst_kind >> 15;
         const double vs0 = s < nv ? v[2 * s] : 0., vs1 = s < nv ? v[2 * s + 1] : 0.;
         const double vd0 = m < nv ? v[2 * m] : 0., vd1 = m < nv ? v[2 * m + 1] : 0.;
-        BwdEdge o;
-        bwd_eval(e, kind, a.tukey_variant, xof(s, 0), xof(s, 1), xof(m, 0), xof(m, 1), o);
-        const double a0 = vd0 - (1.0 + o.fr[0]) * vs0 - o.fc[0] * vs1;      // a = J v = v_dst - P v_src
-        const double a1 = vd1 - o.fr[1] * vs0 - (1.0 + o.fc[1]) * vs1;
-        const double ra = o.r[0] * a0 + o.r[1] * a1;
-        const uint32_t id = a.eid[d.edge_off + p];
-        if ((id >> 1) >= a.n_matches) continue;               // (cannot happen: every record maps to an edge of the graph)
-        const size_t row = 18 * (size_t)(id >> 1);
-        void *out = (id & 1u) ? a.g_disp1 : a.g_disp2;
-        a.g_sim_dir[id] = -o.rho1 * ra;
-        const double q2 = 2.0 * o.w * o.rho2 * ra, q1 = o.w * o.rho1;
-#pragma unroll
-        for (int i = 0; i < 3; ++i)
-#pragma unroll
-            for (int j = 0; j < 3; ++j) {
-                const double A = o.lr[i] * o.lc[j], B = o.dlr[i] * o.lc[j] * vs0 + o.lr[i] * o.dlc[j] * vs1;
-                const double g0 = q2 * o.r[0] * A + q1 * (A * a0 + o.r[0] * B);
-                const double g1 = q2 * o.r[1] * A + q1 * (A * a1 + o.r[1] * B);
-                const size_t at = row + 2 * (3 * i + j);
-                if (a.f64) { static_cast<double *>(out)[at] = g0; static_cast<double *>(out)[at + 1] = g1; }
-                else { static_cast<float *>(out)[at] = (float)g0; static_cast<float *>(out)[at + 1] = (float)g1; }
-            }
+        bwd_sweep_edge(a, e, kind, xof(s, 0), xof(s, 1), xof(m, 0), xof(m, 1), vs0, vs1, vd0, vd1, a.eid[d.edge_off + p]);
     }
     if (tid == 0) a.status[di] = 0;
+}
+
+// ---- Gauss-Newton mode, packed classes (<= 32 rows): the covariance's layout (lfr_packed_normal_device.hpp) ----
+template <int NV>
+struct alignas(16) BwdGnLds {
+    CovLds<NV> c;              // J^T J and x^
+    double u[NV];              // ubar of the free coordinates, 0 elsewhere
+    double v[NV + 2];          // v = H^-1 ubar; slots 2*n_var, 2*n_var+1 stay 0 (constants)
+};
+
+template <int CLS, int EPL>
+__device__ __forceinline__ void bwd_gn_group_body(const BwdArgs &a, const int desc_begin, const int desc_end, const int block_in_class,
+                                                  unsigned char *lds_raw) {
+    constexpr int NV = CLS == 0 ? 8 : CLS == 1 ? 16 : 32, LPR = CLS == 3 ? 2 : 1;
+    constexpr int S = NV * LPR, G = 64 / S, LD = NV + 1;
+    const int lane = threadIdx.x & 63;
+    const int gid = lane / S, sl = lane % S;
+    const int row = sl % NV, part = sl / NV;
+    const int ci0 = desc_begin + block_in_class * G;
+    if (ci0 >= desc_end) return;                      // wave-uniform
+    const int ci = ci0 + gid;
+    const bool have = ci < desc_end;
+    BwdGnLds<NV> &B = reinterpret_cast<BwdGnLds<NV> *>(lds_raw)[gid];
+    CovLds<NV> &L = B.c;
+
+    CompDesc d;
+    d.edge_off = 0; d.n_edges = 0; d.node_off = 0; d.n_nodes = 0; d.n_var = 0;
+    if (have) d = a.descs[ci];
+    const bool usable = have && a.infos[ci].termination != LFR_TERM_FAILURE;
+    const int n_var = usable ? d.n_var : 0, nv2 = 2 * n_var, E = usable ? (int)d.n_edges : 0;     // a group without a usable component inverts the identity
+    const bool is_row = row < nv2;
+    const int nv2_max = cov_wave_max(nv2);
+
+    // the lane's coordinate: bound (|x^| >= 1) or free, its dL/dx; the group's bound rows as a mask (bit = row)
+    const size_t coord = is_row ? 2 * (size_t)a.node_ids[d.node_off + (row >> 1)] + (row & 1) : 0;
+    const bool bound = is_row && !(fabs(a.positions[coord]) < kBound);
+    const uint32_t bmask = (uint32_t)(__builtin_amdgcn_ballot_w64(bound) >> (gid * S)) & (NV == 32 ? 0xffffffffu : (1u << NV) - 1u);
+    if (sl == 0 && bmask) atomicAdd(a.counters, (unsigned long long)__popc(bmask));       // (once per coordinate: the low half of <32,2>)
+    if (part == 0) B.u[row] = (is_row && !bound) ? a.grad_pos[coord] : 0.0;
+    if (sl < 2) B.v[NV + sl] = 0.0;
+    cov_lds_init<NV, S>(a, d, n_var, sl, L);
+    wave_lds_sync();
+    cov_assemble<NV, S, EPL, false>(a, d, n_var, E, sl, L);      // J^T J at x^, the covariance's sweep
+    wave_lds_sync();
+
+    // ---- inversion with the bound rows and columns the identity's, lane = row; v = C ubar ----
+    const double *A = L.A;
+    bool solved = false;
+    cov_invert<CLS>(row, nv2_max,
+        [&](int c) -> double {
+            double h = 0.0;
+            if (is_row && c < nv2) h = (c <= row ? A[row * LD + c] : A[c * LD + row]);
+            const bool fixed = !is_row || bound || ((bmask >> c) & 1u);       // padded and bound rows are identity
+            return fixed ? (c == row ? 1.0 : 0.0) : h;
+        },
+        [&](auto &h, const bool ok) {
+            constexpr int CL = sizeof(h) / sizeof(double);
+            double acc = 0.0;
+#pragma unroll
+            for (int c = 0; c < CL; ++c) acc = fma(h[c], B.u[c], acc);
+            if (part == 0) B.v[row] = is_row ? acc : 0.0;
+            // cov_invert's test (the smallest pivot > 0) lets a NaN pivot pass; bwd_ldlt rejects one.  A NaN or infinite pivot leaves a
+            // v that is not finite, so the group's v decides with it: status 2 means the same in every launch class
+            const unsigned long long bad = __builtin_amdgcn_ballot_w64(is_row && !isfinite(acc));       // (every lane is active here)
+            constexpr unsigned long long kGroup = S == 64 ? ~0ull : (1ull << S) - 1ull;
+            solved = ok && !((bad >> (gid * S)) & kGroup);
+        });
+    if (have && sl == 0) a.status[ci] = !usable ? 1 : solved ? 0 : 2;
+    wave_lds_sync();
+    if (!solved) return;                              // a pivot was not positive: zero gradient (the outputs were cleared)
+
+    // ---- vector-Jacobian sweep over the re-read records ----
+    const EdgeRec *R = a.edges + d.edge_off;
+    const uint32_t *eid = a.eid + d.edge_off;
+#pragma unroll 1
+    for (int p = sl; p < E; p += S) {
+        const EdgeRec e = R[p];
+        const int s = min((int)e.src, n_var), m = min((int)(e.dst_kind & 0x7fff), n_var), kind = e.dst_kind >> 15;     // constants read the zero slots
+        bwd_sweep_edge(a, e, kind, L.x[2 * s], L.x[2 * s + 1], L.x[2 * m], L.x[2 * m + 1], B.v[2 * s], B.v[2 * s + 1], B.v[2 * m],
+                       B.v[2 * m + 1], eid[p]);
+    }
+}
+
+constexpr size_t kBwdGnLdsBytes = 4 * sizeof(BwdGnLds<16>) > 2 * sizeof(BwdGnLds<32>) ? 4 * sizeof(BwdGnLds<16>) : 2 * sizeof(BwdGnLds<32>);
+static_assert(kBwdGnLdsBytes >= 8 * sizeof(BwdGnLds<8>), "LDS budget");
+
+// all packed classes in ONE launch, the blocks dealt to the classes as in covariance_packed_kernel
+__global__ __launch_bounds__(64, 2) void backward_gn_packed_kernel(const BwdArgs a, const PackedRanges r) {
+    __shared__ __attribute__((aligned(16))) unsigned char lds_raw[kBwdGnLdsBytes];
+    const int b = (int)blockIdx.x;
+    if (b < r.blk_begin[1]) bwd_gn_group_body<3, 5>(a, r.desc_begin[0], r.desc_end[0], b - r.blk_begin[0], lds_raw);
+    else if (b < r.blk_begin[2]) bwd_gn_group_body<2, 6>(a, r.desc_begin[1], r.desc_end[1], b - r.blk_begin[1], lds_raw);
+    else if (b < r.blk_begin[3]) { /* retired class, never assigned */ }
+    else if (b < r.blk_begin[4]) bwd_gn_group_body<1, 6>(a, r.desc_begin[3], r.desc_end[3], b - r.blk_begin[3], lds_raw);
+    else bwd_gn_group_body<0, 3>(a, r.desc_begin[4], r.desc_end[4], b - r.blk_begin[4], lds_raw);
 }
 
 __global__ void k_bwd_sim(int64_t n_matches, const double *dir, void *out, int f64) {
@@ -141,10 +253,11 @@ int bwd_setup_extra(lfr_batch *b, lfr::PassState *ps) {
     s->d_gsim = s->slab.take_n<double>(2 * (size_t)std::max<int64_t>(b->n_graph_matches, 1));
     s->d_counters = s->slab.take_n<unsigned long long>(8);
     if (!s->d_gsim || !s->d_counters) { lfr::set_error("backward slab exhausted"); return LFR_ERR_NOMEM; }
-    HIP_TRY(hipFuncSetAttribute((const void *)backward_kernel<kBwdThreads, true>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)bwd_lds_bytes(lfr::kBlockMaxRows, true)));
-    HIP_TRY(hipFuncSetAttribute((const void *)backward_kernel<kBwdThreads, false>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)bwd_lds_bytes(kBwdMaxRows, false)));
+    const int lds_block = (int)bwd_lds_bytes(lfr::kBlockMaxRows, true), lds_global = (int)bwd_lds_bytes(kBwdMaxRows, false);
+    HIP_TRY(hipFuncSetAttribute((const void *)backward_kernel<kBwdThreads, true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_block));
+    HIP_TRY(hipFuncSetAttribute((const void *)backward_kernel<kBwdThreads, false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_global));
+    HIP_TRY(hipFuncSetAttribute((const void *)backward_kernel<kBwdThreads, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_block));
+    HIP_TRY(hipFuncSetAttribute((const void *)backward_kernel<kBwdThreads, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_global));
     return LFR_OK;
 }
 
@@ -165,11 +278,12 @@ int lfr_batch_positions_to_device(lfr_batch *b, double *dst_device, void *hip_st
 
 int lfr_batch_backward(lfr_batch *b, const double *grad_positions_device, void *grad_disp1_device, void *grad_disp2_device,
                        void *grad_sim_device, int flags, void *hip_stream, lfr_backward_stats *stats) {
-    if (!b || !grad_positions_device || !grad_disp1_device || !grad_disp2_device || !grad_sim_device || (flags & ~LFR_BACKWARD_F64)) {
+    if (!b || !grad_positions_device || !grad_disp1_device || !grad_disp2_device || !grad_sim_device || (flags & ~(LFR_BACKWARD_F64 | LFR_BACKWARD_GAUSS_NEWTON))) {
         lfr::set_error("bad argument"); return LFR_ERR_ARG;
     }
     hipStream_t st = (hipStream_t)hip_stream;
     const int f64 = (flags & LFR_BACKWARD_F64) ? 1 : 0;
+    const bool gn = (flags & LFR_BACKWARD_GAUSS_NEWTON) != 0;
     const size_t M = (size_t)b->n_graph_matches, elt = f64 ? 8 : 4;
     { const int rc = lfr::pass_begin(b, &b->bwd, kBackward, 16 * std::max<size_t>(M, 1) + 64, st); if (rc != LFR_OK) return rc; }
     BwdState &s = *static_cast<BwdState *>(b->bwd);
@@ -187,23 +301,33 @@ int lfr_batch_backward(lfr_batch *b, const double *grad_positions_device, void *
     a.hws = s.d_hws; a.hws_off = s.d_hws_off; a.g_disp1 = grad_disp1_device; a.g_disp2 = grad_disp2_device; a.g_sim_dir = s.d_gsim;
     a.status = s.d_status; a.counters = s.d_counters; a.tukey_variant = b->tukey_variant; a.f64 = f64;
     a.n_matches = (uint32_t)M;
-    // packed classes (<= 32 rows): one wave each; LDS classes: 256 threads, matrix in LDS; above 192 rows: matrix in HBM
-    {
+    // Packed classes (<= 32 rows).  Gauss-Newton mode: ONE launch of one-wave blocks, each wave hosting 64/S = 2-8 components (1 in
+    // <32,2>), dealt to the classes as lfr_batch_covariance deals its own.  Exact mode: backward_kernel, one wave per component.
+    if (gn) {
+        PackedRanges r;
+        int nb = 0;
+        lfr::packed_ranges(b, 1, &r, &nb);
+        a.desc_begin = b->class_begin[0]; a.scan_all = 0;
+        if (nb > 0) hipLaunchKernelGGL(backward_gn_packed_kernel, dim3(nb), dim3(64), 0, st, a, r);
+    } else {
         a.desc_begin = b->class_begin[0];
         const int n = b->class_begin[lfr::KC_BLOCK] - a.desc_begin;
         a.scan_all = 1;
         if (n > 0)
-            hipLaunchKernelGGL((backward_kernel<kBwdThreadsSmall, true>), dim3(n), dim3(kBwdThreadsSmall), bwd_lds_bytes(32, true), st, a);
+            hipLaunchKernelGGL((backward_kernel<kBwdThreadsSmall, true, false>), dim3(n), dim3(kBwdThreadsSmall), bwd_lds_bytes(32, true), st, a);
     }
+    // Workgroup classes, both modes: one workgroup of 256 threads per component; matrix in LDS up to 192 rows, in HBM above
     a.scan_all = 0;
     for (int cls = lfr::KC_BLOCK; cls < lfr::KC_COUNT; ++cls) {
         a.desc_begin = b->class_begin[cls];
         const int n = b->class_begin[cls + 1] - a.desc_begin, rows = std::max(s.rows_max[cls], 2);
         if (n <= 0) continue;
-        if (cls == lfr::KC_GLOBAL)
-            hipLaunchKernelGGL((backward_kernel<kBwdThreads, false>), dim3(n), dim3(kBwdThreads), bwd_lds_bytes(rows, false), st, a);
-        else
-            hipLaunchKernelGGL((backward_kernel<kBwdThreads, true>), dim3(n), dim3(kBwdThreads), bwd_lds_bytes(rows, true), st, a);
+        const bool lds_matrix = cls != lfr::KC_GLOBAL;
+        const size_t lds = bwd_lds_bytes(rows, lds_matrix);
+        if (!lds_matrix && gn) hipLaunchKernelGGL((backward_kernel<kBwdThreads, false, true>), dim3(n), dim3(kBwdThreads), lds, st, a);
+        else if (!lds_matrix) hipLaunchKernelGGL((backward_kernel<kBwdThreads, false, false>), dim3(n), dim3(kBwdThreads), lds, st, a);
+        else if (gn) hipLaunchKernelGGL((backward_kernel<kBwdThreads, true, true>), dim3(n), dim3(kBwdThreads), lds, st, a);
+        else hipLaunchKernelGGL((backward_kernel<kBwdThreads, true, false>), dim3(n), dim3(kBwdThreads), lds, st, a);
     }
     if (M) hipLaunchKernelGGL(k_bwd_sim, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, st, (int64_t)M, s.d_gsim, grad_sim_device, f64);
     HIP_TRY(hipGetLastError());

@@ -102,9 +102,10 @@ __host__ __device__ __forceinline__ size_t bwd_tri(int i, int j) { return (size_
 
 // The matrix of a component's normal equations, lower triangle, owner computes: the thread of node l owns rows 2l, 2l+1 (columns of
 // nodes <= l) and sums them over the node's out- and in-edges in record order.  EXACT: the backward's Hessian (rho'' and the
-// interpolant's second derivatives included; coordinates with fr[i] == 0 become identity rows and columns); otherwise the loss-corrected
-// Gauss-Newton matrix J^T J = sum_e w rho' [[P^T P, -P^T], [-P, I]] of the covariance (lfr_covariance.hip), which ignores the bounds.
-template <int T, bool EXACT>
+// interpolant's second derivatives included); otherwise the loss-corrected Gauss-Newton matrix J^T J = sum_e w rho' [[P^T P, -P^T],
+// [-P, I]].  BOUNDS: coordinates with fr[i] == 0 become identity rows and columns (both modes of the backward); without it fr is not
+// read (the covariance, lfr_covariance.hip, ignores the bounds).
+template <int T, bool EXACT, bool BOUNDS = EXACT>
 __device__ __forceinline__ void bwd_assemble(const BwdArgs &a, const CompDesc &d, const int nv, const EdgeRec *E, const uint32_t *ids,
                                              double *H, const uint8_t *fr, const int tid) {
     // The workgroup classes' records come by source node (out-edges contiguous, NodeInc); the packed classes' in edge-id order: a thread scans them all (<= 320)
@@ -176,7 +177,7 @@ __device__ __forceinline__ void bwd_assemble(const BwdArgs &a, const CompDesc &d
             }
         }
         H[bwd_tri(2 * l, 2 * l)] += hd[0]; H[bwd_tri(2 * l + 1, 2 * l)] += hd[1]; H[bwd_tri(2 * l + 1, 2 * l + 1)] += hd[2];
-        if constexpr (EXACT)
+        if constexpr (BOUNDS)
             for (int p = 0; p < 2; ++p) {                     // bound coordinates: identity rows and columns
                 const int i = 2 * l + p;
                 for (int j = 0; j <= i; ++j)

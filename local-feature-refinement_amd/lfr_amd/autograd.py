@@ -13,6 +13,9 @@ assembly ONCE and gives every later forward new flows (and similarities) into th
         pos = r(disp1, disp2)           # set_inputs + solve + positions on torch's current stream, no host synchronisation
         loss(pos).backward()
 
+hessian="gauss_newton" (refine and Refiner) takes the implicit gradient with H = J^T J instead of the exact Hessian
+(LFR_BACKWARD_GAUSS_NEWTON): components whose exact Hessian is indefinite - zero gradient in the default mode - get one too.
+
 One device, first-order only (the backward is not itself differentiable).  The graph stage (tracks, roots, components, the cut) is
 discrete and the box's active set piecewise constant: the gradient holds them fixed.
 """
@@ -22,6 +25,15 @@ from torch.autograd.function import once_differentiable
 
 from . import capi
 from .synthetic import MatchArrays
+
+
+_HESSIANS = ("exact", "gauss_newton")
+
+
+def _check_hessian(who, hessian):
+    if hessian not in _HESSIANS:
+        raise ValueError("%s: hessian must be one of %s, got %r" % (who, ", ".join(map(repr, _HESSIANS)), hessian))
+    return hessian == "gauss_newton"
 
 
 def _kept_rows(pair_img1, pair_img2, pair_off, image_names, banned):
@@ -69,7 +81,7 @@ class _Refine(torch.autograd.Function):
         s1, s2, ss, t1, t2, ts = ctx.n_in
         if grad_pos is None:
             return None, None, None, None
-        g1, g2, gs = b.backward(grad_pos, f64=False)
+        g1, g2, gs = b.backward(grad_pos, f64=False, gauss_newton=meta["gauss_newton"])
         rows = meta["kept_rows"]
         if rows is not None:        # back to the caller's rows (matches of banned pairs get 0)
             idx = torch.as_tensor(rows, device=g1.device)
@@ -84,7 +96,7 @@ class _Refine(torch.autograd.Function):
 
 
 def refine(disp1, disp2, sim, *, image_names, pair_img1, pair_img2, pair_off, feat1, feat2, image_facts=None, banned=(),
-           tukey_variant="ceres1", return_covariance=False):
+           tukey_variant="ceres1", return_covariance=False, hessian="exact"):
     """Multi-view refinement of the matches as a differentiable function of the flows and similarities.
 
     disp1, disp2: [n_matches, 18] (or [n_matches, 9, 2]) float32 tensors on one HIP device - disp2 = flow image1 -> image2, disp1 =
@@ -94,7 +106,9 @@ def refine(disp1, disp2, sim, *, image_names, pair_img1, pair_img2, pair_off, fe
     get 0.
     return_covariance=True: a fourth value, the [n_nodes, 3] float64 device tensor of lfr_batch_covariance (C(di,di), C(di,dj),
     C(dj,dj) per node, the solver's unit squared; 0 = no covariance for this node).  It is detached: the covariance is not
-    differentiated."""
+    differentiated.
+    hessian: "exact" (the default) or "gauss_newton" - the H of the backward pass (lfr_batch_backward); anything else: ValueError."""
+    gauss_newton = _check_hessian("refine", hessian)
     pair_img1 = np.ascontiguousarray(pair_img1, np.int32)
     pair_img2 = np.ascontiguousarray(pair_img2, np.int32)
     pair_off = np.ascontiguousarray(pair_off, np.int64)
@@ -104,6 +118,7 @@ def refine(disp1, disp2, sim, *, image_names, pair_img1, pair_img2, pair_off, fe
     meta = {"image_names": list(image_names), "facts": facts, "pair_img1": pair_img1, "pair_img2": pair_img2, "pair_off": pair_off,
             "feat1": np.ascontiguousarray(feat1, np.uint32), "feat2": np.ascontiguousarray(feat2, np.uint32),
             "banned": tuple(banned), "tukey_variant": tukey_variant, "return_covariance": bool(return_covariance),
+            "gauss_newton": gauss_newton,
             "kept_rows": _kept_rows(pair_img1, pair_img2, pair_off, list(image_names), tuple(banned))}
     pos, node_image, node_feature = _Refine.apply(disp1, disp2, sim, meta)
     if return_covariance:
@@ -132,7 +147,7 @@ class _RefinerStep(torch.autograd.Function):
             raise RuntimeError("Refiner: this forward (step %d) is stale - the shared batch holds only its latest solve (step %d); "
                                "run backward before the next forward" % (ctx.epoch, r._epoch))
         s1, s2, ss, t1, t2, ts = ctx.n_in
-        g1, g2, gs = r._batch.backward(grad_pos, f64=False)
+        g1, g2, gs = r._batch.backward(grad_pos, f64=False, gauss_newton=r._gauss_newton)
         if r._idx is not None:      # back to the caller's rows (matches of banned pairs get 0)
             f1 = torch.zeros((r.n_rows, 18), dtype=g1.dtype, device=g1.device)
             f2 = torch.zeros_like(f1)
@@ -154,10 +169,11 @@ class Refiner:
     the similarities stay, no gradient).  Tensors as for refine(), in the caller's rows (banned pairs included).  The forward issues
     set_inputs, solve and the positions' copy on torch's current stream and does not synchronise the host.  The batch is shared and
     holds only its latest solve: backward() of an older forward raises RuntimeError; several backwards of the latest one are fine.
-    node_image, node_feature, n_nodes: as refine() returns them.  covariance(f64=True): lfr_batch_covariance of the latest solve."""
+    hessian: as for refine().  node_image, node_feature, n_nodes: as refine() returns them.  covariance(f64=True): lfr_batch_covariance of the latest solve."""
 
     def __init__(self, disp1, disp2, sim, *, image_names, pair_img1, pair_img2, pair_off, feat1, feat2, image_facts=None, banned=(),
-                 tukey_variant="ceres1"):
+                 tukey_variant="ceres1", hessian="exact"):
+        self._gauss_newton = _check_hessian("Refiner", hessian)
         pair_img1 = np.ascontiguousarray(pair_img1, np.int32)
         pair_img2 = np.ascontiguousarray(pair_img2, np.int32)
         pair_off = np.ascontiguousarray(pair_off, np.int64)

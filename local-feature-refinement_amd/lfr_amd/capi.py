@@ -65,6 +65,7 @@ class CovarianceStats(C.Structure):
 
 
 BACKWARD_F64 = 1                # LFR_BACKWARD_F64
+BACKWARD_GAUSS_NEWTON = 2       # LFR_BACKWARD_GAUSS_NEWTON
 BACKWARD_OK, BACKWARD_NOT_USABLE, BACKWARD_INDEFINITE = 0, 1, 2      # lfr_batch_backward_status
 COVARIANCE_F64 = 1              # LFR_COVARIANCE_F64
 COVARIANCE_OK, COVARIANCE_NOT_USABLE, COVARIANCE_SINGULAR = 0, 1, 2     # lfr_batch_covariance_status
@@ -676,10 +677,12 @@ class Batch:
             stream = torch.cuda.current_stream(dev).cuda_stream
         _check(lib().lfr_batch_set_inputs(self._h, p1, p2, ps, C.c_void_p(stream) if stream else None))
 
-    def backward(self, grad_positions, f64=False, stream=None, want_stats=False):
+    def backward(self, grad_positions, f64=False, stream=None, want_stats=False, gauss_newton=False):
         """Implicit gradient of the latest solve (lfr_batch_backward, include/lfr.h): grad_positions = dL/dx, [n_nodes, 2] float64 on
         the batch's device.  Returns (grad_disp1, grad_disp2, grad_sim) as device tensors in the graph's match layout ([n_matches, 18],
-        [n_matches, 18], [n_matches]; float32, or float64 with f64=True), and the stats dict when want_stats (that waits)."""
+        [n_matches, 18], [n_matches]; float32, or float64 with f64=True), and the stats dict when want_stats (that waits).
+        gauss_newton=True: H = J^T J instead of the exact Hessian (LFR_BACKWARD_GAUSS_NEWTON): positive definite where the exact one
+        is not, so those components get a gradient too; BACKWARD_INDEFINITE then means singular."""
         import torch
         n = self.problem.graph.n_nodes
         m = self.problem.graph.n_edges // 2
@@ -694,7 +697,8 @@ class Batch:
             stream = torch.cuda.current_stream(g.device).cuda_stream
         st = BackwardStats()
         _check(lib().lfr_batch_backward(self._h, C.c_void_p(g.data_ptr() or 1), C.c_void_p(g1.data_ptr() or 1), C.c_void_p(g2.data_ptr() or 1), C.c_void_p(gs.data_ptr() or 1),
-                                        BACKWARD_F64 if f64 else 0, C.c_void_p(stream) if stream else None,
+                                        (BACKWARD_F64 if f64 else 0) | (BACKWARD_GAUSS_NEWTON if gauss_newton else 0),
+                                        C.c_void_p(stream) if stream else None,
                                         C.byref(st) if want_stats else None))
         if want_stats:
             return g1, g2, gs, st.as_dict()
