@@ -304,7 +304,10 @@ int lfr_batch_positions_view(lfr_batch *b, const double **positions);
  * to the double lfr_batch_positions_view would return; valid until the next solve / view / free of this batch. */
 int lfr_batch_positions_view_f32(lfr_batch *b, const float **positions);
 /* per solved component of the shard, in batch order: original component id, iterations,
- * termination, final cost (any pointer may be NULL). Returns the count. */
+ * termination, final cost (any pointer may be NULL). Returns the count.
+ * final_cost is the fp64 value of F (the backward pass's, below) at the last iterate the solve accepted: the positions it wrote for
+ * CONVERGENCE and NO_CONVERGENCE; for FAILURE the iterate it gave up at, not the zeros it wrote, and NaN where that evaluation was not
+ * finite.  Every component, FAILURE included, is one term of lfr_solve_stats.sum_final_cost. */
 int64_t lfr_batch_component_info(lfr_batch *b, int64_t *component, int32_t *iterations, int32_t *termination,
                                  double *final_cost, int32_t *n_var_nodes, int32_t *n_edges);
 
