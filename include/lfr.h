@@ -454,6 +454,57 @@ int lfr_keypoint_covariances(const lfr_graph *g, const double *cov, const char *
  * a pivot was not positive (Cinv of that system is then zero).  Test infrastructure, not part of the covariance path. */
 int lfr_debug_invert_spd(int device, int solver, int64_t n_sys, const int32_t *n_rows, const double *A, double *Cinv, int32_t *status);
 
+/* ---------------------------------------------------------------------------------------------
+ * Objective, gradient, residuals and loss weights at given positions (the counterpart of ceres::Problem::Evaluate).
+ *
+ * Contract.  Per solved-program component c of this shard, whatever its termination:
+ *   F_c(x) = sum over the component's kept directed edges of 1/2 w_e rho_kind(e)(|r_e|^2),  r_e = x_dst - x_src - f(x_src; phi_e)
+ * - the F of lfr_batch_backward's contract - with the records as they are NOW: after the latest lfr_batch_set_inputs, whether or not a
+ * solve followed.
+ *   - positions_device: 2 * n_nodes doubles of the whole graph on the batch's device, or NULL = the batch's own position array (NULL
+ *     before the first solve: LFR_ERR_ARG; NULL between an lfr_batch_set_inputs and the next solve is allowed: the new records at the
+ *     held positions).  Only variable nodes of this shard's components are read; roots and other constant nodes evaluate at 0 whatever
+ *     the array holds there; nodes outside solved components are ignored.  Nothing is clamped to the +-1 box (the interpolant clamps
+ *     its own argument, so F is defined everywhere).  With explicit positions the call needs no earlier solve;
+ *   - cost_device (may be NULL): one double per component in the order of lfr_batch_component_info.  A component whose evaluation is
+ *     not finite gets that non-finite value and nothing else is affected;
+ *   - grad_positions_device (may be NULL): 2 * n_nodes doubles, the whole array is overwritten: dF/dx per coordinate of the variable
+ *     nodes - no projection onto the box, no free / bound distinction - and 0 for constant nodes, nodes outside solved components and
+ *     nodes outside the shard.  Per edge the destination gets w rho' r, the source -w rho' P^T r, P = I + df/dx_src, the derivative
+ *     of the interpolant zeroed outside [-0.5, 0.5] and kept at exactly +-0.5 (cost.cc:38-43);
+ *   - residuals_device (n_matches x 4) and weights_device (n_matches x 2), float32 or double with LFR_EVALUATE_F64, either may be
+ *     NULL, whole arrays are overwritten; the MATCH layout of lfr_batch_backward / lfr_batch_set_inputs.  Row m of the residuals:
+ *     (r_di, r_dj) of edge node1->node2, then of edge node2->node1 - raw residuals in the solver's unit, not loss-corrected.  Row m of
+ *     the weights: rho'(|r|^2) of the same two edges (1 at a zero residual, 0 for a saturated Tukey edge; the similarity is not folded
+ *     in).  A direction that is no residual block of this shard - a dropped edge, an edge between two constant nodes, a match outside
+ *     the shard - gets residual 0 and weight -1: "turned off by the loss" (0) differs from "not in the program" (-1);
+ *   - all four outputs NULL, or a flag bit other than LFR_EVALUATE_F64: LFR_ERR_ARG.  A batch over one rank's connected components
+ *     (lfr_problem_cc_sharded = 1) numbers its matches by itself: LFR_ERR_UNSUPPORTED when a per-match output is asked for; cost and
+ *     gradient are served.  There is no row limit: nothing here needs a matrix;
+ *   - outputs are bitwise repeatable from call to call, identical for host- and device-assembled batches and whether the records of
+ *     a device-assembled whole batch were materialised by this call or by a second solve; components that share a wavefront do not
+ *     influence each other, bit for bit.  No fp64 value goes through a global-memory atomic;
+ *   - runs on `hip_stream`, asynchronous unless stats != NULL.  Waits BY EVENT for the latest lfr_batch_set_inputs and the latest
+ *     solve, whatever streams they ran on; lfr_batch_set_inputs in turn waits for the latest evaluate.  Between a LATER solve and an
+ *     evaluate the caller orders the streams, as for lfr_batch_backward / lfr_batch_covariance.  The first call that asks for a
+ *     per-match output on a batch whose records do not carry their directed-edge ids builds the record -> edge map (a synchronising
+ *     step; the graph must still be alive: LFR_ERR_ARG otherwise).
+ * Kernels (lfr_evaluate.hip): components of up to 32 rows in ONE launch in the solve's packed layout (64/S components per wavefront,
+ * every record read once, cost by a fixed-order lane reduction, gradient accumulated in the group's LDS); above, one workgroup per
+ * component, owner computes: the thread of a node sums its gradient over the node's out- and in-edges in record order, the out-edge
+ * visit stores the per-match outputs and the cost term, the cost is a fixed wave-then-block tree. */
+typedef struct lfr_evaluate_stats {
+    int64_t n_components;          /* components evaluated (every solved-program component of the shard, whatever its termination) */
+    int64_t n_nonfinite;           /* components whose cost is not finite */
+    double sum_cost;               /* sum of the finite component costs, in descriptor order */
+    double kernel_ms;              /* HIP-event time of the call's kernels (and its clearing of the outputs) */
+} lfr_evaluate_stats;
+
+#define LFR_EVALUATE_F64 1         /* residuals / weights are double instead of float32 (float32 = the fp64 value rounded once) */
+
+int lfr_batch_evaluate(lfr_batch *b, const double *positions_device, double *cost_device, double *grad_positions_device,
+                       void *residuals_device, void *weights_device, int flags, void *hip_stream, lfr_evaluate_stats *stats);
+
 /* Unit-level probe of the device arithmetic (cost.cc:13-48,78-90 + the loss / corrector of solve.cc:111,120): for
  * each of n edges (flows n x 18 float32, sim, kind 0 = intra-track/Cauchy 1 = inter-track/Tukey, x1 = source and
  * x2 = destination position) the kernels' eval_edge on the GPU: out8[8i..] = 0.5*rho, corrected residual r0 r1,

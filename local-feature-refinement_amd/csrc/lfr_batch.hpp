@@ -7,6 +7,7 @@
 //   lfr_backward.hip     implicit-gradient backward pass (lfr_batch_backward): kernels, its own carvings, the launches
 //   lfr_covariance.hip   per-keypoint covariance (lfr_batch_covariance): kernels, the launches
 //   lfr_inputs.hip       new flows / similarities into a live batch (lfr_batch_set_inputs) and the record -> directed-edge map
+//   lfr_evaluate.hip     cost, gradient, residuals and loss weights at given positions (lfr_batch_evaluate): kernels, the launches
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -251,11 +252,13 @@ struct lfr_batch {
     hipStream_t inputs_stream = nullptr;
     bool inputs_pending = false;         // no solve has been issued since: the next one waits for ev_inputs
     lfr::PassState *bwd = nullptr, *cov = nullptr;       // lfr_backward.hip / lfr_covariance.hip: set up on the first call
+    lfr::PassState *eval = nullptr;                      // lfr_evaluate.hip: set up on the first lfr_batch_evaluate (its own entry: needs no solve)
 
     lfr_batch() { for (auto &e : ev_ring) e = nullptr; }
     ~lfr_batch() {
         lfr::pass_free(bwd);
         lfr::pass_free(cov);
+        lfr::pass_free(eval);
         if (ctx) {
             (void)hipSetDevice(device);
             if (n_solves > 0) (void)hipStreamSynchronize(last_stream);      // nothing may still use the slab

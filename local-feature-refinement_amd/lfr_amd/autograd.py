@@ -169,7 +169,8 @@ class Refiner:
     the similarities stay, no gradient).  Tensors as for refine(), in the caller's rows (banned pairs included).  The forward issues
     set_inputs, solve and the positions' copy on torch's current stream and does not synchronise the host.  The batch is shared and
     holds only its latest solve: backward() of an older forward raises RuntimeError; several backwards of the latest one are fine.
-    hessian: as for refine().  node_image, node_feature, n_nodes: as refine() returns them.  covariance(f64=True): lfr_batch_covariance of the latest solve."""
+    hessian: as for refine().  node_image, node_feature, n_nodes: as refine() returns them.  covariance(f64=True): lfr_batch_covariance of the latest solve.
+    evaluate(positions=None, **kw): lfr_batch_evaluate (cost, dF/dx, residuals, loss weights), detached."""
 
     def __init__(self, disp1, disp2, sim, *, image_names, pair_img1, pair_img2, pair_off, feat1, feat2, image_facts=None, banned=(),
                  tukey_variant="ceres1", hessian="exact"):
@@ -229,6 +230,24 @@ class Refiner:
             raise RuntimeError("Refiner: covariance before the first forward")
         with torch.cuda.device(self.device):
             return self._batch.covariance(f64=f64)
+
+    def evaluate(self, positions=None, **kw):
+        """Batch.evaluate (lfr_batch_evaluate) on the shared batch: cost, dF/dx, raw residuals and loss weights at `positions`
+        ([n_nodes, 2], None = the latest forward's), with the records of the latest forward - or of the constructor before the first.
+        "residuals" and "weights" come back in the caller's rows: the rows of banned pairs read residual 0 and weight -1.  Every
+        tensor is detached: F is not differentiated here, neither with respect to the positions (that is "grad") nor to the flows."""
+        if self._batch is None:
+            raise RuntimeError("Refiner: evaluate after close()")
+        with torch.cuda.device(self.device):
+            out = self._batch.evaluate(None if positions is None else positions.detach().to(self.device), **kw)
+            if self._idx is not None:
+                for name, fill in (("residuals", 0.0), ("weights", -1.0)):
+                    if name in out:
+                        t = out[name]
+                        full = torch.full((self.n_rows,) + tuple(t.shape[1:]), fill, dtype=t.dtype, device=t.device)
+                        full[self._idx] = t
+                        out[name] = full
+        return {k: (v.detach() if isinstance(v, torch.Tensor) else v) for k, v in out.items()}
 
     def close(self):
         for name in ("_batch", "_problem", "_graph"):

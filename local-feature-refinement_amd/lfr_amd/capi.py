@@ -64,11 +64,19 @@ class CovarianceStats(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+class EvaluateStats(C.Structure):
+    _fields_ = [(n, C.c_int64) for n in ("n_components", "n_nonfinite")] + [("sum_cost", C.c_double), ("kernel_ms", C.c_double)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
 BACKWARD_F64 = 1                # LFR_BACKWARD_F64
 BACKWARD_GAUSS_NEWTON = 2       # LFR_BACKWARD_GAUSS_NEWTON
 BACKWARD_OK, BACKWARD_NOT_USABLE, BACKWARD_INDEFINITE = 0, 1, 2      # lfr_batch_backward_status
 COVARIANCE_F64 = 1              # LFR_COVARIANCE_F64
 COVARIANCE_OK, COVARIANCE_NOT_USABLE, COVARIANCE_SINGULAR = 0, 1, 2     # lfr_batch_covariance_status
+EVALUATE_F64 = 1                # LFR_EVALUATE_F64
 
 
 _lib = None
@@ -134,6 +142,7 @@ def lib():
         "lfr_batch_set_inputs": (C.c_int, [vp, vp, vp, vp, vp]),
         "lfr_batch_covariance": (C.c_int, [vp, vp, C.c_int, vp, C.POINTER(CovarianceStats)]),
         "lfr_batch_covariance_status": (i64, [vp, vp]),
+        "lfr_batch_evaluate": (C.c_int, [vp, vp, vp, vp, vp, vp, C.c_int, vp, C.POINTER(EvaluateStats)]),
         "lfr_keypoint_covariances": (C.c_int, [vp, vp, C.c_char_p, vp, i64]),
         "lfr_debug_invert_spd": (C.c_int, [C.c_int, C.c_int, i64, vp, vp, vp, vp]),
         "lfr_batch_spin_timeouts": (i64, [vp]),
@@ -169,7 +178,7 @@ EXPORTS = ["lfr_version", "lfr_last_error", "lfr_graph_from_files", "lfr_graph_f
            "lfr_graph_num_images", "lfr_graph_get_nodes", "lfr_graph_image_name", "lfr_graph_image_fact",
            "lfr_write_matching_file", "lfr_problem_build", "lfr_problem_build_labels", "lfr_problem_build_hip", "lfr_problem_free", "lfr_problem_get_stats",
            "lfr_problem_get_labels", "lfr_problem_shard_components", "lfr_hip_warmup", "lfr_batch_create", "lfr_batch_free", "lfr_batch_solve",
-           "lfr_batch_download", "lfr_batch_timing", "lfr_batch_spin_timeouts", "lfr_batch_team_runs", "lfr_batch_team_fallbacks", "lfr_debug_occupy", "lfr_batch_tree_stats", "lfr_batch_component_info", "lfr_batch_positions_to_device", "lfr_batch_backward", "lfr_batch_backward_status", "lfr_batch_set_inputs", "lfr_batch_covariance", "lfr_batch_covariance_status", "lfr_keypoint_covariances", "lfr_debug_invert_spd", "lfr_solve_hip", "lfr_solve_hip_multi", "lfr_solve_graph_hip_multi", "lfr_write_solution", "lfr_apply_displacements"]
+           "lfr_batch_download", "lfr_batch_timing", "lfr_batch_spin_timeouts", "lfr_batch_team_runs", "lfr_batch_team_fallbacks", "lfr_debug_occupy", "lfr_batch_tree_stats", "lfr_batch_component_info", "lfr_batch_positions_to_device", "lfr_batch_backward", "lfr_batch_backward_status", "lfr_batch_set_inputs", "lfr_batch_covariance", "lfr_batch_covariance_status", "lfr_batch_evaluate", "lfr_keypoint_covariances", "lfr_debug_invert_spd", "lfr_solve_hip", "lfr_solve_hip_multi", "lfr_solve_graph_hip_multi", "lfr_write_solution", "lfr_apply_displacements"]
 
 
 def _check(rc):
@@ -737,6 +746,49 @@ class Batch:
         rc = lib().lfr_batch_covariance_status(self._h, _ptr(out))
         if rc < 0:
             _check(rc)
+        return out
+
+    def evaluate(self, positions=None, *, cost=True, grad=True, residuals=True, weights=True, f64=True, stream=None, want_stats=False):
+        """Objective, gradient, residuals and loss weights at `positions` (lfr_batch_evaluate, include/lfr.h): a [n_nodes, 2] float64
+        tensor on the batch's device, or None = the batch's own positions (after a solve).  Returns a dict of device tensors, one per
+        output asked for: "cost" [n_components] float64 in the order of component_info, "grad" [n_nodes, 2] float64 (dF/dx; 0 for
+        constant and unsolved nodes), "residuals" [n_matches, 2, 2] (per match the raw (r_di, r_dj) of edge node1->node2, then of
+        node2->node1) and "weights" [n_matches, 2] (rho' of the two edges; -1: the direction is no residual block of this batch),
+        float64 or float32 with f64=False; with want_stats also "stats" (that waits)."""
+        import torch
+        n = self.problem.graph.n_nodes
+        m = self.problem.graph.n_edges // 2
+        dev = torch.device("cuda", self.device)
+        pos = None
+        if positions is not None:
+            if not isinstance(positions, torch.Tensor) or not positions.is_cuda or positions.device != dev or positions.numel() != 2 * n:
+                raise ValueError("evaluate: need a [%d, 2] float64 tensor on %s" % (n, dev))
+            pos = positions.detach().to(dtype=torch.float64).contiguous()
+        dt = torch.float64 if f64 else torch.float32
+        out = {}
+        if cost:
+            nc = lib().lfr_batch_component_info(self._h, None, None, None, None, None, None)
+            if nc < 0:
+                _check(int(nc))
+            out["cost"] = torch.empty((nc,), dtype=torch.float64, device=dev)
+        if grad:
+            out["grad"] = torch.empty((n, 2), dtype=torch.float64, device=dev)
+        if residuals:
+            out["residuals"] = torch.empty((m, 2, 2), dtype=dt, device=dev)
+        if weights:
+            out["weights"] = torch.empty((m, 2), dtype=dt, device=dev)
+        if stream is None:
+            stream = torch.cuda.current_stream(dev).cuda_stream
+
+        def ptr(name):
+            return C.c_void_p(out[name].data_ptr() or 1) if name in out else None
+
+        st = EvaluateStats()
+        _check(lib().lfr_batch_evaluate(self._h, None if pos is None else C.c_void_p(pos.data_ptr() or 1), ptr("cost"), ptr("grad"),
+                                        ptr("residuals"), ptr("weights"), EVALUATE_F64 if f64 else 0,
+                                        C.c_void_p(stream) if stream else None, C.byref(st) if want_stats else None))
+        if want_stats:
+            out["stats"] = st.as_dict()
         return out
 
     def tree_stats(self):
