@@ -269,7 +269,37 @@ void lfr_batch_free(lfr_batch *b);
  * variable node (a failed solve writes 0), roots and nodes outside solved components stay 0.  Asynchronous
  * unless stats != NULL, in which case the call synchronizes the stream and fills stats. */
 int lfr_batch_solve(lfr_batch *b, void *hip_stream, lfr_solve_stats *stats);
-/* HIP-event timings of one of the last 64 lfr_batch_solve calls (solves_back = 0: the latest);
+/* The same solve started at given positions instead of the origin (the reference always starts at 0, solve.cc:609-612; ceres::Solve
+ * itself starts from whatever the parameter blocks hold - this is that entry for callers that solve the same scenes again and again).
+ *
+ * The start array.  initial_positions_device: 2 * n_nodes doubles of the WHOLE graph on the batch's device, in the layout of
+ * lfr_batch_positions_to_device and of lfr_batch_evaluate's positions_device.  NULL = the batch's own position array, started in
+ * place: the latest solve's result, or the zeros of lfr_batch_create before the first solve (in place is safe: a component reads its
+ * own nodes in its prologue and no other component writes them).  Only the coordinates of variable nodes of this shard's solved
+ * components are read; roots and other constant nodes stay 0 whatever the array holds, everything else is ignored and not written.
+ * An explicit array is read only by work enqueued in this call: the caller may overwrite it in stream order afterwards.
+ *
+ * The start point.  Per component x0 = project(initial): every coordinate clamped to [-1, 1] (Ceres' IterationZero projects onto the
+ * bounds); a NaN reads as 0, +-inf clamps to +-1.  The library still never emits a non-finite displacement.
+ *
+ * The loop.  From x0 on it is lfr_batch_solve's, decision for decision: cost, J^T J and gradient at x0, the Jacobi scaling fixed
+ * there, x_norm = |x0|, radius 1e4, the gradient test before the first iteration.  With an all-zero start (every coordinate that is
+ * read +0 or -0; a -0 stays -0 as the value of x0) the results are those of lfr_batch_solve bit for bit.  That holds for the array
+ * as a whole: components of up to 32 rows share a wavefront with their neighbours in the batch, and the first evaluation takes
+ * lfr_batch_solve's closed form at the origin only when EVERY component of the wavefront starts there.  A component that starts at
+ * zero beside one that does not is evaluated in the general form, which agrees with lfr_batch_solve to rounding only (seen: the last
+ * bit of final_cost, 3e-17 in the positions).  ref_*_passes_* count what Ceres would have performed from x0.
+ *
+ * Results.  final_cost, iterations and termination as for lfr_batch_solve.  A component that FAILS writes x0, the PROJECTED start
+ * (with a zero start the 0 of lfr_batch_solve); Ceres would leave the caller's unprojected values.
+ *
+ * State.  A solve in every respect: lfr_batch_timing, the wait for a pending lfr_batch_set_inputs, and lfr_batch_backward,
+ * lfr_batch_covariance, lfr_batch_evaluate, the downloads and views, lfr_batch_spin_timeouts / _team_runs / _team_fallbacks serve it
+ * afterwards.  A device-assembled batch whose records are not yet written writes them first (the warm kernels have no gathering
+ * form).  Shards are served: the node numbering is the graph's.
+ * Asynchronous unless stats != NULL. */
+int lfr_batch_solve_from(lfr_batch *b, const double *initial_positions_device, void *hip_stream, lfr_solve_stats *stats);
+/* HIP-event timings of one of the last 64 lfr_batch_solve / lfr_batch_solve_from calls (solves_back = 0: the latest);
  * waits for that solve to finish.  class_ms / class_edges: LFR_NUM_KERNEL_CLASSES entries, one
  * per kernel launch (packed <8,1,3>, <16,1,6>, a retired slot, <32,1,6>, <32,2,5>; workgroup per component with the matrix
  * in LDS: <= 88 rows, <= 130 rows, <= 192 rows; workgroup per component with the matrix in HBM). */

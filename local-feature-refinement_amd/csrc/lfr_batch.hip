@@ -781,6 +781,7 @@ KernelArgs make_kernel_args(const lfr_batch *b) {
     }
     a.team_ctl = b->d_team_ctl; a.team_red = b->d_team_red;
     a.trace = nullptr;
+    a.x_start = nullptr;
     for (int k = 0; k < 3; ++k) a.team_work[k] = b->team_work[k];
     a.team_epoch = (uint32_t)(b->n_solves + 1);
     a.team_patience_us = b->team_patience_us;
@@ -1036,16 +1037,11 @@ int64_t read_solve_word(lfr_batch *b, bool team, int word) {
     return (int64_t)v;
 }
 
-}  // namespace
-
-extern "C" {
-
-int lfr_batch_solve(lfr_batch *b, void *hip_stream, lfr_solve_stats *stats) {
-    if (!b) { lfr::set_error("bad argument"); return LFR_ERR_ARG; }
-    host_trace("lfr_batch_solve enters");
-    HIP_TRY(hipSetDevice(b->device));
-    hipStream_t st = (hipStream_t)hip_stream;
+// lfr_batch_solve (x_start == nullptr: from the origin) and lfr_batch_solve_from (x_start: the start array, b->d_positions for "in
+// place") over one launch plan.  The warm kernels read records: a fused batch materialises its records first, whatever its history.
+int solve_impl(lfr_batch *b, const double *x_start, hipStream_t st, lfr_solve_stats *stats) {
     KernelArgs a = make_kernel_args(b);
+    a.x_start = x_start;
 #ifdef LFR_TRACE_TREE
     static unsigned long long *d_trace = nullptr;
     if (!d_trace) { HIP_TRY(hipMalloc(&d_trace, ((size_t)1 << 20) * 8 + 64)); }
@@ -1053,7 +1049,9 @@ int lfr_batch_solve(lfr_batch *b, void *hip_stream, lfr_solve_stats *stats) {
     a.trace = d_trace;
 #endif
     bool materialised = false;
-    if (b->fused && b->n_solves > 0) {           // solved before: this batch is being re-used - write the records once, read them from now on
+    // a fused batch that is solved a second time (it is being re-used) or started warm (the warm packed kernel reads records only):
+    // write the records once, read them from now on
+    if (b->fused && (b->n_solves > 0 || x_start)) {
         lfr::materialize_records(b, st);
         HIP_TRY(hipGetLastError());
         b->fused = false;
@@ -1085,6 +1083,25 @@ int lfr_batch_solve(lfr_batch *b, void *hip_stream, lfr_solve_stats *stats) {
     HIP_TRY(lfr::stream_wait(st));
     { const int rc = read_diagnostics(b, a); if (rc != LFR_OK) return rc; }
     return collect_stats(b, recorded, st, stats);
+}
+
+}  // namespace
+
+extern "C" {
+
+int lfr_batch_solve(lfr_batch *b, void *hip_stream, lfr_solve_stats *stats) {
+    if (!b) { lfr::set_error("bad argument"); return LFR_ERR_ARG; }
+    host_trace("lfr_batch_solve enters");
+    HIP_TRY(hipSetDevice(b->device));
+    return solve_impl(b, nullptr, (hipStream_t)hip_stream, stats);
+}
+
+int lfr_batch_solve_from(lfr_batch *b, const double *initial_positions_device, void *hip_stream, lfr_solve_stats *stats) {
+    if (!b) { lfr::set_error("bad argument"); return LFR_ERR_ARG; }
+    host_trace("lfr_batch_solve_from enters");
+    HIP_TRY(hipSetDevice(b->device));
+    // NULL: the batch's own positions, started in place - a component reads its nodes in its prologue and nobody else writes them
+    return solve_impl(b, initial_positions_device ? initial_positions_device : b->d_positions, (hipStream_t)hip_stream, stats);
 }
 
 // Bounded spins that ran out during the batch's latest solve (the hand-off flags of the LDS factorization, the dependency counters of

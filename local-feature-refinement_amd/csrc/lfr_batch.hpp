@@ -65,6 +65,7 @@ struct KernelArgs {
     uint32_t team_work[3];
     uint32_t team_epoch;        // differs between launches that share the reduction slots
     uint32_t team_patience_us;  // teams that cannot form for this long with nobody at work: the launch goes on one workgroup per component (LFR_TEAM_PATIENCE_MS)
+    const double *x_start;      // lfr_batch_solve_from: 2 * n_nodes start values in the layout of `positions` (may BE positions); nullptr: the origin
     unsigned long long *trace;  // -DLFR_TRACE_TREE: [0] = words used, then {s_memtime, type << 56 | wave of the team << 48 | iteration << 32 | column} pairs
 };
 
@@ -115,6 +116,7 @@ struct SolveGeometry {
 const SolveGeometry &solve_geometry();
 size_t block_lds_bytes(int max_rows);    // dynamic LDS of a workgroup-class launch whose largest system has max_rows rows
 int reserve_block_lds(int lds_s, int lds_m, int lds_l);      // hipFuncAttributeMaxDynamicSharedMemorySize of the three LDS classes
+// (a.x_start set: the warm instantiations; the packed one reads records only - the caller has materialised those of a fused batch)
 void launch_packed(const KernelArgs &a, const PackedRanges &r, bool fused, int n_blocks, hipStream_t cs);       // solve_packed_kernel
 void launch_group_class(int cls, const KernelArgs &a, bool fused, int n_blocks, hipStream_t cs);                // one packed class (LFR_SERIAL_CLASSES=1)
 void launch_block_class(int cls, const KernelArgs &a, int rows, int wgs, hipStream_t cs);                       // solve_block_kernel of an LDS class

@@ -93,6 +93,9 @@ namespace {
 #ifndef LFR_GJ_DPP
 #define LFR_GJ_DPP 2               // elimination of the 16-row (1) and also the 8-row (2) packed class with DPP row broadcasts; 0: ds_swizzle
 #endif
+// The start of a warm solve (lfr_batch_solve_from): Ceres' IterationZero projects the caller's values onto the box; a NaN reads as 0.
+__device__ __forceinline__ double project_start(double v) { return v == v ? clampb(v) : 0.0; }
+
 enum : int { PH_SOLVE = 0, PH_EVAL_INIT = 1, PH_EVAL_LS = 2, PH_EVAL_CAND = 3, PH_REEVAL = 4, PH_DONE = 5 };
 
 // Gauss-Jordan elimination of the damped normal equations held one row per lane, no pivoting (SPD);
@@ -240,10 +243,14 @@ __device__ __forceinline__ double packed_step(const double *A, const int row, co
 #endif
 constexpr int kPackedWaves = LFR_PACKED_WAVES;
 
-template <int NV, int LPR, int EPL, bool FUSED>
+// WARM (lfr_batch_solve_from; record-reading only): the group starts at the projection of a.x_start instead of the origin - its first
+// sweep is a general one unless the whole wave starts at the origin, |x0| comes from a group sum, a FAILURE writes x0 back.  The cold
+// instantiations are what they were.
+template <int NV, int LPR, int EPL, bool FUSED, bool WARM = false>
 __device__ __forceinline__ void solve_group_body(const KernelArgs &a, const int block_in_class, unsigned char *lds_raw) {
     constexpr int S = NV * LPR, G = 64 / S, CPL = NV / LPR, LD = NV + 1;
     static_assert(S <= 64 && (LPR == 1 || LPR == 2), "group geometry");
+    static_assert(!(WARM && FUSED), "the warm start reads records");
 #ifdef LFR_ISA_MARKS
     asm volatile("; LFR_CLASS %0 %1 %2" :: "n"(NV), "n"(LPR), "n"(EPL));
 #endif
@@ -291,7 +298,11 @@ __device__ __forceinline__ void solve_group_body(const KernelArgs &a, const int 
         const int e = sl + S * k;
         load_packed_edge<FUSED>(a, d.edge_off + (e < E ? e : 0), flow[k], sim[k], idx[k]);
     }
-    if (sl < NV) L.x[sl] = 0.0;
+    // WARM: the row's coordinate of the start array in every lane of the row (sl < NV: part 0, row == sl); rows beyond the system and
+    // the constants' slots stay 0
+    double x_start = 0.0;
+    if constexpr (WARM) { if (is_row) x_start = project_start(a.x_start[2 * (size_t)a.node_ids[d.node_off + (row >> 1)] + (row & 1)]); }
+    if (sl < NV) L.x[sl] = WARM ? x_start : 0.0;
     if (sl < 2) L.x[NV + sl] = 0.0;
     // rows >= nv2 stay zero for the whole solve (the sweeps re-zero rows < nv2; the first one finds them zero from here).  16-byte stores.
     static_assert((NV * LD) % 2 == 0, "J^T J is cleared in pairs");
@@ -299,10 +310,11 @@ __device__ __forceinline__ void solve_group_body(const KernelArgs &a, const int 
 
     // ---- group state (uniform inside a group; 'row' values are identical in the LPR lanes of a row) ----
     int phase = have ? PH_EVAL_INIT : PH_DONE;
-    double xi = 0.0, gi = 0.0, scale = 1.0, diag = 1.0;            // row
+    double xi = WARM ? x_start : 0.0, gi = 0.0, scale = 1.0, diag = 1.0;            // row
     double inv_scale = 1.0;                                          // row: 1 / scale = 1 + sqrt(a_ii at iteration 0)
     double xt = 0.0, delta = 0.0;                                    // row
     double cost = 0.0, radius = kInitialRadius, x_norm = 0.0, gmax = 0.0;
+    if constexpr (WARM) x_norm = sqrt(group_sum<S>(own ? xi * xi : 0.0));      // |x0| (every lane of the wave is active)
     double g_dot_delta = 0.0, model_cost_change = 0.0, alpha = 1.0;
     int n_reject = 0;                                 // decrease_factor = 2^(1 + n_reject)  (Ceres: 2, 4, 8, ...)
     bool reuse_diagonal = false, step_successful = true, a_dirty = false;
@@ -310,7 +322,10 @@ __device__ __forceinline__ void solve_group_body(const KernelArgs &a, const int 
     int n_invalid = 0, iteration = 0, term = LFR_TERM_CONVERGENCE;
     if (sl == 0) { L.n_successful = 0; L.n_ls_evals = 0; L.n_cand = 0; L.exec_passes = 0; L.ls_iter = 0; L.ls_prev_flags = 0; }
 
-    bool at_zero = true;                              // wave-uniform: the first sweep evaluates every edge at the origin (PH_EVAL_INIT)
+    // wave-uniform: the first sweep evaluates every edge at the origin (PH_EVAL_INIT).  WARM: only when every group of the wave starts there
+    // (a batch that has never been solved, an all-zero array) - the wave then runs the cold solve's instructions from the first sweep on
+    bool at_zero = true;
+    if constexpr (WARM) at_zero = !__any(x_start != 0.0);
     // the logarithm's series coefficients in 22 VGPRs for the whole solve where the class has them to spare (8- and 16-row classes)
     constexpr bool kLogRegs = NV <= 16 && LPR == 1;
     LogCoef logc;
@@ -603,8 +618,13 @@ __device__ __forceinline__ void solve_group_body(const KernelArgs &a, const int 
     PROF_FLUSH();
 
     if (have) {
-        if (own)       // every variable is written by every solve (a failed solve leaves 0, solve.cc:609-612)
-            a.positions[2 * (size_t)a.node_ids[d.node_off + (row >> 1)] + (row & 1)] = term != LFR_TERM_FAILURE ? xi : 0.0;
+        if (own) {     // every variable is written by every solve (a failed solve leaves 0, solve.cc:609-612; WARM: the projected start,
+                       // read again - in place it is this very entry, which nobody else writes)
+            double *out = a.positions + 2 * (size_t)a.node_ids[d.node_off + (row >> 1)] + (row & 1);
+            double x_fail = 0.0;
+            if constexpr (WARM) { if (term == LFR_TERM_FAILURE) x_fail = project_start(a.x_start[out - a.positions]); }
+            *out = term != LFR_TERM_FAILURE ? xi : x_fail;
+        }
         if (sl == 0) {
             CompInfoDev inf;
             inf.iterations = iteration; inf.termination = term; inf.n_successful = L.n_successful;
@@ -637,7 +657,7 @@ __global__ __launch_bounds__(64 * kPackedWaves, LFR_GROUP_WAVES) void solve_grou
 // long-running one-component-per-wave classes first so their tail overlaps the bulk of the small
 // classes (workgroups are dispatched in index order).  The classes are compiled into one kernel;
 // its register/LDS budget is the maximum over the classes (all are built for 2 waves per SIMD).
-template <bool FUSED>
+template <bool FUSED, bool WARM = false>
 __global__ __launch_bounds__(64 * kPackedWaves, LFR_GROUP_WAVES) void solve_packed_kernel(KernelArgs a, const PackedRanges r) {
     __shared__ __attribute__((aligned(16))) unsigned char lds_raw[kPackedLdsBytes];
     // (one workgroup per block, dealt by the hardware: the wave timeline of config 4 shows the chip full from the first
@@ -647,19 +667,19 @@ __global__ __launch_bounds__(64 * kPackedWaves, LFR_GROUP_WAVES) void solve_pack
     const int b = (int)blockIdx.x;
     if (b < r.blk_begin[1]) {
         a.desc_begin = r.desc_begin[0]; a.desc_end = r.desc_end[0]; a.cls = lfr::KC_G64_4;
-        solve_group_body<32, 2, 5, FUSED>(a, b - r.blk_begin[0], lds_raw);
+        solve_group_body<32, 2, 5, FUSED, WARM>(a, b - r.blk_begin[0], lds_raw);
     } else if (b < r.blk_begin[2]) {
         a.desc_begin = r.desc_begin[1]; a.desc_end = r.desc_end[1]; a.cls = lfr::KC_G64_2;
-        solve_group_body<32, 1, 6, FUSED>(a, b - r.blk_begin[1], lds_raw);
+        solve_group_body<32, 1, 6, FUSED, WARM>(a, b - r.blk_begin[1], lds_raw);
     } else if (b < r.blk_begin[3]) {
         a.desc_begin = r.desc_begin[2]; a.desc_end = r.desc_end[2]; a.cls = lfr::KC_G32;
         // (KC_G32, formerly <16,2,3>, is retired: <16,1,6> takes every <=16-row component up to 96 edges)
     } else if (b < r.blk_begin[4]) {
         a.desc_begin = r.desc_begin[3]; a.desc_end = r.desc_end[3]; a.cls = lfr::KC_G16;
-        solve_group_body<16, 1, 6, FUSED>(a, b - r.blk_begin[3], lds_raw);
+        solve_group_body<16, 1, 6, FUSED, WARM>(a, b - r.blk_begin[3], lds_raw);
     } else {
         a.desc_begin = r.desc_begin[4]; a.desc_end = r.desc_end[4]; a.cls = lfr::KC_G8;
-        solve_group_body<8, 1, 3, FUSED>(a, b - r.blk_begin[4], lds_raw);
+        solve_group_body<8, 1, 3, FUSED, WARM>(a, b - r.blk_begin[4], lds_raw);
     }
 }
 
@@ -1245,7 +1265,8 @@ __device__ __forceinline__ void back_substitute_lds(const double *Mat, const dou
 // vectors and the packed matrix live in dynamic LDS
 // (two waves per SIMD = 256 registers each, VGPRs + the MFMA accumulators: what the 4 / 2 workgroups per CU of the two smaller
 // LDS classes need; without the attribute the allocator takes 264)
-template <int kBlockThreads>
+// WARM (lfr_batch_solve_from): the component starts at the projection of a.x_start; an instantiation of its own, the cold one is what it was
+template <int kBlockThreads, bool WARM>
 __device__ __forceinline__ void solve_component(const KernelArgs &a, const int max_rows, const int ci, double *dyn, BlockShared &sh) {
 #ifdef LFR_PROFILE_WGTIME
     const unsigned long long wg_t0_ = __builtin_amdgcn_s_memtime();
@@ -1273,7 +1294,13 @@ __device__ __forceinline__ void solve_component(const KernelArgs &a, const int m
     double *vadiag = vD + max_rows;   // diagonal of unscaled J^T J at x
     double *vdelta = vadiag + max_rows;
 
-    for (int i = tid; i < n + 2; i += kBlockThreads) { vx[i] = 0.0; vxc[i] = 0.0; }
+    // the start: the origin, or (WARM) the projection of the caller's values; slots n, n + 1 are the constants' zero
+    const double *const x_start = WARM ? a.x_start : nullptr;
+    for (int i = tid; i < n + 2; i += kBlockThreads) {
+        double x0 = 0.0;
+        if (x_start && i < n) x0 = project_start(x_start[2 * (size_t)a.node_ids[d.node_off + (i >> 1)] + (i & 1)]);
+        vx[i] = x0; vxc[i] = x0;
+    }
     __syncthreads();
 
     // One sweep over the edges at xv: returns the cost, fills gout = J^T r and (want_matrix) Mat =
@@ -1608,6 +1635,11 @@ __device__ __forceinline__ void solve_component(const KernelArgs &a, const int m
         return block_max<kBlockThreads>(m, sh);
     };
     LmControl lm{cost0, grad_max(vx, vg)};
+    if (x_start) {                                    // |x0| (0 at the origin)
+        double xn = 0.0;
+        for (int i = tid; i < n; i += kBlockThreads) xn += vx[i] * vx[i];
+        lm.x_norm = uni(sqrt(block_sum<kBlockThreads>(xn, sh)));
+    }
 
     while (lm.begin_iteration()) {
         PROF_MARK(4);                                 // 4: bookkeeping
@@ -1722,8 +1754,10 @@ __device__ __forceinline__ void solve_component(const KernelArgs &a, const int m
     if (lm.iteration >= LFR_PROFILE_ONLY_ITER)
 #endif
     PROF_FLUSH();
-    for (int i = tid; i < n; i += kBlockThreads)
-        a.positions[2 * (size_t)a.node_ids[d.node_off + (i >> 1)] + (i & 1)] = lm.term != LFR_TERM_FAILURE ? vx[i] : 0.0;
+    for (int i = tid; i < n; i += kBlockThreads) {    // (a FAILURE leaves the start: 0, or the projection of x_start read again - in place it is this very entry)
+        double *out = a.positions + 2 * (size_t)a.node_ids[d.node_off + (i >> 1)] + (i & 1);
+        *out = lm.term != LFR_TERM_FAILURE ? vx[i] : x_start ? project_start(x_start[out - a.positions]) : 0.0;
+    }
     if (tid == 0) {
         CompInfoDev inf = lm.info();
 #ifdef LFR_PROFILE_WGTIME          // diagnostic builds: the workgroup's lifetime in s_memtime ticks instead of the cost
@@ -1890,9 +1924,10 @@ struct TreeProbe {
 // PROBE (test infrastructure, one workgroup per system): no sweeps and no trust-region loop - the workspace behind the plan's words
 // is filled with NaN, the prologue below runs as it is, then A, D (into vD: the column tasks square it) and g (into vw) are placed from
 // the caller's buffers, and ONE factor() + back_substitute() produce y.  Every other instantiation compiles to what it was.
-template <int kBlockThreads, bool TEAM, bool PROBE = false>
+// WARM (lfr_batch_solve_from): the component starts at the projection of a.x_start; instantiations of their own
+template <int kBlockThreads, bool TEAM, bool PROBE = false, bool WARM = false>
 __device__ __forceinline__ void solve_tree_component(const KernelArgs &a, const int ci, BlockShared &sh, TreeShared &ts, TeamCtx &tm, const TreeProbe *pb = nullptr) {
-    static_assert(!(PROBE && TEAM), "the probe runs teams of one");
+    static_assert(!(PROBE && TEAM) && !(PROBE && WARM), "the probe runs teams of one, from nowhere");
     constexpr int kWaves = kBlockThreads / 64;
     constexpr uint32_t kNone = 0xffffffffu;
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -1966,8 +2001,16 @@ __device__ __forceinline__ void solve_tree_component(const KernelArgs &a, const 
         for (size_t i = pl[2] + (size_t)tid; i < pb->ws_doubles[ci]; i += kBlockThreads) wsb[i] = __builtin_nan("");
         __syncthreads();
     }
+    // the start: the origin, or (WARM) the projection of the caller's values at the rows of real nodes - split over the team like
+    // everything here, published by the barrier below
+    const double *const x_start = WARM ? a.x_start : nullptr;
     for (int i = gt; i < (int)vs; i += GT) {
-        vx[i] = 0.0; vxc[i] = 0.0; vscale[i] = 1.0; vD[i] = 0.0; vg[i] = 0.0; vgn[i] = 0.0; vstep[i] = 0.0; vinv[i] = 0.0; vw[i] = 0.0;
+        double x0 = 0.0;
+        if (x_start && i < 16 * NB) {
+            const uint32_t v = ipos[i >> 1];
+            if (v != kNone) x0 = project_start(x_start[2 * (size_t)a.node_ids[d.node_off + v] + (i & 1)]);
+        }
+        vx[i] = x0; vxc[i] = x0; vscale[i] = 1.0; vD[i] = 0.0; vg[i] = 0.0; vgn[i] = 0.0; vstep[i] = 0.0; vinv[i] = 0.0; vw[i] = 0.0;
         vadiag[i] = 0.0; vdiag[i] = 0.0; vdelta[i] = 0.0;
     }
     {   // A's tiles: zero once per solve - a sweep stores the same entries every time (one 2x2 block per matched pair, one per node).
@@ -2801,6 +2844,7 @@ __device__ __forceinline__ void solve_tree_component(const KernelArgs &a, const 
     const double cost0 = uni(sw.cost);                // (uni: the loop's scalars are replicated - SGPRs, like the LDS kernel's)
     PROF_MARK(0);
     LmControl lm{cost0, uni(sw.gm)};
+    if (x_start) lm.x_norm = uni(sqrt(sw.xn));        // |x0|: the sweep's |xc|^2 at the start (0 at the origin)
     while (lm.begin_iteration()) {
         TR_IT(lm.iteration);
         TR(10, 0);
@@ -2935,8 +2979,11 @@ __device__ __forceinline__ void solve_tree_component(const KernelArgs &a, const 
         const uint32_t v = ipos[p];
         if (v == kNone) continue;
         double *out = a.positions + 2 * (size_t)a.node_ids[d.node_off + v];
-        out[0] = lm.term != LFR_TERM_FAILURE ? ldd(vx + 2 * p) : 0.0;
-        out[1] = lm.term != LFR_TERM_FAILURE ? ldd(vx + 2 * p + 1) : 0.0;
+        // (a FAILURE leaves the start: 0, or the projection of x_start read again - in place it is this very entry)
+        const bool refill = lm.term == LFR_TERM_FAILURE && x_start != nullptr;
+        const double f0 = refill ? project_start(x_start[out - a.positions]) : 0.0, f1 = refill ? project_start(x_start[out - a.positions + 1]) : 0.0;
+        out[0] = lm.term != LFR_TERM_FAILURE ? ldd(vx + 2 * p) : f0;
+        out[1] = lm.term != LFR_TERM_FAILURE ? ldd(vx + 2 * p + 1) : f1;
     }
     if (tid == 0 && (!TEAM || tm.r == 0)) {
         CompInfoDev inf = lm.info();
@@ -2950,7 +2997,7 @@ __device__ __forceinline__ void solve_tree_component(const KernelArgs &a, const 
 }
 
 // persistent workgroups over the class's queue, like solve_block_kernel
-template <int kBlockThreads>
+template <int kBlockThreads, bool WARM = false>
 __global__ __launch_bounds__(kBlockThreads) __attribute__((amdgpu_waves_per_eu((kBlockThreads + 255) / 256, (kBlockThreads + 255) / 256))) void solve_tree_kernel(const KernelArgs a) {
     __shared__ BlockShared sh;
     __shared__ TreeShared ts;
@@ -2965,7 +3012,7 @@ __global__ __launch_bounds__(kBlockThreads) __attribute__((amdgpu_waves_per_eu((
         __syncthreads();
         if (ci < 0) break;
         TeamCtx tm;
-        solve_tree_component<kBlockThreads, false>(a, ci, sh, ts, tm);
+        solve_tree_component<kBlockThreads, false, false, WARM>(a, ci, sh, ts, tm);
         __syncthreads();
     }
 }
@@ -2996,7 +3043,7 @@ __device__ __forceinline__ int tree_team_size(const KernelArgs &a, const int ci)
     for (int k = 0; k < 3; ++k) if ((2 << k) <= kTeamMax && work >= a.team_work[k]) t = 2 << k;
     return t;
 }
-template <int kBlockThreads>
+template <int kBlockThreads, bool WARM = false>
 __global__ __launch_bounds__(kBlockThreads) __attribute__((amdgpu_waves_per_eu((kBlockThreads + 255) / 256, (kBlockThreads + 255) / 256))) void solve_tree_team_kernel(const KernelArgs a) {
     __shared__ BlockShared sh;
     __shared__ TreeShared ts;
@@ -3126,12 +3173,12 @@ __global__ __launch_bounds__(kBlockThreads) __attribute__((amdgpu_waves_per_eu((
         }
         if (alone) {
             TeamCtx solo;
-            solve_tree_component<kBlockThreads, false>(a, ci, sh, ts, solo);
+            solve_tree_component<kBlockThreads, false, false, WARM>(a, ci, sh, ts, solo);
         } else {
             tm.S = S; tm.r = rank - L; tm.bar = bars + L;
             tm.red = a.team_red + (size_t)unit_slot * kTeamRedPerUnit + (size_t)(L / 2) * (2 * kTeamMax * 16);
             if (tid == 0 && tm.r == 0) atomicAdd(ctl + lfr::kCtlTeamRuns, 1u);           // (statistics: components solved by a team)
-            solve_tree_component<kBlockThreads, true>(a, ci, sh, ts, tm);
+            solve_tree_component<kBlockThreads, true, false, WARM>(a, ci, sh, ts, tm);
         }
         if (tid == 0 && rank == L) atomicSub(ctl + lfr::kCtlAtWork, 1u);              // (the workgroup that took the component from the queue)
         __syncthreads();
@@ -3143,7 +3190,7 @@ __global__ __launch_bounds__(kBlockThreads) __attribute__((amdgpu_waves_per_eu((
 // order to the hardware dispatcher, which deals workgroups to the XCDs round-robin whatever they cost: a CU sat idle 0.16 ms on
 // average (up to 1.3 ms) before its next 160-KB workgroup while the queue was still full, and CUs ended up with one to seven
 // components each (`scripts/c5_timeline.py`).  Here a free CU always takes the largest component left.
-template <int kBlockThreads>
+template <int kBlockThreads, bool WARM>
 __device__ __forceinline__ void block_kernel_body(const KernelArgs &a, int max_rows) {
     extern __shared__ double dyn[];
     __shared__ BlockShared sh;
@@ -3159,14 +3206,14 @@ __device__ __forceinline__ void block_kernel_body(const KernelArgs &a, int max_r
         const int ci = __builtin_amdgcn_readfirstlane(next_ci);
         __syncthreads();                              // everyone has read it before the next round overwrites it
         if (ci < 0) break;
-        solve_component<kBlockThreads>(a, max_rows, ci, dyn, sh);
+        solve_component<kBlockThreads, WARM>(a, max_rows, ci, dyn, sh);
         __syncthreads();                              // the component's last LDS reads are done
     }
 }
 // (two waves per SIMD at every size: without the spills at one wave the kernel was slower - profiles/r06_ab/block_kernel_spills.txt)
-template <int kBlockThreads>
+template <int kBlockThreads, bool WARM = false>
 __global__ __launch_bounds__(kBlockThreads) __attribute__((amdgpu_waves_per_eu(2, 2))) void solve_block_kernel(const KernelArgs a, int max_rows) {
-    block_kernel_body<kBlockThreads>(a, max_rows);
+    block_kernel_body<kBlockThreads, WARM>(a, max_rows);
 }
 
 #ifndef LFR_THREADS_S
@@ -3207,17 +3254,33 @@ int reserve_block_lds(int lds_s, int lds_m, int lds_l) {
     HIP_TRY(hipFuncSetAttribute((const void *)solve_block_kernel<kThreadsM>, hipFuncAttributeMaxDynamicSharedMemorySize, std::max(lds_m, kThreadsM == kThreadsS ? lds_s : 0)));
     HIP_TRY(hipFuncSetAttribute((const void *)solve_block_kernel<kThreadsL>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                 std::max(lds_l, std::max(kThreadsL == kThreadsM ? lds_m : 0, kThreadsL == kThreadsS ? lds_s : 0))));
+    // (the warm instantiations run the same classes at the same sizes)
+    HIP_TRY(hipFuncSetAttribute((const void *)solve_block_kernel<kThreadsS, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_s));
+    HIP_TRY(hipFuncSetAttribute((const void *)solve_block_kernel<kThreadsM, true>, hipFuncAttributeMaxDynamicSharedMemorySize, std::max(lds_m, kThreadsM == kThreadsS ? lds_s : 0)));
+    HIP_TRY(hipFuncSetAttribute((const void *)solve_block_kernel<kThreadsL, true>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                std::max(lds_l, std::max(kThreadsL == kThreadsM ? lds_m : 0, kThreadsL == kThreadsS ? lds_s : 0))));
     return LFR_OK;
 }
 
 void launch_packed(const KernelArgs &a, const PackedRanges &r, bool fused, int n_blocks, hipStream_t cs) {
     const dim3 blk(64 * kPackedWaves);
-    if (fused) hipLaunchKernelGGL(solve_packed_kernel<true>, dim3(n_blocks), blk, 0, cs, a, r);
+    if (a.x_start) hipLaunchKernelGGL((solve_packed_kernel<false, true>), dim3(n_blocks), blk, 0, cs, a, r);     // (the caller has materialised the records)
+    else if (fused) hipLaunchKernelGGL(solve_packed_kernel<true>, dim3(n_blocks), blk, 0, cs, a, r);
     else hipLaunchKernelGGL(solve_packed_kernel<false>, dim3(n_blocks), blk, 0, cs, a, r);
 }
 
 void launch_group_class(int cls, const KernelArgs &a, bool fused, int n_blocks, hipStream_t st) {
     const dim3 grid(n_blocks), blk(64 * kPackedWaves);
+    if (a.x_start) {       // the warm form exists as solve_packed_kernel only: that launch with every block in this class's range
+        static const int kSlot[KC_BLOCK] = {4, 3, 2, 1, 0};      // PackedRanges' dispatch order: G64_4, G64_2, G32, G16, G8
+        static_assert(KC_G8 == 0 && KC_G16 == 1 && KC_G32 == 2 && KC_G64_2 == 3 && KC_G64_4 == 4, "packed classes");
+        PackedRanges r;
+        for (int i = 0; i < 5; ++i) { r.desc_begin[i] = r.desc_end[i] = a.desc_begin; }
+        for (int i = 0; i < 6; ++i) r.blk_begin[i] = i <= kSlot[cls] ? 0 : n_blocks;
+        r.desc_begin[kSlot[cls]] = a.desc_begin; r.desc_end[kSlot[cls]] = a.desc_end;
+        launch_packed(a, r, false, n_blocks, st);
+        return;
+    }
     switch (cls) {
         case lfr::KC_G8:    if (fused) hipLaunchKernelGGL((solve_group_kernel<8, 1, 3, true>), grid, blk, 0, st, a); else hipLaunchKernelGGL((solve_group_kernel<8, 1, 3, false>), grid, blk, 0, st, a); break;
         case lfr::KC_G16:   if (fused) hipLaunchKernelGGL((solve_group_kernel<16, 1, 6, true>), grid, blk, 0, st, a); else hipLaunchKernelGGL((solve_group_kernel<16, 1, 6, false>), grid, blk, 0, st, a); break;
@@ -3229,6 +3292,14 @@ void launch_group_class(int cls, const KernelArgs &a, bool fused, int n_blocks, 
 
 void launch_block_class(int cls, const KernelArgs &a, int rows, int wgs, hipStream_t cs) {
     const size_t lds = block_lds_bytes(rows);
+    if (a.x_start) {
+        switch (cls) {
+            case lfr::KC_BLOCK:   hipLaunchKernelGGL((solve_block_kernel<kThreadsS, true>), dim3(wgs), dim3(kThreadsS), lds, cs, a, rows); break;
+            case lfr::KC_BLOCK_M: hipLaunchKernelGGL((solve_block_kernel<kThreadsM, true>), dim3(wgs), dim3(kThreadsM), lds, cs, a, rows); break;
+            case lfr::KC_BLOCK_L: hipLaunchKernelGGL((solve_block_kernel<kThreadsL, true>), dim3(wgs), dim3(kThreadsL), lds, cs, a, rows); break;
+        }
+        return;
+    }
     switch (cls) {
         case lfr::KC_BLOCK:   hipLaunchKernelGGL((solve_block_kernel<kThreadsS>), dim3(wgs), dim3(kThreadsS), lds, cs, a, rows); break;
         case lfr::KC_BLOCK_M: hipLaunchKernelGGL((solve_block_kernel<kThreadsM>), dim3(wgs), dim3(kThreadsM), lds, cs, a, rows); break;
@@ -3237,6 +3308,11 @@ void launch_block_class(int cls, const KernelArgs &a, int rows, int wgs, hipStre
 }
 
 void launch_tree(const KernelArgs &a, bool team, int grid, hipStream_t cs) {
+    if (a.x_start) {
+        if (team) hipLaunchKernelGGL((solve_tree_team_kernel<kThreadsG, true>), dim3(grid), dim3(kThreadsG), 0, cs, a);
+        else hipLaunchKernelGGL((solve_tree_kernel<kThreadsG, true>), dim3(grid), dim3(kThreadsG), 0, cs, a);
+        return;
+    }
     if (team) hipLaunchKernelGGL((solve_tree_team_kernel<kThreadsG>), dim3(grid), dim3(kThreadsG), 0, cs, a);
     else hipLaunchKernelGGL((solve_tree_kernel<kThreadsG>), dim3(grid), dim3(kThreadsG), 0, cs, a);
 }

@@ -13,6 +13,9 @@ assembly ONCE and gives every later forward new flows (and similarities) into th
         pos = r(disp1, disp2)           # set_inputs + solve + positions on torch's current stream, no host synchronisation
         loss(pos).backward()
 
+Refiner(..., warm_start=True) starts every forward after the first at the previous forward's positions (lfr_batch_solve_from) instead
+of the origin: flows that moved a little need fewer LM iterations.  reset_start() makes the next forward a cold one again.
+
 hessian="gauss_newton" (refine and Refiner) takes the implicit gradient with H = J^T J instead of the exact Hessian
 (LFR_BACKWARD_GAUSS_NEWTON): components whose exact Hessian is indefinite - zero gradient in the default mode - get one too.
 
@@ -169,12 +172,17 @@ class Refiner:
     the similarities stay, no gradient).  Tensors as for refine(), in the caller's rows (banned pairs included).  The forward issues
     set_inputs, solve and the positions' copy on torch's current stream and does not synchronise the host.  The batch is shared and
     holds only its latest solve: backward() of an older forward raises RuntimeError; several backwards of the latest one are fine.
+    warm_start=True: every forward after the first starts LM at the previous forward's positions (Batch.solve_from(None)) instead of
+    the origin; reset_start() makes the next forward cold again.  The backward is the same either way: the implicit gradient is taken
+    at the solution and does not know where LM started.
     hessian: as for refine().  node_image, node_feature, n_nodes: as refine() returns them.  covariance(f64=True): lfr_batch_covariance of the latest solve.
     evaluate(positions=None, **kw): lfr_batch_evaluate (cost, dF/dx, residuals, loss weights), detached."""
 
     def __init__(self, disp1, disp2, sim, *, image_names, pair_img1, pair_img2, pair_off, feat1, feat2, image_facts=None, banned=(),
-                 tukey_variant="ceres1", hessian="exact"):
+                 tukey_variant="ceres1", hessian="exact", warm_start=False):
         self._gauss_newton = _check_hessian("Refiner", hessian)
+        self._warm_start = bool(warm_start)
+        self._have_start = False        # the batch's positions are a forward's result
         pair_img1 = np.ascontiguousarray(pair_img1, np.int32)
         pair_img2 = np.ascontiguousarray(pair_img2, np.int32)
         pair_off = np.ascontiguousarray(pair_off, np.int64)
@@ -217,12 +225,21 @@ class Refiner:
             s = None if sim is None else rows(sim, (-1,))
             # (d1, d2, s may be temporaries: they are read by work enqueued here, and torch reuses their memory in stream order)
             self._batch.set_inputs(d1, d2, s)
-            self._batch.solve(stream=torch.cuda.current_stream(self.device).cuda_stream, want_stats=False)
+            stream = torch.cuda.current_stream(self.device).cuda_stream
+            if self._warm_start and self._have_start:
+                self._batch.solve_from(None, stream=stream, want_stats=False)
+            else:
+                self._batch.solve(stream=stream, want_stats=False)
+            self._have_start = True
         self._epoch += 1
         return self._epoch
 
     def __call__(self, disp1, disp2, sim=None):
         return _RefinerStep.apply(disp1, disp2, sim, self)
+
+    def reset_start(self):
+        """warm_start=True: the next forward starts at the origin, like the first one (the ones after it are warm again)."""
+        self._have_start = False
 
     def covariance(self, f64=True):
         """[n_nodes, 3] device tensor of lfr_batch_covariance for the latest forward (detached: the covariance is not differentiated)."""

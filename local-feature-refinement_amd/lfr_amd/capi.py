@@ -131,6 +131,7 @@ def lib():
         "lfr_batch_create": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, pp]),
         "lfr_batch_free": (None, [vp]),
         "lfr_batch_solve": (C.c_int, [vp, vp, C.POINTER(SolveStats)]),
+        "lfr_batch_solve_from": (C.c_int, [vp, vp, vp, C.POINTER(SolveStats)]),
         "lfr_batch_download": (C.c_int, [vp, vp]),
         "lfr_batch_positions_view": (C.c_int, [vp, pp]),
         "lfr_batch_positions_view_f32": (C.c_int, [vp, pp]),
@@ -177,7 +178,7 @@ EXPORTS = ["lfr_version", "lfr_last_error", "lfr_graph_from_files", "lfr_graph_f
            "lfr_problem_build_hip_ex", "lfr_problem_build_hip_shard", "lfr_problem_cc_sharded", "lfr_hip_reserve", "lfr_hip_trim", "lfr_batch_positions_view", "lfr_batch_positions_view_f32", "lfr_bisect_graph", "lfr_debug_eval_edges", "lfr_debug_ls_next_step", "lfr_debug_solve_damped", "lfr_debug_tree_plan", "lfr_debug_solve_tree", "lfr_debug_pool_selftest", "lfr_debug_sort_pairs", "lfr_debug_exclusive_sum", "lfr_debug_recursive_cut", "lfr_hip_synchronize", "lfr_graph_free", "lfr_graph_num_nodes", "lfr_graph_num_edges",
            "lfr_graph_num_images", "lfr_graph_get_nodes", "lfr_graph_image_name", "lfr_graph_image_fact",
            "lfr_write_matching_file", "lfr_problem_build", "lfr_problem_build_labels", "lfr_problem_build_hip", "lfr_problem_free", "lfr_problem_get_stats",
-           "lfr_problem_get_labels", "lfr_problem_shard_components", "lfr_hip_warmup", "lfr_batch_create", "lfr_batch_free", "lfr_batch_solve",
+           "lfr_problem_get_labels", "lfr_problem_shard_components", "lfr_hip_warmup", "lfr_batch_create", "lfr_batch_free", "lfr_batch_solve", "lfr_batch_solve_from",
            "lfr_batch_download", "lfr_batch_timing", "lfr_batch_spin_timeouts", "lfr_batch_team_runs", "lfr_batch_team_fallbacks", "lfr_debug_occupy", "lfr_batch_tree_stats", "lfr_batch_component_info", "lfr_batch_positions_to_device", "lfr_batch_backward", "lfr_batch_backward_status", "lfr_batch_set_inputs", "lfr_batch_covariance", "lfr_batch_covariance_status", "lfr_batch_evaluate", "lfr_keypoint_covariances", "lfr_debug_invert_spd", "lfr_solve_hip", "lfr_solve_hip_multi", "lfr_solve_graph_hip_multi", "lfr_write_solution", "lfr_apply_displacements"]
 
 
@@ -605,6 +606,24 @@ class Batch:
         st = SolveStats()
         _check(lib().lfr_batch_solve(self._h, C.c_void_p(stream) if stream else None,
                                      C.byref(st) if want_stats else None))
+        return st.as_dict() if want_stats else None
+
+    def solve_from(self, initial=None, stream=None, want_stats=True):
+        """The solve started at given positions (lfr_batch_solve_from, include/lfr.h): `initial` is a contiguous [n_nodes, 2] float64
+        tensor on the batch's device, read by work enqueued in this call only, or None = the batch's own positions, in place (the
+        latest solve's result; zeros before the first).  Every coordinate is clamped to [-1, 1], a NaN reads as 0; from there on the
+        loop is solve()'s.  stream: a hipStream_t as int, or None = the default stream as for solve()."""
+        ptr = None
+        if initial is not None:
+            import torch
+            n = self.problem.graph.n_nodes
+            if (not isinstance(initial, torch.Tensor) or not initial.is_cuda or initial.device != torch.device("cuda", self.device)
+                    or initial.dtype != torch.float64 or not initial.is_contiguous() or tuple(initial.shape) != (n, 2)):
+                raise ValueError("solve_from: need a contiguous [%d, 2] float64 tensor on cuda:%d" % (n, self.device))
+            ptr = C.c_void_p(initial.data_ptr() or 1)       # (no nodes: an empty tensor has no address, and nothing is read)
+        st = SolveStats()
+        _check(lib().lfr_batch_solve_from(self._h, ptr, C.c_void_p(stream) if stream else None,
+                                          C.byref(st) if want_stats else None))
         return st.as_dict() if want_stats else None
 
     def timing(self, solves_back=0):
