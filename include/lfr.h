@@ -474,6 +474,40 @@ int lfr_batch_covariance(lfr_batch *b, void *cov_device, int flags, void *hip_st
 /* Per component (order of lfr_batch_component_info) of the latest covariance: 0 computed, 1 not usable, 2 singular.  Waits for that
  * call.  Returns the count (< 0: error, LFR_ERR_ARG before the first lfr_batch_covariance). */
 int64_t lfr_batch_covariance_status(lfr_batch *b, int32_t *status);
+/* Covariance between matched keypoints: what ceres::Covariance gives for a list of parameter-block PAIRS, with the graph's matches as
+ * the list.  The nodes of a component are strongly correlated through its root, so the uncertainty of a match's relative displacement
+ * x_node2 - x_node1 is not the sum of the two node blocks but
+ *     D = Cov(x_2 - x_1) = C_11 + C_22 - C_12 - C_12^T,
+ * and forming it downstream from float32 pieces cancels most of its digits.  The contract is that of lfr_batch_covariance - the same
+ * A, the same usable components, the same status codes, taken after the latest solve (LFR_ERR_ARG before the first solve and between
+ * an lfr_batch_set_inputs and the next solve), float32 outputs or double with LFR_COVARIANCE_F64, float32 = the fp64 value rounded
+ * once - and the three outputs come from ONE assembly and ONE inversion per component.  Everything is in the solver's unit squared
+ * and in the axis order of `positions`; there is no pixel mapping of the per-match outputs.
+ *   - cov_device (may be NULL): 3 per node, exactly what lfr_batch_covariance writes, bit for bit;
+ *   - cross_device (may be NULL): n_matches x 4 in the MATCH layout of lfr_batch_backward / lfr_batch_set_inputs / lfr_batch_evaluate.
+ *     Row m = Cov(x_node1, x_node2) row-major: C(1di,2di), C(1di,2dj), C(1dj,2di), C(1dj,2dj).  0 where the true value is 0 or where
+ *     there is no covariance: an end that is a root or another constant node, the two ends in different components (a dropped edge:
+ *     independent, so exactly 0), a match outside the shard, a component with status 1 or 2;
+ *   - rel_device (may be NULL): n_matches x 3, D(di,di), D(di,dj), D(dj,dj), formed in fp64 inside the kernel before any rounding to
+ *     float32.  A constant end contributes zeros: a match with one constant end gets the other end's node block bit for bit.  A match
+ *     whose direction node1->node2 is no residual block of this shard - a dropped edge, two constant ends, a match outside the shard -
+ *     gets (-1, 0, -1): a negative variance is the "not in the program" mark, as lfr_batch_evaluate's weight -1.  A match of a
+ *     status 1 / 2 component gets zeros, "no covariance", as in the node output;
+ *   - whole arrays are overwritten.  All three outputs NULL, or a flag bit other than LFR_COVARIANCE_F64: LFR_ERR_ARG.  A batch over
+ *     one rank's connected components (lfr_problem_cc_sharded = 1) numbers its matches by itself: LFR_ERR_UNSUPPORTED when a per-match
+ *     output is asked for; cov alone is served.  Components above 6144 rows: LFR_ERR_UNSUPPORTED;
+ *   - every match row is written once by a fixed rule (the record of direction node1->node2 writes it), no fp64 value goes through a
+ *     global-memory atomic; results are bitwise repeatable, identical for host- and device-assembled batches, and components that
+ *     share a wavefront do not influence each other, bit for bit;
+ *   - lfr_batch_covariance_status serves this call too (the two calls share one pass state: it reports whichever ran last); streams,
+ *     events and the asynchronous-unless-stats rule are those of lfr_batch_covariance.  The first call on a batch whose records do not
+ *     carry their directed-edge ids builds the record -> edge map (a synchronising step; the graph must still be alive).
+ * Kernels: up to 32 rows ONE launch in the covariance's packed layout - after the in-register inversion every row lane puts its row
+ * of C into the group's LDS, then the lanes re-read their records' words and the node1->node2 records write their match; above, one
+ * workgroup per component: the node blocks as in lfr_batch_covariance, then per node a back substitution c = L^-T D^-1 w for its two
+ * full columns of C and a walk over the node's incident records. */
+int lfr_batch_covariance_matches(lfr_batch *b, void *cov_device, void *cross_device, void *rel_device, int flags, void *hip_stream,
+                                 lfr_covariance_stats *stats);
 /* Consumer side, the counterpart of lfr_apply_displacements (colmap_utils.py:126-137): per feature of `image_name` the 2x2 covariance
  * in PIXELS and in keypoint (x, y) order, (16 * fact)^2 * [[C(dj,dj), C(di,dj)], [C(di,dj), C(di,di)]], as out[3f + 0..2] = xx, xy,
  * yy.  cov: 3 * n_nodes doubles on the host.  Features the graph does not know, roots and unsolved nodes get 0.  Host code. */

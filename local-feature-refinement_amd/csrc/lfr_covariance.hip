@@ -210,6 +210,286 @@ __global__ __launch_bounds__(T) void covariance_block_kernel(const CovBlockArgs 
     if (tid == 0) a.status[di] = 0;
 }
 
+// =============================================================================================
+// covariance between matched keypoints (lfr_batch_covariance_matches): the node blocks as above, and per match of the
+// graph the cross block C_12 and D = C_11 + C_22 - C_12 - C_12^T.  Kernels of their own: the two above keep their code.
+// Who writes match m: the record of its direction node1 -> node2 (even directed-edge id) - it exists whenever the match is in the
+// program, and once.  The rows of the other matches keep what the host put there before the launches.
+// =============================================================================================
+struct MatchOut {
+    const uint32_t *eid;       // per record: directed edge id of the graph (2m: node1 -> node2, 2m+1: node2 -> node1)
+    void *cross, *rel;         // n_matches x 4 (cleared) / n_matches x 3 (set to -1, 0, -1), float or double; either may be nullptr
+    uint32_t n_matches;
+    int f64;
+};
+
+template <int N>
+__device__ __forceinline__ void match_store(void *out, const int f64, const uint32_t m, const double (&v)[N]) {
+    if (!out) return;
+    if (f64) {
+        double *o = static_cast<double *>(out) + N * (size_t)m;
+#pragma unroll
+        for (int i = 0; i < N; ++i) o[i] = v[i];
+    } else {
+        float *o = static_cast<float *>(out) + N * (size_t)m;
+#pragma unroll
+        for (int i = 0; i < N; ++i) o[i] = (float)v[i];
+    }
+}
+
+// D of a match with two variable ends from the two node blocks a, b (C(di,di), C(di,dj), C(dj,dj)) and the cross block c (row-major):
+// two sums of like terms and one difference per entry, all in fp64 (2 c is exact), so at most 4 ulp of the largest term
+__device__ __forceinline__ void match_rel(const double (&a)[3], const double (&b)[3], const double (&c)[4], double (&d)[3]) {
+    d[0] = (a[0] + b[0]) - 2.0 * c[0];
+    d[1] = (a[1] + b[1]) - (c[1] + c[2]);
+    d[2] = (a[2] + b[2]) - 2.0 * c[3];
+}
+
+struct CovMatchArgs {
+    CovArgs c;                 // (cov may be nullptr here)
+    MatchOut m;
+};
+
+// cov_group_body, and behind the inversion: every row lane puts its row of C into the group's LDS matrix (the assembled A is dead by
+// then), then sub-lane sl re-reads the words of records sl + S k and the node1 -> node2 records write their match
+template <int CLS, int EPL, bool FUSED>
+__device__ __forceinline__ void cov_match_group_body(const CovMatchArgs &ma, const int desc_begin, const int desc_end, const int block_in_class,
+                                                     unsigned char *lds_raw) {
+    constexpr int NV = CLS == 0 ? 8 : CLS == 1 ? 16 : 32, LPR = CLS == 3 ? 2 : 1;
+    constexpr int S = NV * LPR, G = 64 / S, LD = NV + 1;
+    const CovArgs &ca = ma.c;
+    const KernelArgs &a = ca.k;
+    const int lane = threadIdx.x & 63;
+    const int gid = lane / S, sl = lane % S;
+    const int row = sl % NV, part = sl / NV;
+    const int ci0 = desc_begin + block_in_class * G;
+    if (ci0 >= desc_end) return;                      // wave-uniform
+    const int ci = ci0 + gid;
+    const bool have = ci < desc_end;
+    CovLds<NV> &L = reinterpret_cast<CovLds<NV> *>(lds_raw)[gid];
+
+    CompDesc d;
+    d.edge_off = 0; d.n_edges = 0; d.node_off = 0; d.n_nodes = 0; d.n_var = 0;
+    if (have) d = a.descs[ci];
+    const bool usable = have && a.infos[ci].termination != LFR_TERM_FAILURE;
+    const int n_var = usable ? d.n_var : 0, nv2 = 2 * n_var, E = usable ? (int)d.n_edges : 0;     // a group without a usable component inverts the identity
+    const bool is_row = row < nv2;
+    const int nv2_max = cov_wave_max(nv2);
+    const uint32_t node = is_row ? a.node_ids[d.node_off + (row >> 1)] : 0u;
+
+    cov_lds_init<NV, S>(a, d, n_var, sl, L);
+    wave_lds_sync();
+    cov_assemble<NV, S, EPL, FUSED>(a, d, n_var, E, sl, L);      // one sweep at x^
+    wave_lds_sync();
+
+    // ---- inversion, lane = row ----
+    double *A = L.A;
+    bool solved = false;
+    cov_invert<CLS>(row, nv2_max,
+        [&](int c) -> double {
+            double v = 0.0;
+            if (is_row && c < nv2) v = (c <= row ? A[row * LD + c] : A[c * LD + row]);
+            return (!is_row && c == row) ? 1.0 : v;                  // padded rows are identity
+        },
+        [&](auto &h, const bool ok) {
+            constexpr int CL = sizeof(h) / sizeof(double);
+            double dg = 0.0, off = 0.0;                              // C(row,row), C(row,row+1)
+#pragma unroll
+            for (int c = 0; c < CL; ++c) { dg = (c == row) ? h[c] : dg; off = (c == row + 1) ? h[c] : off; }
+            const double dg_next = dpp_f64<kDppQuadXor1>(dg);       // the odd lane's diagonal, to the even lane of the node
+            if (ca.cov && is_row && part == 0 && !(row & 1) && ok) cov_store(ca, node, dg, off, dg_next);
+            if (have && sl == 0) ca.status[ci] = !usable ? 1 : ok ? 0 : 2;
+            if (is_row && part == 0) {                               // row `row` of C over the dead A (CL <= NV < LD)
+#pragma unroll
+                for (int c = 0; c < CL; ++c) A[row * LD + c] = h[c];
+            }
+            solved = ok;
+        });
+    wave_lds_sync();
+
+    // ---- the matches of the re-read records ----
+    const int E_all = have ? (int)d.n_edges : 0;
+    const bool good = usable && solved;                // otherwise: zeros, "no covariance", for every match of the component's program
+#pragma unroll 1
+    for (int p = sl; p < E_all; p += S) {
+        const uint32_t rec = d.edge_off + (uint32_t)p, id = ma.m.eid[rec], m = id >> 1;
+        if ((id & 1u) || m >= ma.m.n_matches) continue;
+        double cr[4] = {0.0, 0.0, 0.0, 0.0}, rl[3] = {0.0, 0.0, 0.0};
+        if (good) {
+            const uint32_t word = FUSED ? a.edge_word[rec] : reinterpret_cast<const uint32_t *>(a.edges + rec)[19];
+            const int s = (int)(word & 0xffffu), t = (int)((word >> 16) & 0x7fffu);
+            const bool vs = s < n_var, vt = t < n_var;
+            if (!vs && !vt) continue;                  // (cannot happen: an edge between two constants is no record)
+            const int r1 = 2 * (vs ? s : t), r2 = 2 * t;
+            const double b1[3] = {A[r1 * LD + r1], A[r1 * LD + r1 + 1], A[(r1 + 1) * LD + r1 + 1]};      // as cov_store takes them
+            if (vs && vt) {
+                const double b2[3] = {A[r2 * LD + r2], A[r2 * LD + r2 + 1], A[(r2 + 1) * LD + r2 + 1]};
+                cr[0] = A[r1 * LD + r2]; cr[1] = A[r1 * LD + r2 + 1]; cr[2] = A[(r1 + 1) * LD + r2]; cr[3] = A[(r1 + 1) * LD + r2 + 1];
+                match_rel(b1, b2, cr, rl);
+            } else { rl[0] = b1[0]; rl[1] = b1[1]; rl[2] = b1[2]; }       // a constant end contributes zeros: the other end's block
+        }
+        match_store<4>(ma.m.cross, ma.m.f64, m, cr);
+        match_store<3>(ma.m.rel, ma.m.f64, m, rl);
+    }
+}
+
+template <bool FUSED>
+__global__ __launch_bounds__(64, 2) void covariance_matches_packed_kernel(const CovMatchArgs a, const PackedRanges r) {
+    __shared__ __attribute__((aligned(16))) unsigned char lds_raw[kCovPackedLdsBytes];
+    const int b = (int)blockIdx.x;
+    if (b < r.blk_begin[1]) cov_match_group_body<3, 5, FUSED>(a, r.desc_begin[0], r.desc_end[0], b - r.blk_begin[0], lds_raw);
+    else if (b < r.blk_begin[2]) cov_match_group_body<2, 6, FUSED>(a, r.desc_begin[1], r.desc_end[1], b - r.blk_begin[1], lds_raw);
+    else if (b < r.blk_begin[3]) { /* retired class, never assigned */ }
+    else if (b < r.blk_begin[4]) cov_match_group_body<1, 6, FUSED>(a, r.desc_begin[3], r.desc_end[3], b - r.blk_begin[3], lds_raw);
+    else cov_match_group_body<0, 3, FUSED>(a, r.desc_begin[4], r.desc_end[4], b - r.blk_begin[4], lds_raw);
+}
+
+// ---- workgroup classes ----
+struct CovMatchBlockArgs {
+    CovBlockArgs c;            // (cov may be nullptr here; c.b.eid: the record -> directed-edge map)
+    MatchOut m;
+    double *diag;              // 3 per node entry of the batch (node_off + l): the node blocks in fp64, from the first pass to the second
+};
+
+// covariance_block_kernel's assembly, LDL^T and first pass (the node blocks, which also go to `diag`), then a second pass: per node l
+// its two columns of W = L^-1 again, the back substitution c = L^-T D^-1 w - the node's two full columns of C in the wave's vectors -
+// and a walk over the node's incident records: its out-edges l -> m with an even edge id are the matches node l owns (cross block
+// C(2l+p, 2m+q) = c_p[2m+q]; a constant m: D = the node's block), and of its in-edges those from a constant node1, which has no column
+// of its own.  Nodes dealt to waves, every sum in a fixed order.
+template <int T, bool LDS_MATRIX>
+__global__ __launch_bounds__(T) void covariance_matches_block_kernel(const CovMatchBlockArgs ma) {
+    extern __shared__ double bsh[];
+    const CovBlockArgs &ca = ma.c;
+    const BwdArgs &a = ca.b;
+    const int di = a.desc_begin + blockIdx.x, tid = threadIdx.x;
+    const CompDesc d = a.descs[di];
+    const int nv = d.n_var, n = 2 * nv;
+    const EdgeRec *E = a.edges + d.edge_off;
+    const uint32_t *ids = a.node_ids + d.node_off;
+    const uint32_t *eid = a.eid + d.edge_off;
+    auto no_covariance = [&](const int status) {             // zeros for every match of the component's program (the node output was cleared)
+        const double z3[3] = {0.0, 0.0, 0.0};
+        for (uint32_t p = tid; p < d.n_edges; p += T) {
+            const uint32_t id = eid[p];
+            if (!(id & 1u) && (id >> 1) < ma.m.n_matches) match_store<3>(ma.m.rel, ma.m.f64, id >> 1, z3);
+        }
+        if (tid == 0) a.status[di] = status;
+    };
+    if (a.infos[di].termination == LFR_TERM_FAILURE) { no_covariance(1); return; }      // not usable
+    double *H = LDS_MATRIX ? bsh : a.hws + a.hws_off[di];
+    double *scratch = LDS_MATRIX ? bsh + bwd_tri(n, 0) : bsh;
+    double *lval = scratch;                                   // the factorization's column buffer; afterwards the waves' vectors
+    int *lidx = reinterpret_cast<int *>(lval + n);
+    __shared__ int cnt[2];
+
+    const size_t nt = bwd_tri(n, 0);
+    for (size_t t = tid; t < nt; t += T) H[t] = 0.0;
+    if (tid == 0) { cnt[0] = 0; cnt[1] = 0; }
+    __syncthreads();
+    bwd_assemble<T, false>(a, d, nv, E, ids, H, nullptr, tid);
+    __syncthreads();
+    if (bwd_ldlt<T>(H, n, lval, lidx, cnt, tid)) { no_covariance(2); return; }         // singular
+    __syncthreads();
+
+    const int lane = tid & 63, wv = tid >> 6;
+    const int ww = min(T / 64, ca.scratch_doubles / (2 * n));  // waves that have room for their two vectors (>= 1: the launch sizes the LDS)
+    double *w0 = scratch + (size_t)min(wv, ww - 1) * 2 * n, *w1 = w0 + n;
+    double *diag = ma.diag + 3 * (size_t)d.node_off;
+    // first pass: the node blocks, as covariance_block_kernel sums them
+    if (wv < ww) {
+        for (int l = wv; l < nv; l += ww) {
+            const int i0 = 2 * l;
+            for (int r = i0 + lane; r < n; r += 64) { w0[r] = (r == i0) ? 1.0 : 0.0; w1[r] = (r == i0 + 1) ? 1.0 : 0.0; }
+            wave_lds_sync();
+            double c00 = 0.0, c01 = 0.0, c11 = 0.0;
+            for (int k = i0; k < n; ++k) {
+                const double u = w0[k], v = w1[k];             // (wave-uniform)
+                if (u == 0.0 && v == 0.0) continue;
+                const double dinv = 1.0 / H[bwd_tri(k, k)];
+                c00 += u * u * dinv; c01 += u * v * dinv; c11 += v * v * dinv;
+                for (int r = k + 1 + lane; r < n; r += 64) {
+                    const double lrk = H[bwd_tri(r, k)];
+                    if (lrk != 0.0) { w0[r] -= lrk * u; w1[r] -= lrk * v; }
+                }
+                wave_lds_sync();
+            }
+            if (lane == 0) {
+                diag[3 * l] = c00; diag[3 * l + 1] = c01; diag[3 * l + 2] = c11;
+                if (ca.cov && ca.f64) { double *o = static_cast<double *>(ca.cov) + 3 * (size_t)ids[l]; o[0] = c00; o[1] = c01; o[2] = c11; }
+                else if (ca.cov) { float *o = static_cast<float *>(ca.cov) + 3 * (size_t)ids[l]; o[0] = (float)c00; o[1] = (float)c01; o[2] = (float)c11; }
+            }
+            wave_lds_sync();
+        }
+    }
+    __syncthreads();                                          // every node block is in `diag`
+    // second pass: full columns and the matches
+    if (wv < ww) {
+        for (int l = wv; l < nv; l += ww) {
+            const int i0 = 2 * l;
+            for (int r = lane; r < n; r += 64) { w0[r] = (r == i0) ? 1.0 : 0.0; w1[r] = (r == i0 + 1) ? 1.0 : 0.0; }
+            wave_lds_sync();
+            for (int k = i0; k < n; ++k) {                    // w = L^-1 e
+                const double u = w0[k], v = w1[k];             // (wave-uniform)
+                if (u == 0.0 && v == 0.0) continue;
+                for (int r = k + 1 + lane; r < n; r += 64) {
+                    const double lrk = H[bwd_tri(r, k)];
+                    if (lrk != 0.0) { w0[r] -= lrk * u; w1[r] -= lrk * v; }
+                }
+                wave_lds_sync();
+            }
+            for (int r = i0 + lane; r < n; r += 64) { const double dr = H[bwd_tri(r, r)]; w0[r] /= dr; w1[r] /= dr; }
+            wave_lds_sync();
+            for (int i = n - 1; i > 0; --i) {                 // c = L^-T (D^-1 w): row i of L is contiguous
+                const double u = w0[i], v = w1[i];             // (wave-uniform, final)
+                if (u == 0.0 && v == 0.0) continue;
+                const double *Li = H + bwd_tri(i, 0);
+                for (int k = lane; k < i; k += 64) {
+                    const double lik = Li[k];
+                    if (lik != 0.0) { w0[k] -= lik * u; w1[k] -= lik * v; }
+                }
+                wave_lds_sync();
+            }
+            const lfr::NodeInc ni = a.node_inc[d.node_off + l];
+            const double own[3] = {diag[3 * l], diag[3 * l + 1], diag[3 * l + 2]};
+            for (uint32_t k = lane; k < ni.out_count; k += 64) {          // l -> m
+                const uint32_t p = ni.out_begin + k;
+                if (p >= d.n_edges) break;                    // (cannot happen: a run lies inside its component)
+                const uint32_t id = eid[p], mt = id >> 1;
+                if ((id & 1u) || mt >= ma.m.n_matches) continue;
+                const int m = E[p].dst_kind & 0x7fff;
+                double cr[4] = {0.0, 0.0, 0.0, 0.0}, rl[3] = {own[0], own[1], own[2]};
+                if (m < nv) {
+                    const double other[3] = {diag[3 * m], diag[3 * m + 1], diag[3 * m + 2]};
+                    cr[0] = w0[2 * m]; cr[1] = w0[2 * m + 1]; cr[2] = w1[2 * m]; cr[3] = w1[2 * m + 1];
+                    match_rel(own, other, cr, rl);
+                }
+                match_store<4>(ma.m.cross, ma.m.f64, mt, cr);
+                match_store<3>(ma.m.rel, ma.m.f64, mt, rl);
+            }
+            for (uint32_t k = lane; k < ni.in_count; k += 64) {           // a constant node1 -> l
+                if (ni.in_begin + k >= d.n_edges) break;
+                const uint32_t p = a.in_idx[d.edge_off + ni.in_begin + k];
+                if (p >= d.n_edges) break;
+                const uint32_t id = eid[p], mt = id >> 1;
+                if ((id & 1u) || mt >= ma.m.n_matches || (int)E[p].src < nv) continue;
+                const double cr[4] = {0.0, 0.0, 0.0, 0.0};
+                match_store<4>(ma.m.cross, ma.m.f64, mt, cr);
+                match_store<3>(ma.m.rel, ma.m.f64, mt, own);
+            }
+            wave_lds_sync();
+        }
+    }
+    if (tid == 0) a.status[di] = 0;
+}
+
+// the rows of `rel` that no record writes: (-1, 0, -1), "not in the program"
+__global__ void k_cov_fill_rel(size_t n_matches, void *out, int f64) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= 3 * n_matches) return;
+    const double v = (i % 3 == 1) ? 0.0 : -1.0;
+    if (f64) static_cast<double *>(out)[i] = v; else static_cast<float *>(out)[i] = (float)v;
+}
+
 size_t cov_scratch_bytes(int rows) { return std::max<size_t>((size_t)rows * 12, (size_t)rows * 16 * (kCovThreads / 64)) + 16; }
 // dynamic LDS of a launch whose largest component has `rows` rows; scratch_doubles: what lies behind the matrix
 size_t cov_lds_bytes(int rows, bool lds_matrix, int &scratch_doubles) {
@@ -225,10 +505,21 @@ int cov_setup_extra(lfr_batch *, lfr::PassState *) {
                                 (int)cov_lds_bytes(lfr::kBlockMaxRows, true, sd)));
     HIP_TRY(hipFuncSetAttribute((const void *)covariance_block_kernel<kCovThreads, false>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                 (int)cov_lds_bytes(kBwdMaxRows, false, sd)));
+    HIP_TRY(hipFuncSetAttribute((const void *)covariance_matches_block_kernel<kCovThreads, true>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                (int)cov_lds_bytes(lfr::kBlockMaxRows, true, sd)));
+    HIP_TRY(hipFuncSetAttribute((const void *)covariance_matches_block_kernel<kCovThreads, false>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                (int)cov_lds_bytes(kBwdMaxRows, false, sd)));
     return LFR_OK;
 }
 
-const lfr::PassKind kCovariance = {"covariance", [] { return new lfr::PassState(); }, cov_setup_extra};
+// the shared state of a pass behind a solve (lfr_batch.hpp) + what lfr_batch_covariance_matches keeps, made on its first call: the
+// fp64 node blocks of the workgroup classes between their two passes
+struct CovState : lfr::PassState {
+    lfr::DevArena match_slab;
+    double *d_diag = nullptr;
+};
+
+const lfr::PassKind kCovariance = {"covariance", [] { return static_cast<lfr::PassState *>(new CovState()); }, cov_setup_extra};
 
 }  // namespace
 
@@ -276,6 +567,89 @@ int lfr_batch_covariance(lfr_batch *b, void *cov_device, int flags, void *hip_st
         } else {
             const size_t lds = cov_lds_bytes(rows, true, c.scratch_doubles);
             hipLaunchKernelGGL((covariance_block_kernel<kCovThreads, true>), dim3(n), dim3(kCovThreads), lds, st, c);
+        }
+    }
+    HIP_TRY(hipGetLastError());
+    { const int rc = lfr::pass_end(&s, st); if (rc != LFR_OK) return rc; }
+    if (stats) {
+        int64_t count[3];
+        memset(stats, 0, sizeof(*stats));
+        { const int rc = lfr::pass_histogram(b, &s, st, count, &stats->kernel_ms); if (rc != LFR_OK) return rc; }
+        stats->n_computed = count[0]; stats->n_not_usable = count[1]; stats->n_singular = count[2];
+    }
+    return LFR_OK;
+}
+
+int lfr_batch_covariance_matches(lfr_batch *b, void *cov_device, void *cross_device, void *rel_device, int flags, void *hip_stream,
+                                 lfr_covariance_stats *stats) {
+    if (!b) { lfr::set_error("lfr_batch_covariance_matches: no batch"); return LFR_ERR_ARG; }
+    if (flags & ~LFR_COVARIANCE_F64) { lfr::set_error("lfr_batch_covariance_matches: unknown flag bits 0x%x", flags & ~LFR_COVARIANCE_F64); return LFR_ERR_ARG; }
+    if (!cov_device && !cross_device && !rel_device) {
+        lfr::set_error("lfr_batch_covariance_matches: nothing to compute (all three outputs are NULL)"); return LFR_ERR_ARG;
+    }
+    if (!cross_device && !rel_device) return lfr_batch_covariance(b, cov_device, flags, hip_stream, stats);      // the node output alone
+    if (b->cc_sharded) {
+        lfr::set_error("lfr_batch_covariance_matches: a batch over one rank's connected components numbers its matches by itself (lfr_problem_build_hip_shard): no per-match outputs");
+        return LFR_ERR_UNSUPPORTED;
+    }
+    hipStream_t st = (hipStream_t)hip_stream;
+    const int f64 = (flags & LFR_COVARIANCE_F64) ? 1 : 0;
+    const size_t M = (size_t)b->n_graph_matches, elt = f64 ? 8 : 4;
+    HIP_TRY(hipSetDevice(b->device));
+    if (b->n_solves > 0 && b->inputs_epoch == b->solved_epoch) {      // (otherwise pass_begin refuses the call)
+        const int rc = lfr::ensure_edge_map(b);       // records -> edges of the graph: the batch's own, shared with backward, set_inputs and evaluate
+        if (rc != LFR_OK) return rc;
+    }
+    { const int rc = lfr::pass_begin(b, &b->cov, kCovariance, 0, st); if (rc != LFR_OK) return rc; }
+    CovState &s = *static_cast<CovState *>(b->cov);
+    const bool any_block = b->class_begin[lfr::KC_COUNT] > b->class_begin[lfr::KC_BLOCK];
+    if (any_block && !s.d_diag) {
+        if (!s.match_slab.init(b->ctx, 24 * std::max<size_t>((size_t)b->n_nodes, 1) + 4096)) return LFR_ERR_NOMEM;
+        s.d_diag = s.match_slab.take_n<double>(3 * (size_t)b->n_nodes);
+        if (!s.d_diag) { s.match_slab.reset(); lfr::set_error("covariance: match slab exhausted"); return LFR_ERR_NOMEM; }
+    }
+    if (cov_device && b->n_graph_nodes) HIP_TRY(hipMemsetAsync(cov_device, 0, 3 * (size_t)b->n_graph_nodes * elt, st));
+    if (cross_device && M) HIP_TRY(hipMemsetAsync(cross_device, 0, 4 * M * elt, st));
+    if (rel_device && M) hipLaunchKernelGGL(k_cov_fill_rel, dim3((unsigned)((3 * M + 255) / 256)), dim3(256), 0, st, M, rel_device, f64);
+    MatchOut mo;
+    mo.eid = lfr::edge_map(b); mo.cross = cross_device; mo.rel = rel_device; mo.n_matches = (uint32_t)M; mo.f64 = f64;
+    {   // packed classes: one launch of one-wave blocks, dealt as lfr_batch_covariance deals its own
+        PackedRanges r;
+        int nb = 0;
+        lfr::packed_ranges(b, 1, &r, &nb);
+        CovMatchArgs a;
+        memset(&a, 0, sizeof(a));
+        a.c.k.descs = b->d_descs; a.c.k.edges = b->d_edges; a.c.k.node_ids = b->d_node_ids; a.c.k.positions = b->d_positions; a.c.k.infos = b->d_infos;
+        a.c.k.tukey_variant = b->tukey_variant; a.c.k.edge_ref = b->d_edge_ref; a.c.k.edge_word = b->d_edge_word;
+        a.c.cov = cov_device; a.c.status = s.d_status; a.c.f64 = f64;
+        a.m = mo;
+        if (nb > 0) {
+            if (b->fused) {                  // the packed records have not been written yet: flows and words from the graph's arrays, as the solve did
+                const lfr::DevGraph &dgr = *b->dev_hold->graph;
+                a.c.k.f_row = dgr.flow_row; a.c.k.f_disp1 = dgr.disp1; a.c.k.f_disp2 = dgr.disp2; a.c.k.f_sim = dgr.sim;
+                hipLaunchKernelGGL(covariance_matches_packed_kernel<true>, dim3(nb), dim3(64), 0, st, a, r);
+            } else {
+                hipLaunchKernelGGL(covariance_matches_packed_kernel<false>, dim3(nb), dim3(64), 0, st, a, r);
+            }
+        }
+    }
+    CovMatchBlockArgs c;
+    memset(&c, 0, sizeof(c));
+    c.c.b.descs = b->d_descs; c.c.b.edges = b->d_edges; c.c.b.node_ids = b->d_node_ids; c.c.b.node_inc = b->d_node_inc; c.c.b.in_idx = b->d_in_idx;
+    c.c.b.positions = b->d_positions; c.c.b.infos = b->d_infos; c.c.b.hws = s.d_hws; c.c.b.hws_off = s.d_hws_off; c.c.b.status = s.d_status;
+    c.c.b.tukey_variant = b->tukey_variant; c.c.b.scan_all = 0; c.c.b.eid = mo.eid; c.c.b.n_matches = (uint32_t)M;
+    c.c.cov = cov_device; c.c.f64 = f64;
+    c.m = mo; c.diag = s.d_diag;
+    for (int cls = lfr::KC_BLOCK; cls < lfr::KC_COUNT; ++cls) {
+        c.c.b.desc_begin = b->class_begin[cls];
+        const int n = b->class_begin[cls + 1] - c.c.b.desc_begin, rows = std::max(s.rows_max[cls], 2);
+        if (n <= 0) continue;
+        if (cls == lfr::KC_GLOBAL) {
+            const size_t lds = cov_lds_bytes(rows, false, c.c.scratch_doubles);
+            hipLaunchKernelGGL((covariance_matches_block_kernel<kCovThreads, false>), dim3(n), dim3(kCovThreads), lds, st, c);
+        } else {
+            const size_t lds = cov_lds_bytes(rows, true, c.c.scratch_doubles);
+            hipLaunchKernelGGL((covariance_matches_block_kernel<kCovThreads, true>), dim3(n), dim3(kCovThreads), lds, st, c);
         }
     }
     HIP_TRY(hipGetLastError());

@@ -176,6 +176,7 @@ class Refiner:
     the origin; reset_start() makes the next forward cold again.  The backward is the same either way: the implicit gradient is taken
     at the solution and does not know where LM started.
     hessian: as for refine().  node_image, node_feature, n_nodes: as refine() returns them.  covariance(f64=True): lfr_batch_covariance of the latest solve.
+    match_covariance(f64=True): lfr_batch_covariance_matches of the latest solve (cross blocks and relative covariance per match).
     evaluate(positions=None, **kw): lfr_batch_evaluate (cost, dF/dx, residuals, loss weights), detached."""
 
     def __init__(self, disp1, disp2, sim, *, image_names, pair_img1, pair_img2, pair_off, feat1, feat2, image_facts=None, banned=(),
@@ -247,6 +248,26 @@ class Refiner:
             raise RuntimeError("Refiner: covariance before the first forward")
         with torch.cuda.device(self.device):
             return self._batch.covariance(f64=f64)
+
+    def match_covariance(self, f64=True):
+        """Covariance between the matched keypoints of the latest forward (Batch.covariance_matches, lfr_batch_covariance_matches):
+        {"cross": [rows, 2, 2] = Cov(x_node1, x_node2), "relative": [rows, 3] = D(di,di), D(di,dj), D(dj,dj) of Cov(x_node2 - x_node1)}
+        in the caller's rows and the solver's unit squared: the rows of banned pairs read cross 0 and relative (-1, 0, -1), "not in the
+        program".  Detached: the covariance is not differentiated."""
+        if self._batch is None:
+            raise RuntimeError("Refiner: match_covariance after close()")
+        if self._epoch == 0:
+            raise RuntimeError("Refiner: match_covariance before the first forward")
+        with torch.cuda.device(self.device):
+            out = self._batch.covariance_matches(f64=f64, want=("cross", "relative"))
+            if self._idx is not None:
+                full = torch.zeros((self.n_rows, 2, 2), dtype=out["cross"].dtype, device=self.device)
+                full[self._idx] = out["cross"]
+                out["cross"] = full
+                full = torch.tensor([-1.0, 0.0, -1.0], dtype=out["relative"].dtype, device=self.device).repeat(self.n_rows, 1)
+                full[self._idx] = out["relative"]
+                out["relative"] = full
+        return {k: v.detach() for k, v in out.items()}
 
     def evaluate(self, positions=None, **kw):
         """Batch.evaluate (lfr_batch_evaluate) on the shared batch: cost, dF/dx, raw residuals and loss weights at `positions`

@@ -142,6 +142,7 @@ def lib():
         "lfr_batch_backward_status": (i64, [vp, vp]),
         "lfr_batch_set_inputs": (C.c_int, [vp, vp, vp, vp, vp]),
         "lfr_batch_covariance": (C.c_int, [vp, vp, C.c_int, vp, C.POINTER(CovarianceStats)]),
+        "lfr_batch_covariance_matches": (C.c_int, [vp, vp, vp, vp, C.c_int, vp, C.POINTER(CovarianceStats)]),
         "lfr_batch_covariance_status": (i64, [vp, vp]),
         "lfr_batch_evaluate": (C.c_int, [vp, vp, vp, vp, vp, vp, C.c_int, vp, C.POINTER(EvaluateStats)]),
         "lfr_keypoint_covariances": (C.c_int, [vp, vp, C.c_char_p, vp, i64]),
@@ -179,7 +180,7 @@ EXPORTS = ["lfr_version", "lfr_last_error", "lfr_graph_from_files", "lfr_graph_f
            "lfr_graph_num_images", "lfr_graph_get_nodes", "lfr_graph_image_name", "lfr_graph_image_fact",
            "lfr_write_matching_file", "lfr_problem_build", "lfr_problem_build_labels", "lfr_problem_build_hip", "lfr_problem_free", "lfr_problem_get_stats",
            "lfr_problem_get_labels", "lfr_problem_shard_components", "lfr_hip_warmup", "lfr_batch_create", "lfr_batch_free", "lfr_batch_solve", "lfr_batch_solve_from",
-           "lfr_batch_download", "lfr_batch_timing", "lfr_batch_spin_timeouts", "lfr_batch_team_runs", "lfr_batch_team_fallbacks", "lfr_debug_occupy", "lfr_batch_tree_stats", "lfr_batch_component_info", "lfr_batch_positions_to_device", "lfr_batch_backward", "lfr_batch_backward_status", "lfr_batch_set_inputs", "lfr_batch_covariance", "lfr_batch_covariance_status", "lfr_batch_evaluate", "lfr_keypoint_covariances", "lfr_debug_invert_spd", "lfr_solve_hip", "lfr_solve_hip_multi", "lfr_solve_graph_hip_multi", "lfr_write_solution", "lfr_apply_displacements"]
+           "lfr_batch_download", "lfr_batch_timing", "lfr_batch_spin_timeouts", "lfr_batch_team_runs", "lfr_batch_team_fallbacks", "lfr_debug_occupy", "lfr_batch_tree_stats", "lfr_batch_component_info", "lfr_batch_positions_to_device", "lfr_batch_backward", "lfr_batch_backward_status", "lfr_batch_set_inputs", "lfr_batch_covariance", "lfr_batch_covariance_matches", "lfr_batch_covariance_status", "lfr_batch_evaluate", "lfr_keypoint_covariances", "lfr_debug_invert_spd", "lfr_solve_hip", "lfr_solve_hip_multi", "lfr_solve_graph_hip_multi", "lfr_write_solution", "lfr_apply_displacements"]
 
 
 def _check(rc):
@@ -757,6 +758,37 @@ class Batch:
         if want_stats:
             return cov, st.as_dict()
         return cov
+
+    def covariance_matches(self, f64=True, want=("cov", "cross", "relative"), stream=None, want_stats=False):
+        """Covariance between matched keypoints of the latest solve (lfr_batch_covariance_matches, include/lfr.h), from one assembly
+        and one inversion per component.  Returns a dict of device tensors, one per name in `want`: "cov" [n_nodes, 3] exactly as
+        covariance() gives it; "cross" [n_matches, 2, 2] = Cov(x_node1, x_node2) in the graph's match layout (0 for a constant end, a
+        dropped edge, a match outside the batch, a component without covariance); "relative" [n_matches, 3] = D(di,di), D(di,dj),
+        D(dj,dj) of D = Cov(x_node2 - x_node1), formed in fp64 ((-1, 0, -1): the match is no residual block of this batch; zeros: its
+        component has no covariance).  float64, or float32 with f64=False; the solver's unit squared.  With want_stats also "stats"
+        (that waits)."""
+        import torch
+        want = tuple(want)
+        if not want or any(w not in ("cov", "cross", "relative") for w in want):
+            raise ValueError("covariance_matches: want takes \"cov\", \"cross\", \"relative\" (at least one), got %r" % (want,))
+        n = self.problem.graph.n_nodes
+        m = self.problem.graph.n_edges // 2
+        dev = torch.device("cuda", self.device)
+        dt = torch.float64 if f64 else torch.float32
+        shapes = {"cov": (n, 3), "cross": (m, 2, 2), "relative": (m, 3)}
+        out = {k: torch.empty(shapes[k], dtype=dt, device=dev) for k in ("cov", "cross", "relative") if k in want}
+        if stream is None:
+            stream = torch.cuda.current_stream(dev).cuda_stream
+
+        def ptr(name):
+            return C.c_void_p(out[name].data_ptr() or 1) if name in out else None
+
+        st = CovarianceStats()
+        _check(lib().lfr_batch_covariance_matches(self._h, ptr("cov"), ptr("cross"), ptr("relative"), COVARIANCE_F64 if f64 else 0,
+                                                  C.c_void_p(stream) if stream else None, C.byref(st) if want_stats else None))
+        if want_stats:
+            out["stats"] = st.as_dict()
+        return out
 
     def covariance_status(self):
         """Per component (order of component_info) of the latest covariance: COVARIANCE_OK / _NOT_USABLE / _SINGULAR."""
