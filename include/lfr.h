@@ -408,6 +408,55 @@ int lfr_batch_backward(lfr_batch *b, const double *grad_positions_device, void *
 int64_t lfr_batch_backward_status(lfr_batch *b, int32_t *status);
 
 /* ---------------------------------------------------------------------------------------------
+ * Forward-mode sensitivity of the refined positions: xdot = J thetadot, J = dx^/dtheta - the other half of lfr_batch_backward's
+ * J^T ubar (input noise pushed to the positions, torch.autograd.forward_ad / torch.func.jvp, the first-order prediction
+ * x^(theta + dtheta) ~ x^ + J dtheta).
+ *
+ * Contract.  lfr_batch_backward's, read the other way.  Take the batch after its latest solve; per usable component at x^, with the
+ * structure held fixed (tracks, roots, components, edge kinds, the active set of the box):
+ *   - free coordinates: those of the variable nodes with |x^| < 1;
+ *   - H = exactly the matrix of lfr_batch_backward in the same mode: the exact Hessian of F over the free coordinates, or J^T J with
+ *     LFR_JVP_GAUSS_NEWTON (as LFR_BACKWARD_GAUSS_NEWTON), bound coordinates as identity rows and columns;
+ *   - b = -sum_e d/d eps [grad_x F_e(x^; theta_e + eps thetadot_e)] on the free coordinates, 0 on bound ones.  Per edge, with
+ *     rdot_k = -sum_ij Lr_i Lc_j phidot_ijk, sdot = 2 r . rdot and Pdot = d/d eps P (the sums with dLr_i Lc_j and Lr_i dLc_j): the
+ *     destination's rows take -[wdot rho' r + w (rho'' sdot r + rho' rdot)], the source's
+ *     +[wdot rho' P^T r + w (rho'' sdot P^T r + rho' (Pdot^T r + P^T rdot))];
+ *   - xdot = H^-1 b.
+ * Its defining property is the adjoint identity with lfr_batch_backward in the same mode on the same solve:
+ * ubar . (J thetadot) = (J^T ubar) . thetadot for every ubar and thetadot.
+ * Inputs: the tangents in the MATCH layout of lfr_batch_backward / lfr_batch_set_inputs / lfr_batch_evaluate - tan_disp1 / tan_disp2:
+ * n_matches x 18, tan_sim: n_matches, float32 (double with LFR_JVP_F64), DEVICE pointers; edge node1->node2 of match m reads
+ * tan_disp2[m], node2->node1 reads tan_disp1[m], both read tan_sim[m].  tan_disp1 and tan_disp2: both given or both NULL (= a zero flow
+ * tangent); tan_sim NULL = zero; all three NULL: LFR_ERR_ARG.  Only the rows of this shard's records are read, and only by work
+ * enqueued in this call.  A tangent that is not finite makes only its own component's output not finite: the status stays 0 and no
+ * other component - one in the same wavefront included - changes by a bit.
+ * Output: tan_positions_device, 2 * n_nodes doubles, the whole array is overwritten: xdot for the free coordinates of usable
+ * components; 0 for bound coordinates, roots and constant nodes, for nodes outside solved components or outside the shard, for
+ * FAILURE components (status 1) and for components whose factorization meets a pivot that is not positive (status 2).
+ * Errors and state: LFR_ERR_ARG before the first solve, between an lfr_batch_set_inputs and the next solve, and for an unknown flag
+ * bit; LFR_ERR_UNSUPPORTED for a batch over one rank's connected components (lfr_problem_cc_sharded = 1) and for components above
+ * 6144 rows.  Runs on `hip_stream` after the latest solve; asynchronous unless stats != NULL.  Changes nothing the solve, the backward
+ * or the covariance read; lfr_batch_set_inputs waits by event for the latest jvp.  Results are bitwise repeatable from call to call
+ * and identical for host- and device-assembled batches; no fp64 value goes through a global-memory atomic.
+ * Kernels: lfr_batch_backward's launch plan - one workgroup per component (one wave for the classes of up to 32 rows in the exact
+ * mode), the right-hand side summed owner-computes in record order, H in LDS up to 192 rows and in an HBM workspace above; in
+ * Gauss-Newton mode the classes of up to 32 rows run ONE launch in the covariance's packed layout (xdot_row = C_row . b). */
+typedef struct lfr_jvp_stats {
+    int64_t n_differentiated;      /* components whose tangent was computed */
+    int64_t n_not_usable;          /* FAILURE components (zero tangent) */
+    int64_t n_indefinite;          /* components whose H met a pivot that is not positive (zero tangent) */
+    int64_t n_bound_coordinates;   /* coordinates of usable components held at the +-1 bound */
+    double kernel_ms;              /* HIP-event time of the jvp's kernels (and its clearing of the output) */
+} lfr_jvp_stats;
+#define LFR_JVP_F64 1              /* the three tangent INPUTS are double instead of float32 */
+#define LFR_JVP_GAUSS_NEWTON 2     /* H = J^T J over the free coordinates, as LFR_BACKWARD_GAUSS_NEWTON */
+int lfr_batch_jvp(lfr_batch *b, const void *tan_disp1_device, const void *tan_disp2_device, const void *tan_sim_device,
+                  double *tan_positions_device, int flags, void *hip_stream, lfr_jvp_stats *stats);
+/* Per component (order of lfr_batch_component_info) of the latest jvp: 0 differentiated, 1 not usable, 2 indefinite.
+ * Waits for that jvp.  Returns the count (< 0: error, LFR_ERR_ARG before the first jvp). */
+int64_t lfr_batch_jvp_status(lfr_batch *b, int32_t *status);
+
+/* ---------------------------------------------------------------------------------------------
  * New flows and similarities into a live batch: the forward-side counterpart of the backward's contract (a training loop solves the
  * same scenes thousands of times and only the network's outputs change; the reference re-reads its MatchingFile for every run).
  *

@@ -8,6 +8,7 @@
 //   lfr_covariance.hip   per-keypoint covariance (lfr_batch_covariance): kernels, the launches
 //   lfr_inputs.hip       new flows / similarities into a live batch (lfr_batch_set_inputs) and the record -> directed-edge map
 //   lfr_evaluate.hip     cost, gradient, residuals and loss weights at given positions (lfr_batch_evaluate): kernels, the launches
+//   lfr_jvp.hip          forward-mode sensitivity of the positions (lfr_batch_jvp): kernels, the launches
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -255,12 +256,14 @@ struct lfr_batch {
     bool inputs_pending = false;         // no solve has been issued since: the next one waits for ev_inputs
     lfr::PassState *bwd = nullptr, *cov = nullptr;       // lfr_backward.hip / lfr_covariance.hip: set up on the first call
     lfr::PassState *eval = nullptr;                      // lfr_evaluate.hip: set up on the first lfr_batch_evaluate (its own entry: needs no solve)
+    lfr::PassState *jvp = nullptr;                       // lfr_jvp.hip: set up on the first lfr_batch_jvp
 
     lfr_batch() { for (auto &e : ev_ring) e = nullptr; }
     ~lfr_batch() {
         lfr::pass_free(bwd);
         lfr::pass_free(cov);
         lfr::pass_free(eval);
+        lfr::pass_free(jvp);
         if (ctx) {
             (void)hipSetDevice(device);
             if (n_solves > 0) (void)hipStreamSynchronize(last_stream);      // nothing may still use the slab

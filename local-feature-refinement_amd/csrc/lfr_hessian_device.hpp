@@ -213,4 +213,55 @@ __device__ __forceinline__ bool bwd_ldlt(double *H, const int n, double *lval, i
     }
     return indefinite;
 }
+
+// ---- forward-mode sensitivity (lfr_jvp.hip): the transpose of the backward's vector-Jacobian sweep ----
+// The tangent of one record's inputs: the 18 flow values and the similarity of directed edge `id` in the match layout (even ids read
+// tan_disp2, odd ids tan_disp1, both tan_sim); a NULL array is a zero tangent.  f64: the arrays hold doubles instead of floats.
+struct JvpTangent {
+    const void *disp1, *disp2, *sim;
+    uint32_t n_matches;
+    int f64;
+};
+
+__device__ __forceinline__ void jvp_load_tangent(const JvpTangent &t, const uint32_t id, double (&phidot)[18], double &wdot) {
+    const uint32_t m = id >> 1;
+    const bool in = m < t.n_matches;                          // (always: every record maps to an edge of the graph)
+    const void *fl = (id & 1u) ? t.disp1 : t.disp2;
+#pragma unroll
+    for (int i = 0; i < 18; ++i) {
+        double v = 0.0;
+        if (in && fl) v = t.f64 ? static_cast<const double *>(fl)[18 * (size_t)m + i] : (double)static_cast<const float *>(fl)[18 * (size_t)m + i];
+        phidot[i] = v;
+    }
+    wdot = 0.0;
+    if (in && t.sim) wdot = t.f64 ? static_cast<const double *>(t.sim)[m] : (double)static_cast<const float *>(t.sim)[m];
+}
+
+// -d/d eps [grad_x F_e(x^; theta_e + eps thetadot_e)] of one record evaluated as `o` (bwd_eval): its two rows at the source (bs) and at
+// the destination (bd).  With rdot = -sum_ij lr_i lc_j phidot_ij, sdot = 2 r . rdot and Pdot = d/d eps (I + df/dx_src):
+//   d grad_dst =   wdot rho' r     + w (rho'' sdot r     + rho' rdot)
+//   d grad_src = -[wdot rho' P^T r + w (rho'' sdot P^T r + rho' (Pdot^T r + P^T rdot))]
+__device__ __forceinline__ void jvp_rhs_edge(const BwdEdge &o, const double (&phidot)[18], const double wdot, double (&bs)[2], double (&bd)[2]) {
+    double rd[2] = {0., 0.}, pr[2] = {0., 0.}, pc[2] = {0., 0.};      // rdot, Pdot's columns
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int j = 0; j < 3; ++j)
+#pragma unroll
+            for (int k = 0; k < 2; ++k) {
+                const double d = phidot[2 * (3 * i + j) + k];
+                rd[k] -= o.lr[i] * o.lc[j] * d;
+                pr[k] += o.dlr[i] * o.lc[j] * d;
+                pc[k] += o.lr[i] * o.dlc[j] * d;
+            }
+    const double sdot = 2.0 * (o.r[0] * rd[0] + o.r[1] * rd[1]);
+    const double c0 = wdot * o.rho1 + o.w * o.rho2 * sdot, c1 = o.w * o.rho1;      // d grad_dst = c0 r + c1 rdot
+    bd[0] = -(c0 * o.r[0] + c1 * rd[0]);
+    bd[1] = -(c0 * o.r[1] + c1 * rd[1]);
+    const double ptr0 = (1.0 + o.fr[0]) * o.r[0] + o.fr[1] * o.r[1], ptr1 = o.fc[0] * o.r[0] + (1.0 + o.fc[1]) * o.r[1];      // P^T r
+    const double q0 = pr[0] * o.r[0] + pr[1] * o.r[1] + (1.0 + o.fr[0]) * rd[0] + o.fr[1] * rd[1];      // Pdot^T r + P^T rdot
+    const double q1 = pc[0] * o.r[0] + pc[1] * o.r[1] + o.fc[0] * rd[0] + (1.0 + o.fc[1]) * rd[1];
+    bs[0] = c0 * ptr0 + c1 * q0;
+    bs[1] = c0 * ptr1 + c1 * q1;
+}
 }  // namespace lfrdev

@@ -1,5 +1,6 @@
 """PyTorch autograd through the batched LM solve: the two-view network's flows (and the similarities) in, refined positions out, and
-the implicit-function-theorem gradient back (lfr_batch_backward, include/lfr.h).
+the implicit-function-theorem gradient back (lfr_batch_backward, include/lfr.h) - or, in forward mode, the tangent
+of the positions for tangents of the flows and similarities (lfr_batch_jvp).
 
     pos, node_image, node_feature = refine(disp1, disp2, sim, image_names=..., pair_img1=..., pair_img2=..., pair_off=...,
                                            feat1=..., feat2=...)
@@ -19,7 +20,9 @@ of the origin: flows that moved a little need fewer LM iterations.  reset_start(
 hessian="gauss_newton" (refine and Refiner) takes the implicit gradient with H = J^T J instead of the exact Hessian
 (LFR_BACKWARD_GAUSS_NEWTON): components whose exact Hessian is indefinite - zero gradient in the default mode - get one too.
 
-One device, first-order only (the backward is not itself differentiable).  The graph stage (tracks, roots, components, the cut) is
+One device.  First order in both modes: reverse (backward()) and forward (torch.autograd.forward_ad, Refiner.jvp) - the tangent J
+thetadot comes from lfr_batch_jvp with the H of `hessian`, so ubar . (J thetadot) = (J^T ubar) . thetadot holds between the two.  Neither
+pass is itself differentiable: no double backward, no forward-over-reverse through the solve.  The graph stage (tracks, roots, components, the cut) is
 discrete and the box's active set piecewise constant: the gradient holds them fixed.
 """
 import numpy as np
@@ -47,6 +50,28 @@ def _kept_rows(pair_img1, pair_img2, pair_off, image_names, banned):
     keep = ~(bad[pair_img1] | bad[pair_img2])
     rows = [np.arange(pair_off[p], pair_off[p + 1], dtype=np.int64) for p in np.nonzero(keep)[0]]
     return np.concatenate(rows) if rows else np.zeros(0, np.int64)
+
+
+def _tangent_rows(who, tangents, n_rows, idx, device):
+    """The tangents of (disp1, disp2, sim) in the caller's rows -> what Batch.jvp takes: the graph's rows (banned pairs dropped
+    through idx), contiguous on `device`, float32 or - when one of them is float64 - float64; None stays None (= zero)."""
+    t1, t2, ts = tangents
+    if t1 is None and t2 is None and ts is None:
+        raise ValueError("%s: no tangent (all three are None)" % who)
+    f64 = any(t is not None and t.dtype == torch.float64 for t in tangents)
+    dt = torch.float64 if f64 else torch.float32
+
+    def rows(t, shape):
+        t = t.detach().to(device=device, dtype=dt).reshape(shape)
+        if t.shape[0] != n_rows:
+            raise ValueError("%s: %d rows, the forward saw %d" % (who, t.shape[0], n_rows))
+        return (t if idx is None else t.index_select(0, idx)).contiguous()
+
+    if (t1 is None) != (t2 is None):         # one flow tangent alone: the other is zero
+        t1 = torch.zeros_like(t2) if t1 is None else t1
+        t2 = torch.zeros_like(t1) if t2 is None else t2
+    return (None if t1 is None else rows(t1, (-1, 18)), None if t2 is None else rows(t2, (-1, 18)),
+            None if ts is None else rows(ts, (-1,)), f64)
 
 
 class _Refine(torch.autograd.Function):
@@ -96,6 +121,19 @@ class _Refine(torch.autograd.Function):
         return (g1.reshape(s1).to(t1) if ctx.needs_input_grad[0] else None,
                 g2.reshape(s2).to(t2) if ctx.needs_input_grad[1] else None,
                 gs.reshape(ss).to(device=gs.device, dtype=ts) if ctx.needs_input_grad[2] else None, None)
+
+    @staticmethod
+    def jvp(ctx, tan_disp1, tan_disp2, tan_sim, *_):
+        """forward mode (torch.autograd.forward_ad): the tangent of the positions; the node maps have none"""
+        b, meta = ctx.batch, ctx.meta
+        pos_dev = torch.device("cuda", b.device)
+        if tan_disp1 is None and tan_disp2 is None and tan_sim is None:
+            return torch.zeros((b.problem.graph.n_nodes, 2), dtype=torch.float64, device=pos_dev), None, None
+        rows = meta["kept_rows"]
+        idx = None if rows is None else torch.as_tensor(rows, device=pos_dev)
+        with torch.cuda.device(pos_dev):
+            t1, t2, ts, f64 = _tangent_rows("refine", (tan_disp1, tan_disp2, tan_sim), int(np.prod(ctx.n_in[2])), idx, pos_dev)
+            return b.jvp(t1, t2, ts, f64=f64, gauss_newton=meta["gauss_newton"]), None, None
 
 
 def refine(disp1, disp2, sim, *, image_names, pair_img1, pair_img2, pair_off, feat1, feat2, image_facts=None, banned=(),
@@ -161,6 +199,19 @@ class _RefinerStep(torch.autograd.Function):
                 g2.reshape(s2).to(t2) if ctx.needs_input_grad[1] else None,
                 gs.reshape(ss).to(device=ts[1], dtype=ts[0]) if ss is not None and ctx.needs_input_grad[2] else None, None)
 
+    @staticmethod
+    def jvp(ctx, tan_disp1, tan_disp2, tan_sim, *_):
+        """forward mode (torch.autograd.forward_ad): the tangent of the positions of THIS forward"""
+        r = ctx.refiner
+        if r._batch is None:
+            raise RuntimeError("Refiner: jvp after close()")
+        if ctx.epoch != r._epoch:
+            raise RuntimeError("Refiner: this forward (step %d) is stale - the shared batch holds only its latest solve (step %d)"
+                               % (ctx.epoch, r._epoch))
+        if tan_disp1 is None and tan_disp2 is None and tan_sim is None:
+            return torch.zeros((r.n_nodes, 2), dtype=torch.float64, device=r.device)
+        return r.jvp(tan_disp1, tan_disp2, tan_sim)
+
 
 class Refiner:
     """refine() for a loop over the same scenes: the graph stage (tracks, roots, components) and the batch assembly run once, in the
@@ -177,7 +228,9 @@ class Refiner:
     at the solution and does not know where LM started.
     hessian: as for refine().  node_image, node_feature, n_nodes: as refine() returns them.  covariance(f64=True): lfr_batch_covariance of the latest solve.
     match_covariance(f64=True): lfr_batch_covariance_matches of the latest solve (cross blocks and relative covariance per match).
-    evaluate(positions=None, **kw): lfr_batch_evaluate (cost, dF/dx, residuals, loss weights), detached."""
+    evaluate(positions=None, **kw): lfr_batch_evaluate (cost, dF/dx, residuals, loss weights), detached.
+    jvp(tan_disp1, tan_disp2, tan_sim=None): lfr_batch_jvp of the latest forward (the tangent of the positions), detached;
+    torch.autograd.forward_ad through r(...) calls it."""
 
     def __init__(self, disp1, disp2, sim, *, image_names, pair_img1, pair_img2, pair_off, feat1, feat2, image_facts=None, banned=(),
                  tukey_variant="ceres1", hessian="exact", warm_start=False):
@@ -268,6 +321,20 @@ class Refiner:
                 full[self._idx] = out["relative"]
                 out["relative"] = full
         return {k: v.detach() for k, v in out.items()}
+
+    def jvp(self, tan_disp1, tan_disp2, tan_sim=None):
+        """Forward-mode sensitivity of the latest forward (Batch.jvp, lfr_batch_jvp): the [n_nodes, 2] float64 tangent of the positions
+        for tangents of the flows and / or the similarities in the caller's rows (banned pairs included: their rows are not read; a
+        None is a zero tangent, all three None: ValueError).  float32 tangents, or float64 when one of them is.  The H is the
+        Refiner's `hessian`, so ubar . r.jvp(t) equals the sum of backward()'s gradients times t.  Detached."""
+        if self._batch is None:
+            raise RuntimeError("Refiner: jvp after close()")
+        if self._epoch == 0:
+            raise RuntimeError("Refiner: jvp before the first forward")
+        with torch.cuda.device(self.device):
+            t1, t2, ts, f64 = _tangent_rows("Refiner.jvp", (tan_disp1, tan_disp2, tan_sim), self.n_rows, self._idx, self.device)
+            # (t1, t2, ts may be temporaries: they are read by work enqueued here, and torch reuses their memory in stream order)
+            return self._batch.jvp(t1, t2, ts, f64=f64, gauss_newton=self._gauss_newton).detach()
 
     def evaluate(self, positions=None, **kw):
         """Batch.evaluate (lfr_batch_evaluate) on the shared batch: cost, dF/dx, raw residuals and loss weights at `positions`

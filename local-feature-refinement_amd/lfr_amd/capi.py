@@ -71,9 +71,19 @@ class EvaluateStats(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+class JvpStats(C.Structure):
+    _fields_ = [(n, C.c_int64) for n in ("n_differentiated", "n_not_usable", "n_indefinite", "n_bound_coordinates")] + [("kernel_ms", C.c_double)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
 BACKWARD_F64 = 1                # LFR_BACKWARD_F64
 BACKWARD_GAUSS_NEWTON = 2       # LFR_BACKWARD_GAUSS_NEWTON
 BACKWARD_OK, BACKWARD_NOT_USABLE, BACKWARD_INDEFINITE = 0, 1, 2      # lfr_batch_backward_status
+JVP_F64 = 1                     # LFR_JVP_F64
+JVP_GAUSS_NEWTON = 2            # LFR_JVP_GAUSS_NEWTON
+JVP_OK, JVP_NOT_USABLE, JVP_INDEFINITE = 0, 1, 2      # lfr_batch_jvp_status
 COVARIANCE_F64 = 1              # LFR_COVARIANCE_F64
 COVARIANCE_OK, COVARIANCE_NOT_USABLE, COVARIANCE_SINGULAR = 0, 1, 2     # lfr_batch_covariance_status
 EVALUATE_F64 = 1                # LFR_EVALUATE_F64
@@ -140,6 +150,8 @@ def lib():
         "lfr_batch_positions_to_device": (C.c_int, [vp, vp, vp]),
         "lfr_batch_backward": (C.c_int, [vp, vp, vp, vp, vp, C.c_int, vp, C.POINTER(BackwardStats)]),
         "lfr_batch_backward_status": (i64, [vp, vp]),
+        "lfr_batch_jvp": (C.c_int, [vp, vp, vp, vp, vp, C.c_int, vp, C.POINTER(JvpStats)]),
+        "lfr_batch_jvp_status": (i64, [vp, vp]),
         "lfr_batch_set_inputs": (C.c_int, [vp, vp, vp, vp, vp]),
         "lfr_batch_covariance": (C.c_int, [vp, vp, C.c_int, vp, C.POINTER(CovarianceStats)]),
         "lfr_batch_covariance_matches": (C.c_int, [vp, vp, vp, vp, C.c_int, vp, C.POINTER(CovarianceStats)]),
@@ -180,7 +192,7 @@ EXPORTS = ["lfr_version", "lfr_last_error", "lfr_graph_from_files", "lfr_graph_f
            "lfr_graph_num_images", "lfr_graph_get_nodes", "lfr_graph_image_name", "lfr_graph_image_fact",
            "lfr_write_matching_file", "lfr_problem_build", "lfr_problem_build_labels", "lfr_problem_build_hip", "lfr_problem_free", "lfr_problem_get_stats",
            "lfr_problem_get_labels", "lfr_problem_shard_components", "lfr_hip_warmup", "lfr_batch_create", "lfr_batch_free", "lfr_batch_solve", "lfr_batch_solve_from",
-           "lfr_batch_download", "lfr_batch_timing", "lfr_batch_spin_timeouts", "lfr_batch_team_runs", "lfr_batch_team_fallbacks", "lfr_debug_occupy", "lfr_batch_tree_stats", "lfr_batch_component_info", "lfr_batch_positions_to_device", "lfr_batch_backward", "lfr_batch_backward_status", "lfr_batch_set_inputs", "lfr_batch_covariance", "lfr_batch_covariance_matches", "lfr_batch_covariance_status", "lfr_batch_evaluate", "lfr_keypoint_covariances", "lfr_debug_invert_spd", "lfr_solve_hip", "lfr_solve_hip_multi", "lfr_solve_graph_hip_multi", "lfr_write_solution", "lfr_apply_displacements"]
+           "lfr_batch_download", "lfr_batch_timing", "lfr_batch_spin_timeouts", "lfr_batch_team_runs", "lfr_batch_team_fallbacks", "lfr_debug_occupy", "lfr_batch_tree_stats", "lfr_batch_component_info", "lfr_batch_positions_to_device", "lfr_batch_backward", "lfr_batch_backward_status", "lfr_batch_jvp", "lfr_batch_jvp_status", "lfr_batch_set_inputs", "lfr_batch_covariance", "lfr_batch_covariance_matches", "lfr_batch_covariance_status", "lfr_batch_evaluate", "lfr_keypoint_covariances", "lfr_debug_invert_spd", "lfr_solve_hip", "lfr_solve_hip_multi", "lfr_solve_graph_hip_multi", "lfr_write_solution", "lfr_apply_displacements"]
 
 
 def _check(rc):
@@ -738,6 +750,54 @@ class Batch:
         n = lib().lfr_batch_component_info(self._h, None, None, None, None, None, None)
         out = np.zeros(max(n, 0), np.int32)
         rc = lib().lfr_batch_backward_status(self._h, _ptr(out))
+        if rc < 0:
+            _check(rc)
+        return out
+
+    def jvp(self, tan_disp1=None, tan_disp2=None, tan_sim=None, f64=False, gauss_newton=False, stream=None, want_stats=False):
+        """Forward-mode sensitivity of the latest solve (lfr_batch_jvp, include/lfr.h): the tangent of the positions for the tangents
+        of the flows and similarities - contiguous tensors on the batch's device in the graph's match layout, tan_disp1 / tan_disp2:
+        [n_matches, 18] or [n_matches, 9, 2], given together or not at all (None = zero); tan_sim: [n_matches] (None = zero); float32,
+        or float64 with f64=True.  Returns the [n_nodes, 2] float64 device tensor J thetadot (0 for roots, bound coordinates, unsolved
+        nodes and the nodes of components that are not usable or indefinite), and the stats dict when want_stats (that waits).
+        gauss_newton=True: H = J^T J instead of the exact Hessian (LFR_JVP_GAUSS_NEWTON), the mode of backward(gauss_newton=True)."""
+        import torch
+        n = self.problem.graph.n_nodes
+        m = self.problem.graph.n_edges // 2
+        dev = torch.device("cuda", self.device)
+        dt = torch.float64 if f64 else torch.float32
+
+        def ptr(t, name, shapes):
+            if t is None:
+                return None
+            if not isinstance(t, torch.Tensor):
+                raise ValueError("jvp: %s must be a torch tensor" % name)
+            if not t.is_cuda or t.device != dev:
+                raise ValueError("jvp: %s is on %s, the batch on %s" % (name, t.device, dev))
+            if t.dtype != dt:
+                raise ValueError("jvp: %s is %s, need %s" % (name, t.dtype, dt))
+            if tuple(t.shape) not in shapes or not t.is_contiguous():
+                raise ValueError("jvp: %s has shape %s, need a contiguous %s" % (name, tuple(t.shape), " or ".join(map(str, shapes))))
+            return C.c_void_p(t.data_ptr() or 1)          # (no matches: an empty tensor has no address, and nothing is read)
+
+        flow_shapes = ((m, 18), (m, 9, 2))
+        p1, p2, ps = ptr(tan_disp1, "tan_disp1", flow_shapes), ptr(tan_disp2, "tan_disp2", flow_shapes), ptr(tan_sim, "tan_sim", ((m,),))
+        out = torch.empty((n, 2), dtype=torch.float64, device=dev)
+        if stream is None:
+            stream = torch.cuda.current_stream(dev).cuda_stream
+        st = JvpStats()
+        _check(lib().lfr_batch_jvp(self._h, p1, p2, ps, C.c_void_p(out.data_ptr() or 1),
+                                   (JVP_F64 if f64 else 0) | (JVP_GAUSS_NEWTON if gauss_newton else 0),
+                                   C.c_void_p(stream) if stream else None, C.byref(st) if want_stats else None))
+        if want_stats:
+            return out, st.as_dict()
+        return out
+
+    def jvp_status(self):
+        """Per component (order of component_info) of the latest jvp: JVP_OK / _NOT_USABLE / _INDEFINITE."""
+        n = lib().lfr_batch_component_info(self._h, None, None, None, None, None, None)
+        out = np.zeros(max(n, 0), np.int32)
+        rc = lib().lfr_batch_jvp_status(self._h, _ptr(out))
         if rc < 0:
             _check(rc)
         return out
