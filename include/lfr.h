@@ -107,6 +107,31 @@ int lfr_graph_from_arrays_device_flows(int32_t n_images, const char *const *imag
                                        const float *sim, const void *disp1_device, const void *disp2_device, int device,
                                        const char *const *banned, int n_banned, lfr_graph **out);
 
+/* Producer contract without any host hop for the per-match arrays (compute_match_graph.py:134-159 runs the matchers and the
+ * two-view network on the device): as lfr_graph_from_arrays_device_flows, but feat1 / feat2 / sim are DEVICE pointers too
+ * (n_matches = pair_off[n_pairs] elements each on HIP device `device`, laid out as in lfr_graph_from_arrays; feature indices use the
+ * full uint32 range).  Names, facts, pair_img1/2, pair_off and banned stay on the host.  The nodes are numbered on the GPU
+ *  and the graph is the one lfr_graph_from_arrays_device_flows builds from the same values, bit for bit: images in
+ * order of first appearance over the kept pairs (first fact wins), pairs that touch a banned image skipped, nodes in order of first
+ * appearance, match by match, node1 before node2 (solve.cc:474-475) - and so is every label, batch and result downstream.
+ *   lifetime   disp1 / disp2: owned by the caller, alive until the batch has been created.  feat1 / feat2 / sim are read inside this
+ *              call only; the graph keeps its own copies.
+ *   order      the five arrays must be complete when the call is made (the caller synchronises); the call is synchronous and returns
+ *              with the graph usable by every entry point.
+ *   residency  the graph is left resident on `device`, as if lfr_graph_to_device had run: lfr_problem_build_hip and
+ *              lfr_batch_create there continue from that copy and upload nothing; lfr_graph_evict_device drops it and the next use
+ *              rebuilds it from the host arrays, which the call has filled from the device (16 bytes per match, 8 per node).
+ *              lfr_problem_build (host assembly) rejects the graph like every graph with device flows.
+ *   errors     LFR_ERR_ARG, checked on the host before any GPU work: a NULL among the five device pointers while n_matches > 0,
+ *              device < 0, an image index out of range, a pair_off that starts below 0 or decreases; LFR_ERR_UNSUPPORTED:
+ *              n_matches >= 2^30; LFR_ERR_HIP / LFR_ERR_NOMEM as elsewhere.  n_matches == 0, or every pair banned: an empty graph
+ *              (not resident), LFR_OK. */
+int lfr_graph_from_device_arrays(int32_t n_images, const char *const *image_names, const float *image_facts,
+                                 int64_t n_pairs, const int32_t *pair_img1, const int32_t *pair_img2, const int64_t *pair_off,
+                                 const uint32_t *feat1_device, const uint32_t *feat2_device, const float *sim_device,
+                                 const void *disp1_device, const void *disp2_device, int device,
+                                 const char *const *banned, int n_banned, lfr_graph **out);
+
 /* Device residency of the graph (the GPU-side counterpart of the Graph object solve.cc:405-481 builds while it
  * parses).  lfr_graph_to_device starts copying endpoints, similarities and flows to HBM
  * asynchronously and returns; the device pipeline (lfr_problem_build_hip, lfr_batch_create) continues from that
@@ -683,6 +708,13 @@ int lfr_debug_exclusive_sum(int device, int64_t n, int item_bytes, const void *i
  * a stream of their own; returns when they have started): the tests take CUs away from a solve with it (lfr_batch_team_fallbacks).
  * Test infrastructure, not part of the solve path. */
 int lfr_debug_occupy(int device, int workgroups, double milliseconds);
+
+/* Where the time of this thread's latest lfr_graph_from_device_arrays went, in ms, into ms[0..n): expand, sort, head flags + prefix
+ * sums, heads + scatter (device time between events; 0 unless the environment held LFR_GRAPHBUILD_SPANS=1 at the process's first such
+ * call - the switch puts one more stream wait into the call, in front of the host mirror, and changes no result), then host mirror,
+ * finish() and the host's pair table (host clock, always).  Diagnostic only (scripts/bench_graph_from_device.py): neither the
+ * function nor the switch is part of the producer contract. */
+int lfr_debug_graph_build_spans(double *ms, int n);
 
 /* One-call convenience used by the `solve` launcher: upload, solve, download on one device. */
 int lfr_solve_hip(const lfr_problem *p, int device, int tukey_variant, double *positions,

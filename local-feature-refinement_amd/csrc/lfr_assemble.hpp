@@ -39,6 +39,7 @@ struct DevGraph {
     DevCtx *ctx = nullptr;
     int64_t N = 0, M = 0;
     DevArena slab;                       // endpoints, similarities, node images [, flow rows] [, staged flows]
+    DevArena node_slab;                  // a graph numbered on the device (lfr_graphbuild.hip): the node images, sized once N is known
     uint32_t *n1 = nullptr, *n2 = nullptr;
     float *sim = nullptr;
     int32_t *node_image = nullptr;

@@ -52,6 +52,42 @@ def _kept_rows(pair_img1, pair_img2, pair_off, image_names, banned):
     return np.concatenate(rows) if rows else np.zeros(0, np.int64)
 
 
+def _all_on(device, *tensors):
+    return all(isinstance(t, torch.Tensor) and t.is_cuda and t.device == device for t in tensors)
+
+
+def _device_indices(t):
+    """Feature indices as a contiguous int32 tensor on their device holding the uint32 bit patterns (a wider integer type wraps)."""
+    t = t.detach().reshape(-1)
+    t = t.view(torch.int32) if t.dtype in (torch.int32, torch.uint32) else t.to(torch.int64).to(torch.int32)
+    return t.contiguous()
+
+
+def _build_graph(who, d1, d2, sim, dev, *, image_names, facts, pair_img1, pair_img2, pair_off, feat1, feat2, banned):
+    """The match graph of refine() / Refiner from the flows d1, d2 ([n, 18] float32, contiguous, on HIP device `dev`).  feat1, feat2
+    and sim all torch tensors on that device: the nodes are numbered there (lfr_graph_from_device_arrays) and nothing comes to the
+    host; anything else: the host numbering over host copies (lfr_graph_from_arrays_device_flows).  Call inside
+    torch.cuda.device(dev)."""
+    ma = MatchArrays(image_names=list(image_names), facts=facts, pair_img1=pair_img1, pair_img2=pair_img2, pair_off=pair_off,
+                     feat1=None, feat2=None, sim=None, disp1=None, disp2=None)
+    if _all_on(d1.device, feat1, feat2, sim):
+        f1, f2 = _device_indices(feat1), _device_indices(feat2)
+        s = sim.detach().to(torch.float32).reshape(-1).contiguous()
+        n = int(pair_off[-1]) if len(pair_off) else 0
+        if not (f1.numel() == f2.numel() == s.numel() == d1.shape[0] == d2.shape[0] == n):
+            raise ValueError("%s: pair_off ends at %d, feat1 / feat2 / sim / disp1 / disp2 have %d / %d / %d / %d / %d rows"
+                             % (who, n, f1.numel(), f2.numel(), s.numel(), d1.shape[0], d2.shape[0]))
+        # the library reads the arrays on its own streams: they must be complete before the graph takes them
+        torch.cuda.current_stream(d1.device).synchronize()
+        return capi.Graph.from_device_arrays(ma, f1.data_ptr(), f2.data_ptr(), s.data_ptr(), d1.data_ptr(), d2.data_ptr(), device=dev,
+                                             banned=tuple(banned))       # (f1, f2, s are read inside the call only)
+    ma.feat1, ma.feat2 = np.ascontiguousarray(feat1, np.uint32), np.ascontiguousarray(feat2, np.uint32)
+    ma.sim = sim.detach().to(torch.float32).cpu().numpy()
+    # the library reads the flows on its own streams: they must be complete before the graph takes them
+    torch.cuda.current_stream(d1.device).synchronize()
+    return capi.Graph.from_device_flows(ma, d1.data_ptr(), d2.data_ptr(), device=dev, banned=tuple(banned))
+
+
 def _tangent_rows(who, tangents, n_rows, idx, device):
     """The tangents of (disp1, disp2, sim) in the caller's rows -> what Batch.jvp takes: the graph's rows (banned pairs dropped
     through idx), contiguous on `device`, float32 or - when one of them is float64 - float64; None stays None (= zero)."""
@@ -80,15 +116,12 @@ class _Refine(torch.autograd.Function):
         device = disp1.device
         d1 = disp1.detach().to(torch.float32).reshape(-1, 18).contiguous()
         d2 = disp2.detach().to(torch.float32).reshape(-1, 18).contiguous()
-        ma = MatchArrays(image_names=list(meta["image_names"]), facts=meta["facts"], pair_img1=meta["pair_img1"],
-                         pair_img2=meta["pair_img2"], pair_off=meta["pair_off"], feat1=meta["feat1"], feat2=meta["feat2"],
-                         sim=sim.detach().to(torch.float32).cpu().numpy(), disp1=None, disp2=None)
         dev = device.index if device.index is not None else torch.cuda.current_device()
         with torch.cuda.device(dev):
             stream = torch.cuda.current_stream(device).cuda_stream
-            # the library reads the flows on its own streams: they must be complete before the graph takes them
-            torch.cuda.current_stream(device).synchronize()
-            g = capi.Graph.from_device_flows(ma, d1.data_ptr(), d2.data_ptr(), device=dev, banned=tuple(meta["banned"]))
+            g = _build_graph("refine", d1, d2, sim, dev, image_names=meta["image_names"], facts=meta["facts"], pair_img1=meta["pair_img1"],
+                             pair_img2=meta["pair_img2"], pair_off=meta["pair_off"], feat1=meta["feat1"], feat2=meta["feat2"],
+                             banned=meta["banned"])
             p = capi.Problem(g, device_graph_stage=dev)
             b = capi.Batch(p, dev, tukey_variant=meta["tukey_variant"])      # (gathers its records: d1 / d2 may go after this)
             b.solve(stream=stream, want_stats=False)
@@ -142,6 +175,8 @@ def refine(disp1, disp2, sim, *, image_names, pair_img1, pair_img2, pair_off, fe
 
     disp1, disp2: [n_matches, 18] (or [n_matches, 9, 2]) float32 tensors on one HIP device - disp2 = flow image1 -> image2, disp1 =
     flow image2 -> image1 (lfr_graph_from_arrays); sim: [n_matches] similarities (any device); the rest as lfr_graph_from_arrays.
+    feat1, feat2 (integer tensors) and sim all on the device of disp1: they stay there and the graph is numbered on the GPU
+    (lfr_graph_from_device_arrays) - same graph, same results, no copy of the similarities to the host.
     Returns (positions, node_image, node_feature): [n_nodes, 2] float64 device positions (di, dj per node, the solver's unit) and the
     node -> (image index, feature index) map as numpy arrays.  Gradients reach disp1, disp2 and sim; the matches of banned pairs
     get 0.
@@ -156,8 +191,10 @@ def refine(disp1, disp2, sim, *, image_names, pair_img1, pair_img2, pair_off, fe
     facts = np.ones(len(image_names), np.float32) if image_facts is None else np.ascontiguousarray(image_facts, np.float32)
     if not disp1.is_cuda or disp2.device != disp1.device:
         raise ValueError("refine: disp1 and disp2 must be on the same HIP device")
+    if not _all_on(disp1.device, feat1, feat2, sim):         # (all three on the flows' device: they stay there, _build_graph)
+        feat1, feat2 = np.ascontiguousarray(feat1, np.uint32), np.ascontiguousarray(feat2, np.uint32)
     meta = {"image_names": list(image_names), "facts": facts, "pair_img1": pair_img1, "pair_img2": pair_img2, "pair_off": pair_off,
-            "feat1": np.ascontiguousarray(feat1, np.uint32), "feat2": np.ascontiguousarray(feat2, np.uint32),
+            "feat1": feat1, "feat2": feat2,
             "banned": tuple(banned), "tukey_variant": tukey_variant, "return_covariance": bool(return_covariance),
             "gauss_newton": gauss_newton,
             "kept_rows": _kept_rows(pair_img1, pair_img2, pair_off, list(image_names), tuple(banned))}
@@ -249,15 +286,11 @@ class Refiner:
         d1 = disp1.detach().to(torch.float32).reshape(-1, 18).contiguous()
         d2 = disp2.detach().to(torch.float32).reshape(-1, 18).contiguous()
         self.n_rows = int(d1.shape[0])
-        ma = MatchArrays(image_names=list(image_names), facts=facts, pair_img1=pair_img1, pair_img2=pair_img2, pair_off=pair_off,
-                         feat1=np.ascontiguousarray(feat1, np.uint32), feat2=np.ascontiguousarray(feat2, np.uint32),
-                         sim=sim.detach().to(torch.float32).cpu().numpy(), disp1=None, disp2=None)
         rows = _kept_rows(pair_img1, pair_img2, pair_off, list(image_names), tuple(banned))
         self._idx = None if rows is None else torch.as_tensor(rows, device=self.device)
         with torch.cuda.device(dev):
-            # the library reads the flows on its own streams: they must be complete before the graph takes them (once, here)
-            torch.cuda.current_stream(self.device).synchronize()
-            self._graph = capi.Graph.from_device_flows(ma, d1.data_ptr(), d2.data_ptr(), device=dev, banned=tuple(banned))
+            self._graph = _build_graph("Refiner", d1, d2, sim, dev, image_names=image_names, facts=facts, pair_img1=pair_img1,
+                                       pair_img2=pair_img2, pair_off=pair_off, feat1=feat1, feat2=feat2, banned=banned)
             self._problem = capi.Problem(self._graph, device_graph_stage=dev)
             self._batch = capi.Batch(self._problem, dev, tukey_variant=tukey_variant)     # (gathers its records: d1 / d2 may go after this)
         self.n_nodes = self._graph.n_nodes

@@ -112,6 +112,8 @@ def lib():
         "lfr_graph_from_matches_file_device": (C.c_int, [C.c_char_p, cpp, C.c_int, C.c_int, pp]),
         "lfr_graph_from_arrays": (C.c_int, [i32, cpp, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, cpp, C.c_int, pp]),
         "lfr_graph_from_arrays_device_flows": (C.c_int, [i32, cpp, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, C.c_int, cpp, C.c_int, pp]),
+        "lfr_graph_from_device_arrays": (C.c_int, [i32, cpp, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, C.c_int, cpp, C.c_int, pp]),
+        "lfr_debug_graph_build_spans": (C.c_int, [vp, C.c_int]),
         "lfr_graph_to_device": (C.c_int, [vp, C.c_int]),
         "lfr_graph_evict_device": (C.c_int, [vp]),
         "lfr_graph_free": (None, [vp]),
@@ -187,7 +189,7 @@ def lib():
 
 
 EXPORTS = ["lfr_version", "lfr_last_error", "lfr_graph_from_files", "lfr_graph_from_matches_file", "lfr_graph_from_matches_file_device",
-           "lfr_graph_from_arrays", "lfr_graph_from_arrays_device_flows", "lfr_graph_to_device", "lfr_graph_evict_device",
+           "lfr_graph_from_arrays", "lfr_graph_from_arrays_device_flows", "lfr_graph_from_device_arrays", "lfr_debug_graph_build_spans", "lfr_graph_to_device", "lfr_graph_evict_device",
            "lfr_problem_build_hip_ex", "lfr_problem_build_hip_shard", "lfr_problem_cc_sharded", "lfr_hip_reserve", "lfr_hip_trim", "lfr_batch_positions_view", "lfr_batch_positions_view_f32", "lfr_bisect_graph", "lfr_debug_eval_edges", "lfr_debug_ls_next_step", "lfr_debug_solve_damped", "lfr_debug_tree_plan", "lfr_debug_solve_tree", "lfr_debug_pool_selftest", "lfr_debug_sort_pairs", "lfr_debug_exclusive_sum", "lfr_debug_recursive_cut", "lfr_hip_synchronize", "lfr_graph_free", "lfr_graph_num_nodes", "lfr_graph_num_edges",
            "lfr_graph_num_images", "lfr_graph_get_nodes", "lfr_graph_image_name", "lfr_graph_image_fact",
            "lfr_write_matching_file", "lfr_problem_build", "lfr_problem_build_labels", "lfr_problem_build_hip", "lfr_problem_free", "lfr_problem_get_stats",
@@ -275,6 +277,33 @@ class Graph:
             _ptr(a["off"]), _ptr(a["f1"]), _ptr(a["f2"]), _ptr(a["sim"]), C.c_void_p(disp1_ptr), C.c_void_p(disp2_ptr),
             device, _cstrs(list(banned)), len(banned), C.byref(h)))
         return cls(h)
+
+    @classmethod
+    def from_device_arrays(cls, ma, feat1_ptr, feat2_ptr, sim_ptr, disp1_ptr, disp2_ptr, device=0, banned=()):
+        """lfr_graph_from_device_arrays: the nodes are numbered on the GPU.  ma: MatchArrays of which only the host-side fields are
+        read (image_names, facts, pair_img1, pair_img2, pair_off); feat*_ptr / sim_ptr / disp*_ptr: device addresses (int, e.g.
+        tensor.data_ptr(); 0 = NULL) of uint32 [n_matches], float32 [n_matches] and float32 [n_matches, 18] arrays on HIP device
+        `device`, complete when the call is made.  The caller keeps the flows alive until the Batch exists; the other three are read
+        inside the call only.  The graph is resident on `device` afterwards."""
+        h = C.c_void_p()
+        facts = np.ascontiguousarray(ma.facts, np.float32)
+        p1, p2 = np.ascontiguousarray(ma.pair_img1, np.int32), np.ascontiguousarray(ma.pair_img2, np.int32)
+        off = np.ascontiguousarray(ma.pair_off, np.int64)
+        if len(off) != len(p1) + 1 or len(p2) != len(p1):
+            raise ValueError("from_device_arrays: pair_off needs one entry more than pair_img1 / pair_img2")
+        _check(lib().lfr_graph_from_device_arrays(
+            len(ma.image_names), _cstrs(ma.image_names), _ptr(facts), len(p1), _ptr(p1), _ptr(p2), _ptr(off),
+            C.c_void_p(feat1_ptr), C.c_void_p(feat2_ptr), C.c_void_p(sim_ptr), C.c_void_p(disp1_ptr), C.c_void_p(disp2_ptr),
+            int(device), _cstrs(list(banned)), len(banned), C.byref(h)))
+        return cls(h)
+
+    @staticmethod
+    def build_spans():
+        """Spans (ms) of this thread's latest from_device_arrays (lfr_debug_graph_build_spans); the four device spans are 0 unless
+        LFR_GRAPHBUILD_SPANS=1 was set when the library first built such a graph."""
+        ms = np.zeros(7, np.float64)
+        _check(lib().lfr_debug_graph_build_spans(_ptr(ms), 7))
+        return dict(zip(("expand", "sort", "scans", "scatter", "host_mirror", "finish", "host_pair_table"), ms.tolist()))
 
     def close(self):
         if self._h:
