@@ -33,6 +33,17 @@ __device__ __forceinline__ double fast_rcp(double x) {
     r = fma(fma(-x, r, 1.0), r, r);
     return r;
 }
+// fmin(a, b) as the bare v_min_f64.  fmin() puts a canonicalizing v_max_f64 x, x in front of every operand the compiler cannot prove
+// quiet (an asm result, a v_rcp): two more fp64 instructions per call.  They change no finite value and no quiet NaN (v_min_f64 returns
+// the other operand for one, as fmin does); only a SIGNALLING NaN comes out differently (quieted and returned, where fmin drops it), and
+// arithmetic produces none.  For the running minimum of the elimination's pivots, which is only ever tested `> 0`.  This holds in the
+// kernels' float mode (IEEE = 1, the default of a compute kernel, which no kernel here changes): there v_min_f64 returns the non-NaN
+// operand for a quiet NaN; a kernel compiled with another mode must not use it.
+__device__ __forceinline__ double min_f64_bare(double a, double b) {
+    double r;
+    asm("v_min_f64 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
+    return r;
+}
 // sqrt(x) for finite x >= 0 in the normal range (here: rho' * sim in [0, ~1]): v_rsq_f64 + Newton/Goldschmidt
 __device__ __forceinline__ double fast_sqrt(double x) {
     if (!(x > 1e-290)) return sqrt(x);                 // zero / tiny: take the exact path (rare: Tukey outliers give 0)
@@ -798,18 +809,117 @@ __device__ __forceinline__ void fmac_bcast(double nf, double &a, double &b, doub
                  : "+v"(a), "+v"(b), "+v"(c), "+v"(d) : [nf] "v"(nf), [k] "n"(K), [bank] "n"(BANK));
 }
 #undef LFR_FMAC_DPP
-// columns [C0, CL) of h, then rhs, four to a statement
-template <int K, int BANK, int C0, int CL>
-__device__ __forceinline__ void fmac_bcast_row(double nf, double (&h)[CL], double &rhs) {
-    constexpr int n = CL - C0;                       // live columns; rhs rides as column n
-    if constexpr (n >= 4) {
-        fmac_bcast<K, BANK>(nf, h[C0], h[C0 + 1], h[C0 + 2], h[C0 + 3]);
-        fmac_bcast_row<K, BANK, C0 + 4, CL>(nf, h, rhs);
-    } else if constexpr (n == 3) fmac_bcast<K, BANK>(nf, h[C0], h[C0 + 1], h[C0 + 2], rhs);
-    else if constexpr (n == 2) fmac_bcast<K, BANK>(nf, h[C0], h[C0 + 1], rhs);
-    else if constexpr (n == 1) fmac_bcast<K, BANK>(nf, h[C0], rhs);
-    else fmac_bcast<K, BANK>(nf, rhs);
+
+// The rank-1 update of elimination step K of the packed solve (GaussJordan, lfr_solve.hip) as ONE asm statement: columns [C0, CL) of h,
+// then rhs, each h_c += nf * (h_c of lane K of the row).  NV == 8 (two groups per DPP row): all of the lower half (banks 0-1 take lane
+// K), then all of the upper half (banks 2-3 take lane K + 8), the same instructions in the same order as one statement per half.
+// Hazard ("VALU writes a VGPR -> a DPP operand reads that VGPR": 2 wait states; nothing inside asm is padded by hipcc):
+//  - the only DPP operands are h_c and rhs; nf is a plain source and needs no distance from its v_cndmask.
+//  - the statement's instructions write N = CL - C0 + 1 DIFFERENT registers and each reads only its own, so inside a half nothing
+//    reads what the statement wrote.  NV == 8: the upper half reads h_c again, N - 1 independent v_fmac after the lower half wrote it -
+//    two wait states or more from N = 3 on; the last steps (N = 2: one column and rhs, N = 1: rhs alone) keep a pad of 2 - (N - 1)
+//    states between the halves.
+//  - every h_c was last written by the previous step's statement (volatile, so in program order), and the pivot broadcast, the
+//    reciprocal's five instructions, the multiply and the selects of nf lie in between (nf depends on that statement's h_K).  What the
+//    argument cannot see is the compiler's own code in front of the FIRST instruction: at step 0 the v_add / v_cndmask of the matrix
+//    build, at any step a register copy made for the operands.  Hence one s_nop 1 (two states) opens the statement, and none follows.
+//  - the other DPP hazard, "VALU writes EXEC -> DPP op: 5 wait states": no VALU writes EXEC near a statement.  The step tests
+//    `K + 1 < n_steps` are scalar (s_cmp / s_cbranch_scc: n_steps lives in an SGPR, packed_step), the selects of nf are v_cndmask, and
+//    every lane of the wave is active through the whole elimination - no v_cmpx, no divergent branch.  An edit that makes a step's
+//    branch divergent has to put five states in front of the statement.
+// (CovGaussJordan, lfr_packed_normal_device.hpp, keeps the four-to-a-statement fmac_bcast above: the inversion is off the hot path.)
+template <int C0, int CL, int I>
+__device__ __forceinline__ double &gj_col(double (&h)[CL], double &rhs) {
+    if constexpr (C0 + I < CL) return h[C0 + I]; else return rhs;
 }
+#define LFR_GJ16(i) "v_fmac_f64_dpp %" #i ", %" #i ", %[nf] row_newbcast:%[k] row_mask:0xf bank_mask:0xf\n\t"
+#define LFR_GJ8A(i) "v_fmac_f64_dpp %" #i ", %" #i ", %[nf] row_newbcast:%[k] row_mask:0xf bank_mask:0x3\n\t"
+#define LFR_GJ8B(i) "v_fmac_f64_dpp %" #i ", %" #i ", %[nf] row_newbcast:%[k8] row_mask:0xf bank_mask:0xc\n\t"
+#define LFR_GJOP(i) "+v"(gj_col<C0, CL, i>(h, rhs))
+#define LFR_SEQ1(M) M(0)
+#define LFR_SEQ2(M) LFR_SEQ1(M) M(1)
+#define LFR_SEQ3(M) LFR_SEQ2(M) M(2)
+#define LFR_SEQ4(M) LFR_SEQ3(M) M(3)
+#define LFR_SEQ5(M) LFR_SEQ4(M) M(4)
+#define LFR_SEQ6(M) LFR_SEQ5(M) M(5)
+#define LFR_SEQ7(M) LFR_SEQ6(M) M(6)
+#define LFR_SEQ8(M) LFR_SEQ7(M) M(7)
+#define LFR_SEQ9(M) LFR_SEQ8(M) M(8)
+#define LFR_SEQ10(M) LFR_SEQ9(M) M(9)
+#define LFR_SEQ11(M) LFR_SEQ10(M) M(10)
+#define LFR_SEQ12(M) LFR_SEQ11(M) M(11)
+#define LFR_SEQ13(M) LFR_SEQ12(M) M(12)
+#define LFR_SEQ14(M) LFR_SEQ13(M) M(13)
+#define LFR_SEQ15(M) LFR_SEQ14(M) M(14)
+#define LFR_SEQ16(M) LFR_SEQ15(M) M(15)
+#define LFR_OPS1 LFR_GJOP(0)
+#define LFR_OPS2 LFR_OPS1, LFR_GJOP(1)
+#define LFR_OPS3 LFR_OPS2, LFR_GJOP(2)
+#define LFR_OPS4 LFR_OPS3, LFR_GJOP(3)
+#define LFR_OPS5 LFR_OPS4, LFR_GJOP(4)
+#define LFR_OPS6 LFR_OPS5, LFR_GJOP(5)
+#define LFR_OPS7 LFR_OPS6, LFR_GJOP(6)
+#define LFR_OPS8 LFR_OPS7, LFR_GJOP(7)
+#define LFR_OPS9 LFR_OPS8, LFR_GJOP(8)
+#define LFR_OPS10 LFR_OPS9, LFR_GJOP(9)
+#define LFR_OPS11 LFR_OPS10, LFR_GJOP(10)
+#define LFR_OPS12 LFR_OPS11, LFR_GJOP(11)
+#define LFR_OPS13 LFR_OPS12, LFR_GJOP(12)
+#define LFR_OPS14 LFR_OPS13, LFR_GJOP(13)
+#define LFR_OPS15 LFR_OPS14, LFR_GJOP(14)
+#define LFR_OPS16 LFR_OPS15, LFR_GJOP(15)
+// (half_pad: what the upper half of an 8-row step waits after the lower half)
+#define LFR_GJ_STEP(n, half_pad)                                                                                                        \
+    if constexpr (N == n) {                                                                                                            \
+        if constexpr (NV == 16) asm volatile("s_nop 1\n\t" LFR_SEQ##n(LFR_GJ16) : LFR_OPS##n : [nf] "v"(nf), [k] "n"(K));              \
+        else asm volatile("s_nop 1\n\t" LFR_SEQ##n(LFR_GJ8A) half_pad LFR_SEQ##n(LFR_GJ8B) : LFR_OPS##n : [nf] "v"(nf), [k] "n"(K), [k8] "n"(K + 8)); \
+    }
+template <int NV, int K, int C0, int CL>
+__device__ __forceinline__ void fmac_bcast_step(double nf, double (&h)[CL], double &rhs) {
+    static_assert(NV == 8 || NV == 16, "one DPP row holds the group");
+    constexpr int N = CL - C0 + 1;                   // live columns and rhs
+    static_assert(N >= 1 && N <= (NV == 16 ? 16 : 8), "a step updates at most NV - 1 columns and rhs");
+    LFR_GJ_STEP(1, "s_nop 1\n\t") LFR_GJ_STEP(2, "s_nop 0\n\t") LFR_GJ_STEP(3, "") LFR_GJ_STEP(4, "") LFR_GJ_STEP(5, "") LFR_GJ_STEP(6, "")
+    LFR_GJ_STEP(7, "") LFR_GJ_STEP(8, "") LFR_GJ_STEP(9, "") LFR_GJ_STEP(10, "") LFR_GJ_STEP(11, "") LFR_GJ_STEP(12, "") LFR_GJ_STEP(13, "")
+    LFR_GJ_STEP(14, "") LFR_GJ_STEP(15, "") LFR_GJ_STEP(16, "")
+}
+#undef LFR_GJ_STEP
+#undef LFR_GJ16
+#undef LFR_GJ8A
+#undef LFR_GJ8B
+#undef LFR_GJOP
+#undef LFR_SEQ1
+#undef LFR_OPS1
+#undef LFR_SEQ2
+#undef LFR_OPS2
+#undef LFR_SEQ3
+#undef LFR_OPS3
+#undef LFR_SEQ4
+#undef LFR_OPS4
+#undef LFR_SEQ5
+#undef LFR_OPS5
+#undef LFR_SEQ6
+#undef LFR_OPS6
+#undef LFR_SEQ7
+#undef LFR_OPS7
+#undef LFR_SEQ8
+#undef LFR_OPS8
+#undef LFR_SEQ9
+#undef LFR_OPS9
+#undef LFR_SEQ10
+#undef LFR_OPS10
+#undef LFR_SEQ11
+#undef LFR_OPS11
+#undef LFR_SEQ12
+#undef LFR_OPS12
+#undef LFR_SEQ13
+#undef LFR_OPS13
+#undef LFR_SEQ14
+#undef LFR_OPS14
+#undef LFR_SEQ15
+#undef LFR_OPS15
+#undef LFR_SEQ16
+#undef LFR_OPS16
 
 // Four sums at once.  S >= 16: a TRANSPOSED butterfly - after the xor-8 step the lower half of a 16-lane row carries the partial sums
 // of a (b), the upper half those of c (d); after the mirror step inside 8 lanes each quad carries one of the four; two quad steps, then

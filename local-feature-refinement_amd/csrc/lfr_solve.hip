@@ -125,13 +125,12 @@ struct GaussJordan {
             // and an fma per column, 75 % of the kernel's LDS instructions).  NV == 8: two groups per DPP row, the update is issued
             // per half with a bank mask (lanes 0-7 take lane K, lanes 8-15 lane K + 8).
             const double piv = (NV == 16) ? bcast16_f64<K>(h[K]) : bcast8_f64<K>(h[K]);
-            minpiv = fmin(minpiv, piv);
+            minpiv = min_f64_bare(minpiv, piv);
             double nf = -(h[K] * fast_rcp(piv));
             const bool is_k = row == K;
             nf = is_k ? 0.0 : nf;                                      // (the pivot lane's own row stays: h += 0 * h)
             piv_own = is_k ? piv : piv_own;
-            if constexpr (NV == 16) fmac_bcast_row<K, 0xf, c0, CL>(nf, h, rhs);
-            else { fmac_bcast_row<K, 0x3, c0, CL>(nf, h, rhs); fmac_bcast_row<K + 8, 0xc, c0, CL>(nf, h, rhs); }
+            fmac_bcast_step<NV, K, c0, CL>(nf, h, rhs);                // the whole step: one statement, one hazard pad (lfr_device.hpp)
             if constexpr (K + 1 < CL && K + 1 < NV) {
                 if (K + 1 < n_steps) GaussJordan<NV, LPR, K + 1, CL>::run(h, rhs, piv_own, minpiv, row, part, n_steps);
             }
@@ -187,6 +186,11 @@ __device__ __forceinline__ double packed_step(const double *A, const int row, co
     double rhs = rhs0;
     double piv_own = 1.0;
     double minpiv = 1.0;
+    // DPP classes: the step count is re-defined here, opaquely, for every LM step.  nv2_max is constant over the solve, and left visible
+    // the `K + 1 < n_steps` tests of all elimination steps are hoisted out of the solve's loop as 64-bit masks, spilled to VGPR lanes and
+    // fetched back per step (two v_readlane and an s_andn2 in front of every branch) where one s_cmp against the SGPR does it.
+    int n_steps = nv2_max;
+    if constexpr (LPR == 1 && NV <= 16) asm volatile("" : "+s"(n_steps));
     // build the lane's columns (LPR*c + part of the own row) and eliminate, in the instantiation
     // sized for the largest system of the wave
     auto lm_solve = [&](auto cl_tag) {
@@ -208,9 +212,9 @@ __device__ __forceinline__ double packed_step(const double *A, const int row, co
         }
         mark();
         ISA_MARK("gauss_jordan");
-        GaussJordan<NV, LPR, 0, CL>::run(h, rhs, piv_own, minpiv, row, part, nv2_max);
+        GaussJordan<NV, LPR, 0, CL>::run(h, rhs, piv_own, minpiv, row, part, n_steps);
     };
-    const int c_hi = (nv2_max + LPR - 1) / LPR;          // wave-uniform
+    const int c_hi = (n_steps + LPR - 1) / LPR;          // wave-uniform
 #ifdef LFR_ABL_GJ              // matrix build + elimination twice (the first result discarded through an opaque reset)
 #define LFR_CL(n) do { lm_solve(std::integral_constant<int, n>{}); asm volatile("" : "+v"(rhs), "+v"(piv_own), "+v"(minpiv)); rhs = rhs0; piv_own = 1.0; minpiv = 1.0; lm_solve(std::integral_constant<int, n>{}); } while (0)
 #else

@@ -3,7 +3,9 @@ phase boundaries, no GPU needed), walks the ISA of the kernel in textual order a
 packed class.  The counts are STATIC (one pass over the unrolled code: every edge slot, every elimination step, every instantiation of
 the elimination once); next to the s_memtime phase profile (-DLFR_PROFILE_PHASES) they say what a phase's cycles are spent on.
 usage: python scripts/isa_account.py [kernel-substring [existing.s]] > profiles/r04_isa_account_packed_kernel.txt
-(an existing ISA file given as the second argument is read instead of compiling)"""
+(an existing ISA file given as the second argument is read instead of compiling; the default substring meets the warm-start
+instantiation first: solve_packed_kernelILb0ELb0E names the cold record-reading kernel the bench runs).  The first line of the output
+carries the kernel's VGPR count, scratch size and occupancy from the compiler's own comment block."""
 import collections, os, re, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 C = os.path.join(ROOT, "local-feature-refinement_amd", "csrc")
@@ -61,6 +63,13 @@ for l in lines[start:end]:
     if "dpp" in op or "row_" in t or "quad_perm" in t: dpp[(cls, mark)] += 1
 kinds = ["valu_f64", "valu_other", "lane", "lds", "lds_atomic", "lds_xbar", "vmem", "scratch", "smem", "salu", "waitcnt", "branch", "other"]
 print("solve_packed_kernel<false>: static instruction counts per phase (compile-time unrolled code, one pass), from the ISA of this tree\n")
+# the kernel's resources, from the comment block the compiler writes behind the function (one kernel holds every class: one register
+# allocation; the scratch instructions of each class are the `scratch` column below)
+res = {}
+for l in lines[end:end + 80]:
+    m = re.match(r";\s*(NumVgprs|NumAgprs|NumSgprs|ScratchSize|Occupancy|codeLenInByte)\s*[:=]\s*(\d+)", l)
+    if m and m.group(1) not in res: res[m.group(1)] = int(m.group(2))
+print("kernel %s: %s\n" % (lines[start].split(":")[0], "  ".join("%s %d" % kv for kv in res.items())))
 order = ["0", "loop_top", "5", "gauss_jordan", "step_reductions", "1", "6", "sweep_setup", "eval", "assemble", "eval_cost_only", "cost_only_loop", "2", "3", "4"]
 for c in sorted({k[0] for k in acc}):
     print("class %s" % c)

@@ -63,7 +63,8 @@ for c in ("SQ_WAVE_CYCLES", "SQ_ACTIVE_INST_VALU", "SQ_INSTS_VALU", "SQ_WAIT_ANY
 if summary.get("SQ_WAVE_CYCLES"):
     summary["valu_busy"] = summary.get("SQ_ACTIVE_INST_VALU", 0) / summary["SQ_WAVE_CYCLES"]
     summary["wait_fraction"] = summary.get("SQ_WAIT_ANY", 0) / summary["SQ_WAVE_CYCLES"]
-json.dump(summary, open(os.path.join(prof, TAG + "_pmc_config5.json"), "w"), indent=1)
+if blocks:                         # (only when the config-5 passes were collected)
+    json.dump(summary, open(os.path.join(prof, TAG + "_pmc_config5.json"), "w"), indent=1)
 print(json.dumps({k: v for k, v in summary.items() if k not in ("kernels", "source", "correction", "workload")}, indent=1))
 # cap-sized sparse workload: solve_tree_kernel (one launch per solve, beside three tiny LDS-class launches and a packed one)
 pS = collect("pmcS")
@@ -86,14 +87,15 @@ if trees:
     print("sparse:", json.dumps({k: v for k, v in ssum.items() if k not in ("kernels", "source", "correction", "workload")}, indent=1))
 # config 4: what bench.py reads for roofline.traffic
 # (solve_packed_kernel<false> reads the batch's 80-byte records: the timed steps; <true> gathers from the graph's arrays: the FIRST solve of a batch)
-pk = p4.get("solve_packed_kernel<false>") or next((v for k, v in p4.items() if k.startswith("solve_packed_kernel")), None)
-pk_gather = p4.get("solve_packed_kernel<true>")
+# (since the warm-start instantiations the kernel has a second template argument: <false,false> is the cold record-reading one)
+pk = p4.get("solve_packed_kernel<false,false>") or p4.get("solve_packed_kernel<false>") or next((v for k, v in p4.items() if k.startswith("solve_packed_kernel")), None)
+pk_gather = p4.get("solve_packed_kernel<true,false>") or p4.get("solve_packed_kernel<true>")
 dom = None
 tr = glob.glob(os.path.join(out, "trace", "*kernel_trace.csv"))
 if tr:
     by = collections.defaultdict(list)
     for row in csv.DictReader(open(tr[0])):
-        if short(row["Kernel_Name"]) == "solve_packed_kernel<false>":
+        if short(row["Kernel_Name"]) in ("solve_packed_kernel<false>", "solve_packed_kernel<false,false>"):
             by[int(row["Grid_Size_X"])].append(int(row["End_Timestamp"]) - int(row["Start_Timestamp"]))
     if by:
         dom = {"kernel": "solve_packed_kernel<false>", "by_grid_size_x": {str(g): {"launches": len(v), "avg_us": sum(v) / len(v) / 1e3, "min_us": min(v) / 1e3, "max_us": max(v) / 1e3}
