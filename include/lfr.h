@@ -392,7 +392,7 @@ int64_t lfr_batch_component_info(lfr_batch *b, int64_t *component, int32_t *iter
  * Kernels: one workgroup per component over the batch's kernel classes; H in LDS up to 192 rows, in an HBM workspace above; a dense
  * LDL^T that skips the zeros of each column.  Components above 6144 rows: LFR_ERR_UNSUPPORTED. */
 typedef struct lfr_backward_stats {
-    int64_t n_differentiated;      /* components whose gradient was computed */
+    int64_t n_differentiated;      /* components whose gradient was computed (status 0 and, in fallback mode, 3) */
     int64_t n_not_usable;          /* FAILURE components (zero gradient) */
     int64_t n_indefinite;          /* components whose H met a pivot that is not positive (zero gradient) */
     int64_t n_bound_coordinates;   /* coordinates of usable components held at the +-1 bound */
@@ -417,18 +417,42 @@ typedef struct lfr_backward_stats {
  * Kernels: the classes of up to 32 rows run ONE launch in the covariance's packed layout (2-8 components per wave64, J^T J inverted in
  * registers, v = C ubar); the workgroup classes run the exact mode's kernel with the Gauss-Newton assembly. */
 #define LFR_BACKWARD_GAUSS_NEWTON 2
+/* Gauss-Newton fallback (may be combined with LFR_BACKWARD_F64; with LFR_BACKWARD_GAUSS_NEWTON in the same call: LFR_ERR_ARG, raised
+ * before any output is touched).  The exact mode's contract, per usable component, with one change:
+ *   - the exact Hessian over the free coordinates is assembled and factored, exactly as with flags 0.  Every pivot positive and finite:
+ *     status 0, and the component's outputs - its match rows of grad_disp1/2, its terms of grad_sim - are those of the exact mode bit
+ *     for bit;
+ *   - otherwise the same workgroup rebuilds H as the Gauss-Newton matrix of LFR_BACKWARD_GAUSS_NEWTON over the same free set (bound
+ *     rows and columns the identity's) and factors again.  Success: status 3, "differentiated with the Gauss-Newton matrix" - the
+ *     outputs follow the Gauss-Newton mode's contract (v = (J^T J)^-1 ubar, the exact vector-Jacobian sweep).  A second failure (a node
+ *     tied in only by edges of weight 0 or by saturated Tukey edges, a pivot that is not finite): status 2 and zeros, as today;
+ *   - status 1 (FAILURE components) is unchanged.
+ * lfr_backward_stats keeps its layout: n_differentiated counts status 0 AND 3, n_indefinite status 2 only; how many components fell
+ * back is read from lfr_batch_backward_status.  Everything else is the exact mode's: epochs, errors, the 6144-row limit.  Outputs are
+ * bitwise repeatable and identical for host- and device-assembled batches, float32 is the float64 result rounded once.  A status-3
+ * component of more than 32 rows has bit for bit the outputs LFR_BACKWARD_GAUSS_NEWTON gives on the same solve (the same assembly,
+ * LDL^T, substitutions and sweep on an untouched right-hand side).  In the classes of up to 32 rows the fallback runs in the exact
+ * mode's one-wave-per-component kernel (LDL^T) while the Gauss-Newton mode's packed launch inverts explicitly: there the two agree
+ * to rounding, |difference| <= max(1e-8, 64 eps kappa_2(J^T J)) |value| per component, not bitwise.
+ * lfr_batch_jvp with LFR_JVP_FALLBACK_GAUSS_NEWTON decides from the same matrix with the same code: the statuses of the two calls on
+ * one solve are equal and the adjoint identity holds between them.
+ * Kernels: the exact mode's launch plan with the fallback compiled in; no extra launch, LDS or workspace. */
+#define LFR_BACKWARD_FALLBACK_GAUSS_NEWTON 32
 
 /* Stream-ordered device copy of the latest solve's positions (2 * n_nodes doubles of the whole graph; nodes outside the shard: 0). */
 int lfr_batch_positions_to_device(lfr_batch *b, double *dst_device, void *hip_stream);
 /* The gradient above.  grad_positions_device: 2 * n_nodes doubles (dL/dx of the whole graph); grad_disp1/2_device: n_matches x 18,
  * grad_sim_device: n_matches, float32 (double with LFR_BACKWARD_F64); whole arrays are overwritten.  flags: LFR_BACKWARD_F64 and / or
- * LFR_BACKWARD_GAUSS_NEWTON (0: the exact Hessian, float32 outputs); any other bit: LFR_ERR_ARG.  Runs on `hip_stream` after the
+ * one of LFR_BACKWARD_GAUSS_NEWTON, LFR_BACKWARD_FALLBACK_GAUSS_NEWTON (0: the exact Hessian, float32 outputs); any other bit, or both
+ * Hessian flags together: LFR_ERR_ARG before any output is touched.  Runs on `hip_stream` after the
  * latest solve; asynchronous unless stats != NULL.  LFR_ERR_ARG before the first solve, and between an lfr_batch_set_inputs and the
  * next solve.  The first call sets up its workspace and, for batches whose records do not carry their directed-edge ids, maps records to
  * edges from the graph (which must still be alive; lfr_batch_set_inputs shares the map). */
 int lfr_batch_backward(lfr_batch *b, const double *grad_positions_device, void *grad_disp1_device, void *grad_disp2_device,
                        void *grad_sim_device, int flags, void *hip_stream, lfr_backward_stats *stats);
-/* Per component (order of lfr_batch_component_info) of the latest backward: 0 differentiated, 1 not usable, 2 indefinite.
+/* Per component (order of lfr_batch_component_info) of the latest backward: 0 differentiated, 1 not usable, 2 indefinite (zero
+ * gradient), 3 differentiated with the Gauss-Newton matrix after the exact Hessian proved indefinite (only with
+ * LFR_BACKWARD_FALLBACK_GAUSS_NEWTON).
  * Waits for that backward.  Returns the count (< 0: error, LFR_ERR_ARG before the first backward). */
 int64_t lfr_batch_backward_status(lfr_batch *b, int32_t *status);
 
@@ -458,8 +482,8 @@ int64_t lfr_batch_backward_status(lfr_batch *b, int32_t *status);
  * Output: tan_positions_device, 2 * n_nodes doubles, the whole array is overwritten: xdot for the free coordinates of usable
  * components; 0 for bound coordinates, roots and constant nodes, for nodes outside solved components or outside the shard, for
  * FAILURE components (status 1) and for components whose factorization meets a pivot that is not positive (status 2).
- * Errors and state: LFR_ERR_ARG before the first solve, between an lfr_batch_set_inputs and the next solve, and for an unknown flag
- * bit; LFR_ERR_UNSUPPORTED for a batch over one rank's connected components (lfr_problem_cc_sharded = 1) and for components above
+ * Errors and state: LFR_ERR_ARG before the first solve, between an lfr_batch_set_inputs and the next solve, for an unknown flag
+ * bit and for LFR_JVP_GAUSS_NEWTON together with LFR_JVP_FALLBACK_GAUSS_NEWTON; LFR_ERR_UNSUPPORTED for a batch over one rank's connected components (lfr_problem_cc_sharded = 1) and for components above
  * 6144 rows.  Runs on `hip_stream` after the latest solve; asynchronous unless stats != NULL.  Changes nothing the solve, the backward
  * or the covariance read; lfr_batch_set_inputs waits by event for the latest jvp.  Results are bitwise repeatable from call to call
  * and identical for host- and device-assembled batches; no fp64 value goes through a global-memory atomic.
@@ -467,7 +491,7 @@ int64_t lfr_batch_backward_status(lfr_batch *b, int32_t *status);
  * mode), the right-hand side summed owner-computes in record order, H in LDS up to 192 rows and in an HBM workspace above; in
  * Gauss-Newton mode the classes of up to 32 rows run ONE launch in the covariance's packed layout (xdot_row = C_row . b). */
 typedef struct lfr_jvp_stats {
-    int64_t n_differentiated;      /* components whose tangent was computed */
+    int64_t n_differentiated;      /* components whose tangent was computed (status 0 and, in fallback mode, 3) */
     int64_t n_not_usable;          /* FAILURE components (zero tangent) */
     int64_t n_indefinite;          /* components whose H met a pivot that is not positive (zero tangent) */
     int64_t n_bound_coordinates;   /* coordinates of usable components held at the +-1 bound */
@@ -475,9 +499,21 @@ typedef struct lfr_jvp_stats {
 } lfr_jvp_stats;
 #define LFR_JVP_F64 1              /* the three tangent INPUTS are double instead of float32 */
 #define LFR_JVP_GAUSS_NEWTON 2     /* H = J^T J over the free coordinates, as LFR_BACKWARD_GAUSS_NEWTON */
+/* Gauss-Newton fallback, the H of LFR_BACKWARD_FALLBACK_GAUSS_NEWTON (may be combined with LFR_JVP_F64; with LFR_JVP_GAUSS_NEWTON in
+ * the same call: LFR_ERR_ARG, nothing written).  Per usable component the exact Hessian is factored as with flags 0 - success: status
+ * 0, xdot bit for bit the exact mode's - and where it meets a pivot that is not positive or not finite the same workgroup rebuilds H
+ * as J^T J over the same free set and factors again: status 3, xdot = (J^T J)^-1 b with the exact b (built once); a second failure:
+ * status 2, zeros.  Status 1 unchanged.  lfr_jvp_stats: n_differentiated counts status 0 and 3, n_indefinite status 2.  The statuses
+ * equal those of lfr_batch_backward with LFR_BACKWARD_FALLBACK_GAUSS_NEWTON on the same solve, and the adjoint identity holds between
+ * the two.  Repeatability, assemblies, errors (LFR_ERR_UNSUPPORTED for cc_sharded batches and above 6144 rows) as in the other modes.
+ * A status-3 component of more than 32 rows has bit for bit the xdot of LFR_JVP_GAUSS_NEWTON; in the classes of up to 32 rows (one
+ * wave per component and LDL^T here, an explicit inverse in the Gauss-Newton mode's packed launch) the two agree to rounding,
+ * |difference| <= max(1e-8, 64 eps kappa_2(J^T J)) |xdot| per component. */
+#define LFR_JVP_FALLBACK_GAUSS_NEWTON 32
 int lfr_batch_jvp(lfr_batch *b, const void *tan_disp1_device, const void *tan_disp2_device, const void *tan_sim_device,
                   double *tan_positions_device, int flags, void *hip_stream, lfr_jvp_stats *stats);
-/* Per component (order of lfr_batch_component_info) of the latest jvp: 0 differentiated, 1 not usable, 2 indefinite.
+/* Per component (order of lfr_batch_component_info) of the latest jvp: 0 differentiated, 1 not usable, 2 indefinite (zero tangent),
+ * 3 differentiated with the Gauss-Newton matrix after the exact Hessian proved indefinite (only with LFR_JVP_FALLBACK_GAUSS_NEWTON).
  * Waits for that jvp.  Returns the count (< 0: error, LFR_ERR_ARG before the first jvp). */
 int64_t lfr_batch_jvp_status(lfr_batch *b, int32_t *status);
 

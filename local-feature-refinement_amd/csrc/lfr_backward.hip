@@ -18,6 +18,10 @@
 // the covariance's layout (lfr_packed_normal_device.hpp: 64/S components per wave64, one-wave workgroups, no barriers), its sweep and
 // its in-register inversion with the bound rows and columns replaced by the identity's, v = C ubar as one dot product per lane, then the
 // vector-Jacobian sweep over the re-read records.
+//
+// Gauss-Newton fallback (LFR_BACKWARD_FALLBACK_GAUSS_NEWTON): the exact mode's launches with FB = true.  A workgroup whose exact
+// Hessian is indefinite clears the triangle, assembles J^T J over the same free set and factors again (bwd_refactor_gauss_newton);
+// the right-hand side is untouched.  Status 0: the exact mode's bits; 3: the Gauss-Newton matrix; 2: both failed.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -64,8 +68,11 @@ __device__ __forceinline__ void bwd_sweep_edge(const BwdArgs &a, const EdgeRec &
 }
 
 // GN: H is the loss-corrected Gauss-Newton matrix (bwd_assemble<T, false, true>) instead of the exact Hessian
-template <int T, bool LDS_MATRIX, bool GN>
+// FB: the exact Hessian, and where bwd_ldlt finds it indefinite the Gauss-Newton matrix in the same workgroup (status 3).  A template
+// parameter, not a field of the arguments: the instantiations of the two pure modes stay the code they were
+template <int T, bool LDS_MATRIX, bool GN, bool FB = false>
 __global__ __launch_bounds__(T) void backward_kernel(const BwdArgs a) {
+    static_assert(!(GN && FB), "the fallback starts from the exact Hessian");
     extern __shared__ double bsh[];
     const int di = a.desc_begin + blockIdx.x, tid = threadIdx.x;
     const CompDesc d = a.descs[di];
@@ -104,7 +111,14 @@ __global__ __launch_bounds__(T) void backward_kernel(const BwdArgs a) {
     __syncthreads();
 
     // 3. LDL^T over the nonzeros of each column
-    const bool indefinite = bwd_ldlt<T>(H, n, lval, lidx, cnt, tid);
+    bool indefinite = bwd_ldlt<T>(H, n, lval, lidx, cnt, tid);
+    int status = 0;
+    if constexpr (FB) {
+        if (indefinite) {                                     // (block-uniform) the exact Hessian is indefinite: J^T J, same v, same fr
+            indefinite = bwd_refactor_gauss_newton<T>(a, d, nv, E, ids, H, n, fr, lval, lidx, cnt, tid);
+            status = 3;
+        }
+    }
     if (indefinite) {                                         // zero gradient
         if (tid == 0) a.status[di] = 2;
         return;
@@ -131,7 +145,7 @@ __global__ __launch_bounds__(T) void backward_kernel(const BwdArgs a) {
         const double vd0 = m < nv ? v[2 * m] : 0., vd1 = m < nv ? v[2 * m + 1] : 0.;
         bwd_sweep_edge(a, e, kind, xof(s, 0), xof(s, 1), xof(m, 0), xof(m, 1), vs0, vs1, vd0, vd1, a.eid[d.edge_off + p]);
     }
-    if (tid == 0) a.status[di] = 0;
+    if (tid == 0) a.status[di] = status;
 }
 
 // ---- Gauss-Newton mode, packed classes (<= 32 rows): the covariance's layout (lfr_packed_normal_device.hpp) ----
@@ -258,6 +272,8 @@ int bwd_setup_extra(lfr_batch *b, lfr::PassState *ps) {
     HIP_TRY(hipFuncSetAttribute((const void *)backward_kernel<kBwdThreads, false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_global));
     HIP_TRY(hipFuncSetAttribute((const void *)backward_kernel<kBwdThreads, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_block));
     HIP_TRY(hipFuncSetAttribute((const void *)backward_kernel<kBwdThreads, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_global));
+    HIP_TRY(hipFuncSetAttribute((const void *)backward_kernel<kBwdThreads, true, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_block));
+    HIP_TRY(hipFuncSetAttribute((const void *)backward_kernel<kBwdThreads, false, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_global));
     return LFR_OK;
 }
 
@@ -278,12 +294,16 @@ int lfr_batch_positions_to_device(lfr_batch *b, double *dst_device, void *hip_st
 
 int lfr_batch_backward(lfr_batch *b, const double *grad_positions_device, void *grad_disp1_device, void *grad_disp2_device,
                        void *grad_sim_device, int flags, void *hip_stream, lfr_backward_stats *stats) {
-    if (!b || !grad_positions_device || !grad_disp1_device || !grad_disp2_device || !grad_sim_device || (flags & ~(LFR_BACKWARD_F64 | LFR_BACKWARD_GAUSS_NEWTON))) {
+    if (!b || !grad_positions_device || !grad_disp1_device || !grad_disp2_device || !grad_sim_device ||
+        (flags & ~(LFR_BACKWARD_F64 | LFR_BACKWARD_GAUSS_NEWTON | LFR_BACKWARD_FALLBACK_GAUSS_NEWTON))) {
         lfr::set_error("bad argument"); return LFR_ERR_ARG;
+    }
+    if ((flags & LFR_BACKWARD_GAUSS_NEWTON) && (flags & LFR_BACKWARD_FALLBACK_GAUSS_NEWTON)) {
+        lfr::set_error("lfr_batch_backward: LFR_BACKWARD_GAUSS_NEWTON and LFR_BACKWARD_FALLBACK_GAUSS_NEWTON exclude each other"); return LFR_ERR_ARG;
     }
     hipStream_t st = (hipStream_t)hip_stream;
     const int f64 = (flags & LFR_BACKWARD_F64) ? 1 : 0;
-    const bool gn = (flags & LFR_BACKWARD_GAUSS_NEWTON) != 0;
+    const bool gn = (flags & LFR_BACKWARD_GAUSS_NEWTON) != 0, fb = (flags & LFR_BACKWARD_FALLBACK_GAUSS_NEWTON) != 0;
     const size_t M = (size_t)b->n_graph_matches, elt = f64 ? 8 : 4;
     { const int rc = lfr::pass_begin(b, &b->bwd, kBackward, 16 * std::max<size_t>(M, 1) + 64, st); if (rc != LFR_OK) return rc; }
     BwdState &s = *static_cast<BwdState *>(b->bwd);
@@ -302,7 +322,7 @@ int lfr_batch_backward(lfr_batch *b, const double *grad_positions_device, void *
     a.status = s.d_status; a.counters = s.d_counters; a.tukey_variant = b->tukey_variant; a.f64 = f64;
     a.n_matches = (uint32_t)M;
     // Packed classes (<= 32 rows).  Gauss-Newton mode: ONE launch of one-wave blocks, each wave hosting 64/S = 2-8 components (1 in
-    // <32,2>), dealt to the classes as lfr_batch_covariance deals its own.  Exact mode: backward_kernel, one wave per component.
+    // <32,2>), dealt to the classes as lfr_batch_covariance deals its own.  Exact mode (with or without the fallback): backward_kernel, one wave per component.
     if (gn) {
         PackedRanges r;
         int nb = 0;
@@ -313,10 +333,12 @@ int lfr_batch_backward(lfr_batch *b, const double *grad_positions_device, void *
         a.desc_begin = b->class_begin[0];
         const int n = b->class_begin[lfr::KC_BLOCK] - a.desc_begin;
         a.scan_all = 1;
-        if (n > 0)
+        if (n > 0 && fb)
+            hipLaunchKernelGGL((backward_kernel<kBwdThreadsSmall, true, false, true>), dim3(n), dim3(kBwdThreadsSmall), bwd_lds_bytes(32, true), st, a);
+        else if (n > 0)
             hipLaunchKernelGGL((backward_kernel<kBwdThreadsSmall, true, false>), dim3(n), dim3(kBwdThreadsSmall), bwd_lds_bytes(32, true), st, a);
     }
-    // Workgroup classes, both modes: one workgroup of 256 threads per component; matrix in LDS up to 192 rows, in HBM above
+    // Workgroup classes, every mode: one workgroup of 256 threads per component; matrix in LDS up to 192 rows, in HBM above
     a.scan_all = 0;
     for (int cls = lfr::KC_BLOCK; cls < lfr::KC_COUNT; ++cls) {
         a.desc_begin = b->class_begin[cls];
@@ -324,7 +346,9 @@ int lfr_batch_backward(lfr_batch *b, const double *grad_positions_device, void *
         if (n <= 0) continue;
         const bool lds_matrix = cls != lfr::KC_GLOBAL;
         const size_t lds = bwd_lds_bytes(rows, lds_matrix);
-        if (!lds_matrix && gn) hipLaunchKernelGGL((backward_kernel<kBwdThreads, false, true>), dim3(n), dim3(kBwdThreads), lds, st, a);
+        if (fb && lds_matrix) hipLaunchKernelGGL((backward_kernel<kBwdThreads, true, false, true>), dim3(n), dim3(kBwdThreads), lds, st, a);
+        else if (fb) hipLaunchKernelGGL((backward_kernel<kBwdThreads, false, false, true>), dim3(n), dim3(kBwdThreads), lds, st, a);
+        else if (!lds_matrix && gn) hipLaunchKernelGGL((backward_kernel<kBwdThreads, false, true>), dim3(n), dim3(kBwdThreads), lds, st, a);
         else if (!lds_matrix) hipLaunchKernelGGL((backward_kernel<kBwdThreads, false, false>), dim3(n), dim3(kBwdThreads), lds, st, a);
         else if (gn) hipLaunchKernelGGL((backward_kernel<kBwdThreads, true, true>), dim3(n), dim3(kBwdThreads), lds, st, a);
         else hipLaunchKernelGGL((backward_kernel<kBwdThreads, true, false>), dim3(n), dim3(kBwdThreads), lds, st, a);

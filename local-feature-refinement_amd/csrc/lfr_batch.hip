@@ -203,7 +203,7 @@ int lfr::pass_histogram(lfr_batch *b, PassState *s, hipStream_t st, int64_t coun
     if (!status.empty()) HIP_TRY(hipMemcpyAsync(status.data(), s->d_status, 4 * status.size(), hipMemcpyDeviceToHost, st));
     HIP_TRY(lfr::stream_wait(st));
     count[0] = count[1] = count[2] = 0;
-    for (int32_t v : status) ++count[v == 0 ? 0 : v == 1 ? 1 : 2];
+    for (int32_t v : status) ++count[(v == 0 || v == 3) ? 0 : v == 1 ? 1 : 2];      // (3: differentiated with the Gauss-Newton fallback)
     float ms = 0.f;
     HIP_TRY(hipEventElapsedTime(&ms, s->ev0, s->ev1));
     *kernel_ms = ms;

@@ -162,7 +162,7 @@ hipEvent_t pass_last_event(const PassState *s);         // end of the latest cal
 int pass_begin(lfr_batch *b, PassState **slot, const PassKind &kind, size_t extra_bytes, hipStream_t st);
 int pass_end(PassState *s, hipStream_t st);             // records ev1; the call is now the pass's latest
 int64_t pass_status(lfr_batch *b, PassState *s, const char *name, int32_t *status);     // lfr_batch_<name>_status
-int pass_histogram(lfr_batch *b, PassState *s, hipStream_t st, int64_t count[3], double *kernel_ms);     // waits for the latest call: descriptors with status 0, 1, 2 and the time between its events
+int pass_histogram(lfr_batch *b, PassState *s, hipStream_t st, int64_t count[3], double *kernel_ms);     // waits for the latest call: descriptors with status 0 or 3, 1, 2 and the time between its events
 // deals the blocks of the one packed launch to the packed classes, waves_per_block waves each (components per wave: solve_geometry())
 void packed_ranges(const lfr_batch *b, int waves_per_block, PackedRanges *r, int *n_blocks);
 }  // namespace lfr

@@ -214,6 +214,25 @@ __device__ __forceinline__ bool bwd_ldlt(double *H, const int n, double *lval, i
     return indefinite;
 }
 
+// The Gauss-Newton fallback of the backward and the jvp (LFR_BACKWARD_FALLBACK_GAUSS_NEWTON, LFR_JVP_FALLBACK_GAUSS_NEWTON): after
+// bwd_ldlt has reported the exact Hessian indefinite, the same workgroup clears the half-factored triangle, assembles the Gauss-Newton
+// matrix over the same free set fr (bound rows and columns the identity's) and factors again.  The right-hand side, fr and the
+// bound-coordinate count are the caller's and are not touched.  Every thread of the block calls it (the verdict it follows is
+// block-uniform) and every thread returns the same: true when J^T J met a pivot that is not positive (or not finite) too.
+template <int T>
+__device__ __forceinline__ bool bwd_refactor_gauss_newton(const BwdArgs &a, const CompDesc &d, const int nv, const EdgeRec *E,
+                                                          const uint32_t *ids, double *H, const int n, const uint8_t *fr, double *lval,
+                                                          int *lidx, int *cnt, const int tid) {
+    __syncthreads();                                          // every thread has read the pivot that failed
+    const size_t nt = bwd_tri(n, 0);
+    for (size_t t = tid; t < nt; t += T) H[t] = 0.0;
+    if (tid == 0) { cnt[0] = 0; cnt[1] = 0; }
+    __syncthreads();
+    bwd_assemble<T, false, true>(a, d, nv, E, ids, H, fr, tid);
+    __syncthreads();
+    return bwd_ldlt<T>(H, n, lval, lidx, cnt, tid);
+}
+
 // ---- forward-mode sensitivity (lfr_jvp.hip): the transpose of the backward's vector-Jacobian sweep ----
 // The tangent of one record's inputs: the 18 flow values and the similarity of directed edge `id` in the match layout (even ids read
 // tan_disp2, odd ids tan_disp1, both tan_sim); a NULL array is a zero tangent.  f64: the arrays hold doubles instead of floats.

@@ -11,6 +11,8 @@
 //                         the component's nodes.  One wave per component for the classes of up to 32 rows in the exact mode.
 //   jvp_gn_packed_kernel  Gauss-Newton mode, classes of up to 32 rows: ONE launch in the covariance's layout.  The sweep adds the
 //                         records' terms into the group's LDS vector, the matrix is inverted in registers, xdot_row = C_row . b.
+// LFR_JVP_FALLBACK_GAUSS_NEWTON: jvp_kernel with FB = true, the backward's fallback (bwd_refactor_gauss_newton) on the same matrix with
+// the same code - equal statuses - and the right-hand side, built once, survives the first factorization.
 // No fp64 value goes through a global-memory atomic; a component's output depends on nothing outside the component.
 #include <hip/hip_runtime.h>
 
@@ -46,8 +48,11 @@ __device__ __forceinline__ void jvp_record(const JvpArgs &ja, const EdgeRec &e, 
 }
 
 // GN: H is the loss-corrected Gauss-Newton matrix (bwd_assemble<T, false, true>) instead of the exact Hessian
-template <int T, bool LDS_MATRIX, bool GN>
+// FB: the exact Hessian, and where bwd_ldlt finds it indefinite the Gauss-Newton matrix in the same workgroup (status 3).  A template
+// parameter, not a field of the arguments: the instantiations of the two pure modes stay the code they were
+template <int T, bool LDS_MATRIX, bool GN, bool FB = false>
 __global__ __launch_bounds__(T) void jvp_kernel(const JvpArgs ja) {
+    static_assert(!(GN && FB), "the fallback starts from the exact Hessian");
     extern __shared__ double jsh[];
     const BwdArgs &a = ja.h;
     const int di = a.desc_begin + blockIdx.x, tid = threadIdx.x;
@@ -116,7 +121,14 @@ __global__ __launch_bounds__(T) void jvp_kernel(const JvpArgs ja) {
     __syncthreads();
 
     // 3. LDL^T over the nonzeros of each column
-    const bool indefinite = bwd_ldlt<T>(H, n, lval, lidx, cnt, tid);
+    bool indefinite = bwd_ldlt<T>(H, n, lval, lidx, cnt, tid);
+    int status = 0;
+    if constexpr (FB) {
+        if (indefinite) {                                     // (block-uniform) the exact Hessian is indefinite: J^T J, same v, same fr
+            indefinite = bwd_refactor_gauss_newton<T>(a, d, nv, E, ids, H, n, fr, lval, lidx, cnt, tid);
+            status = 3;
+        }
+    }
     if (indefinite) {                                         // zero tangent
         if (tid == 0) a.status[di] = 2;
         return;
@@ -137,7 +149,7 @@ __global__ __launch_bounds__(T) void jvp_kernel(const JvpArgs ja) {
 
     // 5. xdot to the component's nodes; a bound coordinate is an exact 0 (also beside a tangent that is not finite)
     for (int i = tid; i < n; i += T) ja.xdot[2 * (size_t)ids[i >> 1] + (i & 1)] = fr[i] ? v[i] : 0.0;
-    if (tid == 0) a.status[di] = 0;
+    if (tid == 0) a.status[di] = status;
 }
 
 // ---- Gauss-Newton mode, packed classes (<= 32 rows): the covariance's layout (lfr_packed_normal_device.hpp) ----
@@ -261,6 +273,8 @@ int jvp_setup_extra(lfr_batch *b, lfr::PassState *ps) {
     HIP_TRY(hipFuncSetAttribute((const void *)jvp_kernel<kJvpThreads, false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_global));
     HIP_TRY(hipFuncSetAttribute((const void *)jvp_kernel<kJvpThreads, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_block));
     HIP_TRY(hipFuncSetAttribute((const void *)jvp_kernel<kJvpThreads, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_global));
+    HIP_TRY(hipFuncSetAttribute((const void *)jvp_kernel<kJvpThreads, true, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_block));
+    HIP_TRY(hipFuncSetAttribute((const void *)jvp_kernel<kJvpThreads, false, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_global));
     return LFR_OK;
 }
 
@@ -273,7 +287,11 @@ extern "C" {
 int lfr_batch_jvp(lfr_batch *b, const void *tan_disp1_device, const void *tan_disp2_device, const void *tan_sim_device,
                   double *tan_positions_device, int flags, void *hip_stream, lfr_jvp_stats *stats) {
     if (!b || !tan_positions_device) { lfr::set_error("lfr_batch_jvp: bad argument"); return LFR_ERR_ARG; }
-    if (flags & ~(LFR_JVP_F64 | LFR_JVP_GAUSS_NEWTON)) { lfr::set_error("lfr_batch_jvp: unknown flag bits 0x%x", flags & ~(LFR_JVP_F64 | LFR_JVP_GAUSS_NEWTON)); return LFR_ERR_ARG; }
+    constexpr int kFlags = LFR_JVP_F64 | LFR_JVP_GAUSS_NEWTON | LFR_JVP_FALLBACK_GAUSS_NEWTON;
+    if (flags & ~kFlags) { lfr::set_error("lfr_batch_jvp: unknown flag bits 0x%x", flags & ~kFlags); return LFR_ERR_ARG; }
+    if ((flags & LFR_JVP_GAUSS_NEWTON) && (flags & LFR_JVP_FALLBACK_GAUSS_NEWTON)) {
+        lfr::set_error("lfr_batch_jvp: LFR_JVP_GAUSS_NEWTON and LFR_JVP_FALLBACK_GAUSS_NEWTON exclude each other"); return LFR_ERR_ARG;
+    }
     if (!tan_disp1_device && !tan_disp2_device && !tan_sim_device) { lfr::set_error("lfr_batch_jvp: no tangent (all three inputs are NULL)"); return LFR_ERR_ARG; }
     if (!tan_disp1_device != !tan_disp2_device) { lfr::set_error("lfr_batch_jvp: tan_disp1 and tan_disp2 go together (both or neither)"); return LFR_ERR_ARG; }
     if (b->cc_sharded) {
@@ -281,7 +299,7 @@ int lfr_batch_jvp(lfr_batch *b, const void *tan_disp1_device, const void *tan_di
         return LFR_ERR_UNSUPPORTED;
     }
     hipStream_t st = (hipStream_t)hip_stream;
-    const bool gn = (flags & LFR_JVP_GAUSS_NEWTON) != 0;
+    const bool gn = (flags & LFR_JVP_GAUSS_NEWTON) != 0, fb = (flags & LFR_JVP_FALLBACK_GAUSS_NEWTON) != 0;
     { const int rc = lfr::pass_begin(b, &b->jvp, kJvp, 64, st); if (rc != LFR_OK) return rc; }
     JvpState &s = *static_cast<JvpState *>(b->jvp);
     if (b->fused) lfr::materialize_records(b, st);     // the packed records have not been written yet: write them (the next solve would write the same bytes)
@@ -300,7 +318,7 @@ int lfr_batch_jvp(lfr_batch *b, const void *tan_disp1_device, const void *tan_di
     ja.t.n_matches = (uint32_t)b->n_graph_matches; ja.t.f64 = (flags & LFR_JVP_F64) ? 1 : 0;
     ja.xdot = tan_positions_device;
     // Packed classes (<= 32 rows).  Gauss-Newton mode: ONE launch of one-wave blocks, each wave hosting 64/S = 2-8 components (1 in
-    // <32,2>), dealt to the classes as lfr_batch_covariance deals its own.  Exact mode: jvp_kernel, one wave per component.
+    // <32,2>), dealt to the classes as lfr_batch_covariance deals its own.  Exact mode (with or without the fallback): jvp_kernel, one wave per component.
     if (gn) {
         PackedRanges r;
         int nb = 0;
@@ -311,10 +329,12 @@ int lfr_batch_jvp(lfr_batch *b, const void *tan_disp1_device, const void *tan_di
         a.desc_begin = b->class_begin[0];
         const int n = b->class_begin[lfr::KC_BLOCK] - a.desc_begin;
         a.scan_all = 1;
-        if (n > 0)
+        if (n > 0 && fb)
+            hipLaunchKernelGGL((jvp_kernel<kJvpThreadsSmall, true, false, true>), dim3(n), dim3(kJvpThreadsSmall), jvp_lds_bytes(32, true), st, ja);
+        else if (n > 0)
             hipLaunchKernelGGL((jvp_kernel<kJvpThreadsSmall, true, false>), dim3(n), dim3(kJvpThreadsSmall), jvp_lds_bytes(32, true), st, ja);
     }
-    // Workgroup classes, both modes: one workgroup of 256 threads per component; matrix in LDS up to 192 rows, in HBM above
+    // Workgroup classes, every mode: one workgroup of 256 threads per component; matrix in LDS up to 192 rows, in HBM above
     a.scan_all = 0;
     for (int cls = lfr::KC_BLOCK; cls < lfr::KC_COUNT; ++cls) {
         a.desc_begin = b->class_begin[cls];
@@ -322,7 +342,9 @@ int lfr_batch_jvp(lfr_batch *b, const void *tan_disp1_device, const void *tan_di
         if (n <= 0) continue;
         const bool lds_matrix = cls != lfr::KC_GLOBAL;
         const size_t lds = jvp_lds_bytes(rows, lds_matrix);
-        if (!lds_matrix && gn) hipLaunchKernelGGL((jvp_kernel<kJvpThreads, false, true>), dim3(n), dim3(kJvpThreads), lds, st, ja);
+        if (fb && lds_matrix) hipLaunchKernelGGL((jvp_kernel<kJvpThreads, true, false, true>), dim3(n), dim3(kJvpThreads), lds, st, ja);
+        else if (fb) hipLaunchKernelGGL((jvp_kernel<kJvpThreads, false, false, true>), dim3(n), dim3(kJvpThreads), lds, st, ja);
+        else if (!lds_matrix && gn) hipLaunchKernelGGL((jvp_kernel<kJvpThreads, false, true>), dim3(n), dim3(kJvpThreads), lds, st, ja);
         else if (!lds_matrix) hipLaunchKernelGGL((jvp_kernel<kJvpThreads, false, false>), dim3(n), dim3(kJvpThreads), lds, st, ja);
         else if (gn) hipLaunchKernelGGL((jvp_kernel<kJvpThreads, true, true>), dim3(n), dim3(kJvpThreads), lds, st, ja);
         else hipLaunchKernelGGL((jvp_kernel<kJvpThreads, true, false>), dim3(n), dim3(kJvpThreads), lds, st, ja);

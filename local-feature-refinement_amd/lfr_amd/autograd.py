@@ -19,6 +19,8 @@ of the origin: flows that moved a little need fewer LM iterations.  reset_start(
 
 hessian="gauss_newton" (refine and Refiner) takes the implicit gradient with H = J^T J instead of the exact Hessian
 (LFR_BACKWARD_GAUSS_NEWTON): components whose exact Hessian is indefinite - zero gradient in the default mode - get one too.
+hessian="exact_or_gauss_newton" keeps the exact Hessian wherever its factorization succeeds and takes J^T J only for the components
+where it does not (LFR_BACKWARD_FALLBACK_GAUSS_NEWTON / LFR_JVP_FALLBACK_GAUSS_NEWTON; Batch.backward_status() tells which).
 
 One device.  First order in both modes: reverse (backward()) and forward (torch.autograd.forward_ad, Refiner.jvp) - the tangent J
 thetadot comes from lfr_batch_jvp with the H of `hessian`, so ubar . (J thetadot) = (J^T ubar) . thetadot holds between the two.  Neither
@@ -33,13 +35,18 @@ from . import capi
 from .synthetic import MatchArrays
 
 
-_HESSIANS = ("exact", "gauss_newton")
+_HESSIANS = ("exact", "gauss_newton", "exact_or_gauss_newton")
 
 
 def _check_hessian(who, hessian):
     if hessian not in _HESSIANS:
         raise ValueError("%s: hessian must be one of %s, got %r" % (who, ", ".join(map(repr, _HESSIANS)), hessian))
-    return hessian == "gauss_newton"
+    return hessian
+
+
+def _hessian_flags(hessian):
+    """the mode of _check_hessian as the keywords of Batch.backward / Batch.jvp"""
+    return {"gauss_newton": hessian == "gauss_newton", "gn_fallback": hessian == "exact_or_gauss_newton"}
 
 
 def _kept_rows(pair_img1, pair_img2, pair_off, image_names, banned):
@@ -142,7 +149,7 @@ class _Refine(torch.autograd.Function):
         s1, s2, ss, t1, t2, ts = ctx.n_in
         if grad_pos is None:
             return None, None, None, None
-        g1, g2, gs = b.backward(grad_pos, f64=False, gauss_newton=meta["gauss_newton"])
+        g1, g2, gs = b.backward(grad_pos, f64=False, **_hessian_flags(meta["hessian"]))
         rows = meta["kept_rows"]
         if rows is not None:        # back to the caller's rows (matches of banned pairs get 0)
             idx = torch.as_tensor(rows, device=g1.device)
@@ -166,7 +173,7 @@ class _Refine(torch.autograd.Function):
         idx = None if rows is None else torch.as_tensor(rows, device=pos_dev)
         with torch.cuda.device(pos_dev):
             t1, t2, ts, f64 = _tangent_rows("refine", (tan_disp1, tan_disp2, tan_sim), int(np.prod(ctx.n_in[2])), idx, pos_dev)
-            return b.jvp(t1, t2, ts, f64=f64, gauss_newton=meta["gauss_newton"]), None, None
+            return b.jvp(t1, t2, ts, f64=f64, **_hessian_flags(meta["hessian"])), None, None
 
 
 def refine(disp1, disp2, sim, *, image_names, pair_img1, pair_img2, pair_off, feat1, feat2, image_facts=None, banned=(),
@@ -183,8 +190,10 @@ def refine(disp1, disp2, sim, *, image_names, pair_img1, pair_img2, pair_off, fe
     return_covariance=True: a fourth value, the [n_nodes, 3] float64 device tensor of lfr_batch_covariance (C(di,di), C(di,dj),
     C(dj,dj) per node, the solver's unit squared; 0 = no covariance for this node).  It is detached: the covariance is not
     differentiated.
-    hessian: "exact" (the default) or "gauss_newton" - the H of the backward pass (lfr_batch_backward); anything else: ValueError."""
-    gauss_newton = _check_hessian("refine", hessian)
+    hessian: "exact" (the default), "gauss_newton" or "exact_or_gauss_newton" (exact where the exact Hessian is positive definite,
+    Gauss-Newton for the other components) - the H of the backward pass and of forward mode (lfr_batch_backward, lfr_batch_jvp);
+    anything else: ValueError."""
+    hessian = _check_hessian("refine", hessian)
     pair_img1 = np.ascontiguousarray(pair_img1, np.int32)
     pair_img2 = np.ascontiguousarray(pair_img2, np.int32)
     pair_off = np.ascontiguousarray(pair_off, np.int64)
@@ -196,7 +205,7 @@ def refine(disp1, disp2, sim, *, image_names, pair_img1, pair_img2, pair_off, fe
     meta = {"image_names": list(image_names), "facts": facts, "pair_img1": pair_img1, "pair_img2": pair_img2, "pair_off": pair_off,
             "feat1": feat1, "feat2": feat2,
             "banned": tuple(banned), "tukey_variant": tukey_variant, "return_covariance": bool(return_covariance),
-            "gauss_newton": gauss_newton,
+            "hessian": hessian,
             "kept_rows": _kept_rows(pair_img1, pair_img2, pair_off, list(image_names), tuple(banned))}
     pos, node_image, node_feature = _Refine.apply(disp1, disp2, sim, meta)
     if return_covariance:
@@ -225,7 +234,7 @@ class _RefinerStep(torch.autograd.Function):
             raise RuntimeError("Refiner: this forward (step %d) is stale - the shared batch holds only its latest solve (step %d); "
                                "run backward before the next forward" % (ctx.epoch, r._epoch))
         s1, s2, ss, t1, t2, ts = ctx.n_in
-        g1, g2, gs = r._batch.backward(grad_pos, f64=False, gauss_newton=r._gauss_newton)
+        g1, g2, gs = r._batch.backward(grad_pos, f64=False, **_hessian_flags(r._hessian))
         if r._idx is not None:      # back to the caller's rows (matches of banned pairs get 0)
             f1 = torch.zeros((r.n_rows, 18), dtype=g1.dtype, device=g1.device)
             f2 = torch.zeros_like(f1)
@@ -271,7 +280,7 @@ class Refiner:
 
     def __init__(self, disp1, disp2, sim, *, image_names, pair_img1, pair_img2, pair_off, feat1, feat2, image_facts=None, banned=(),
                  tukey_variant="ceres1", hessian="exact", warm_start=False):
-        self._gauss_newton = _check_hessian("Refiner", hessian)
+        self._hessian = _check_hessian("Refiner", hessian)
         self._warm_start = bool(warm_start)
         self._have_start = False        # the batch's positions are a forward's result
         pair_img1 = np.ascontiguousarray(pair_img1, np.int32)
@@ -367,7 +376,7 @@ class Refiner:
         with torch.cuda.device(self.device):
             t1, t2, ts, f64 = _tangent_rows("Refiner.jvp", (tan_disp1, tan_disp2, tan_sim), self.n_rows, self._idx, self.device)
             # (t1, t2, ts may be temporaries: they are read by work enqueued here, and torch reuses their memory in stream order)
-            return self._batch.jvp(t1, t2, ts, f64=f64, gauss_newton=self._gauss_newton).detach()
+            return self._batch.jvp(t1, t2, ts, f64=f64, **_hessian_flags(self._hessian)).detach()
 
     def evaluate(self, positions=None, **kw):
         """Batch.evaluate (lfr_batch_evaluate) on the shared batch: cost, dF/dx, raw residuals and loss weights at `positions`

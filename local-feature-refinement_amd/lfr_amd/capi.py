@@ -80,10 +80,12 @@ class JvpStats(C.Structure):
 
 BACKWARD_F64 = 1                # LFR_BACKWARD_F64
 BACKWARD_GAUSS_NEWTON = 2       # LFR_BACKWARD_GAUSS_NEWTON
-BACKWARD_OK, BACKWARD_NOT_USABLE, BACKWARD_INDEFINITE = 0, 1, 2      # lfr_batch_backward_status
+BACKWARD_FALLBACK_GAUSS_NEWTON = 32      # LFR_BACKWARD_FALLBACK_GAUSS_NEWTON
+BACKWARD_OK, BACKWARD_NOT_USABLE, BACKWARD_INDEFINITE, BACKWARD_FALLBACK = 0, 1, 2, 3      # lfr_batch_backward_status
 JVP_F64 = 1                     # LFR_JVP_F64
 JVP_GAUSS_NEWTON = 2            # LFR_JVP_GAUSS_NEWTON
-JVP_OK, JVP_NOT_USABLE, JVP_INDEFINITE = 0, 1, 2      # lfr_batch_jvp_status
+JVP_FALLBACK_GAUSS_NEWTON = 32  # LFR_JVP_FALLBACK_GAUSS_NEWTON
+JVP_OK, JVP_NOT_USABLE, JVP_INDEFINITE, JVP_FALLBACK = 0, 1, 2, 3      # lfr_batch_jvp_status
 COVARIANCE_F64 = 1              # LFR_COVARIANCE_F64
 COVARIANCE_OK, COVARIANCE_NOT_USABLE, COVARIANCE_SINGULAR = 0, 1, 2     # lfr_batch_covariance_status
 EVALUATE_F64 = 1                # LFR_EVALUATE_F64
@@ -747,13 +749,18 @@ class Batch:
             stream = torch.cuda.current_stream(dev).cuda_stream
         _check(lib().lfr_batch_set_inputs(self._h, p1, p2, ps, C.c_void_p(stream) if stream else None))
 
-    def backward(self, grad_positions, f64=False, stream=None, want_stats=False, gauss_newton=False):
+    def backward(self, grad_positions, f64=False, stream=None, want_stats=False, gauss_newton=False, gn_fallback=False):
         """Implicit gradient of the latest solve (lfr_batch_backward, include/lfr.h): grad_positions = dL/dx, [n_nodes, 2] float64 on
         the batch's device.  Returns (grad_disp1, grad_disp2, grad_sim) as device tensors in the graph's match layout ([n_matches, 18],
         [n_matches, 18], [n_matches]; float32, or float64 with f64=True), and the stats dict when want_stats (that waits).
         gauss_newton=True: H = J^T J instead of the exact Hessian (LFR_BACKWARD_GAUSS_NEWTON): positive definite where the exact one
-        is not, so those components get a gradient too; BACKWARD_INDEFINITE then means singular."""
+        is not, so those components get a gradient too; BACKWARD_INDEFINITE then means singular.
+        gn_fallback=True: the exact Hessian, and J^T J for the components where it is indefinite (LFR_BACKWARD_FALLBACK_GAUSS_NEWTON):
+        backward_status() reads BACKWARD_FALLBACK for those, BACKWARD_INDEFINITE where J^T J is singular too.  With gauss_newton=True:
+        ValueError."""
         import torch
+        if gauss_newton and gn_fallback:
+            raise ValueError("backward: gauss_newton and gn_fallback exclude each other")
         n = self.problem.graph.n_nodes
         m = self.problem.graph.n_edges // 2
         g = grad_positions.detach().to(dtype=torch.float64).contiguous()
@@ -767,7 +774,8 @@ class Batch:
             stream = torch.cuda.current_stream(g.device).cuda_stream
         st = BackwardStats()
         _check(lib().lfr_batch_backward(self._h, C.c_void_p(g.data_ptr() or 1), C.c_void_p(g1.data_ptr() or 1), C.c_void_p(g2.data_ptr() or 1), C.c_void_p(gs.data_ptr() or 1),
-                                        (BACKWARD_F64 if f64 else 0) | (BACKWARD_GAUSS_NEWTON if gauss_newton else 0),
+                                        (BACKWARD_F64 if f64 else 0) | (BACKWARD_GAUSS_NEWTON if gauss_newton else 0)
+                                        | (BACKWARD_FALLBACK_GAUSS_NEWTON if gn_fallback else 0),
                                         C.c_void_p(stream) if stream else None,
                                         C.byref(st) if want_stats else None))
         if want_stats:
@@ -775,7 +783,7 @@ class Batch:
         return g1, g2, gs
 
     def backward_status(self):
-        """Per component (order of component_info) of the latest backward: BACKWARD_OK / _NOT_USABLE / _INDEFINITE."""
+        """Per component (order of component_info) of the latest backward: BACKWARD_OK / _NOT_USABLE / _INDEFINITE / _FALLBACK."""
         n = lib().lfr_batch_component_info(self._h, None, None, None, None, None, None)
         out = np.zeros(max(n, 0), np.int32)
         rc = lib().lfr_batch_backward_status(self._h, _ptr(out))
@@ -783,14 +791,19 @@ class Batch:
             _check(rc)
         return out
 
-    def jvp(self, tan_disp1=None, tan_disp2=None, tan_sim=None, f64=False, gauss_newton=False, stream=None, want_stats=False):
+    def jvp(self, tan_disp1=None, tan_disp2=None, tan_sim=None, f64=False, gauss_newton=False, stream=None, want_stats=False,
+            gn_fallback=False):
         """Forward-mode sensitivity of the latest solve (lfr_batch_jvp, include/lfr.h): the tangent of the positions for the tangents
         of the flows and similarities - contiguous tensors on the batch's device in the graph's match layout, tan_disp1 / tan_disp2:
         [n_matches, 18] or [n_matches, 9, 2], given together or not at all (None = zero); tan_sim: [n_matches] (None = zero); float32,
         or float64 with f64=True.  Returns the [n_nodes, 2] float64 device tensor J thetadot (0 for roots, bound coordinates, unsolved
         nodes and the nodes of components that are not usable or indefinite), and the stats dict when want_stats (that waits).
-        gauss_newton=True: H = J^T J instead of the exact Hessian (LFR_JVP_GAUSS_NEWTON), the mode of backward(gauss_newton=True)."""
+        gauss_newton=True: H = J^T J instead of the exact Hessian (LFR_JVP_GAUSS_NEWTON), the mode of backward(gauss_newton=True).
+        gn_fallback=True: the exact Hessian, and J^T J where it is indefinite (LFR_JVP_FALLBACK_GAUSS_NEWTON, jvp_status() JVP_FALLBACK),
+        the mode of backward(gn_fallback=True).  With gauss_newton=True: ValueError."""
         import torch
+        if gauss_newton and gn_fallback:
+            raise ValueError("jvp: gauss_newton and gn_fallback exclude each other")
         n = self.problem.graph.n_nodes
         m = self.problem.graph.n_edges // 2
         dev = torch.device("cuda", self.device)
@@ -816,14 +829,15 @@ class Batch:
             stream = torch.cuda.current_stream(dev).cuda_stream
         st = JvpStats()
         _check(lib().lfr_batch_jvp(self._h, p1, p2, ps, C.c_void_p(out.data_ptr() or 1),
-                                   (JVP_F64 if f64 else 0) | (JVP_GAUSS_NEWTON if gauss_newton else 0),
+                                   (JVP_F64 if f64 else 0) | (JVP_GAUSS_NEWTON if gauss_newton else 0)
+                                   | (JVP_FALLBACK_GAUSS_NEWTON if gn_fallback else 0),
                                    C.c_void_p(stream) if stream else None, C.byref(st) if want_stats else None))
         if want_stats:
             return out, st.as_dict()
         return out
 
     def jvp_status(self):
-        """Per component (order of component_info) of the latest jvp: JVP_OK / _NOT_USABLE / _INDEFINITE."""
+        """Per component (order of component_info) of the latest jvp: JVP_OK / _NOT_USABLE / _INDEFINITE / _FALLBACK."""
         n = lib().lfr_batch_component_info(self._h, None, None, None, None, None, None)
         out = np.zeros(max(n, 0), np.int32)
         rc = lib().lfr_batch_jvp_status(self._h, _ptr(out))
