@@ -191,6 +191,13 @@ __device__ __forceinline__ double packed_step(const double *A, const int row, co
     // fetched back per step (two v_readlane and an s_andn2 in front of every branch) where one s_cmp against the SGPR does it.
     int n_steps = nv2_max;
     if constexpr (LPR == 1 && NV <= 16) asm volatile("" : "+s"(n_steps));
+    // The same for the lane's row in the tests `j == row` of the build and `row == K` of the steps: row is a lane constant, and left
+    // visible the NV compares are hoisted out of the solve's loop as NV 64-bit masks - a third of the kernel's SGPRs for the whole
+    // solve, about ten of them spilled and fetched back with two v_readlane at each of their two uses per LM step, and the SGPRs they
+    // hold are what the rest of the kernel spills around.  Opaque per LM step, each test is one v_cmp against an inline constant at its
+    // use.  (The addresses of the build keep the visible row: they are hoisted as sixteen VGPRs, which is what they should be.)
+    int row_t = row;
+    if constexpr (LPR == 1 && NV <= 16) asm volatile("" : "+v"(row_t));
     // build the lane's columns (LPR*c + part of the own row) and eliminate, in the instantiation
     // sized for the largest system of the wave
     auto lm_solve = [&](auto cl_tag) {
@@ -207,12 +214,12 @@ __device__ __forceinline__ double packed_step(const double *A, const int row, co
             } else {
                 // rows >= nv2 of A are zero (prologue), so columns beyond the system and padded rows read 0 without a mask
                 const double v = (j <= row ? A[row * LD + j] : A[j * LD + row]);
-                h[c] = (j == row) ? v + dd_lane : v;
+                h[c] = (j == row_t) ? v + dd_lane : v;
             }
         }
         mark();
         ISA_MARK("gauss_jordan");
-        GaussJordan<NV, LPR, 0, CL>::run(h, rhs, piv_own, minpiv, row, part, n_steps);
+        GaussJordan<NV, LPR, 0, CL>::run(h, rhs, piv_own, minpiv, row_t, part, n_steps);
     };
     const int c_hi = (n_steps + LPR - 1) / LPR;          // wave-uniform
 #ifdef LFR_ABL_GJ              // matrix build + elimination twice (the first result discarded through an opaque reset)
@@ -484,8 +491,11 @@ __device__ __forceinline__ void solve_group_body(const KernelArgs &a, const int 
                 }
                 if (ra >= 0 && rb >= 0) {
                     const int r1 = rb + q, k1 = ra, r2 = rb + 1 - q, k2 = ra + 1;
-                    atomicAdd(&A[rb > ra ? r1 * LD + k1 : k1 * LD + r1], c1);
-                    atomicAdd(&A[rb > ra ? r2 * LD + k2 : k2 * LD + r2], c2);
+                    // (row and column selected, then one index: as `below ? r * LD + k : k * LD + r` the two sides became a divergent
+                    // if / else with its exec bracket, 5 SALU per slot)
+                    const bool below = rb > ra;
+                    atomicAdd(&A[(below ? r1 : k1) * LD + (below ? k1 : r1)], c1);
+                    atomicAdd(&A[(below ? r2 : k2) * LD + (below ? k2 : r2)], c2);
                 }
             }
         } else {

@@ -20,7 +20,7 @@ import csv, collections, glob
 for f in sorted(glob.glob("$O/p*/*counter_collection.csv")):
     agg = collections.defaultdict(lambda: collections.defaultdict(list))
     for row in csv.DictReader(open(f)):
-        agg[row["Kernel_Name"][:48]][row["Counter_Name"]].append(float(row["Counter_Value"]))
+        agg[row["Kernel_Name"][:64]][row["Counter_Name"]].append(float(row["Counter_Value"]))
     for k, d in agg.items():
         if "solve_packed" not in k: continue
         print(k)
