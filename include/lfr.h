@@ -679,6 +679,66 @@ typedef struct lfr_evaluate_stats {
 int lfr_batch_evaluate(lfr_batch *b, const double *positions_device, double *cost_device, double *grad_positions_device,
                        void *residuals_device, void *weights_device, int flags, void *hip_stream, lfr_evaluate_stats *stats);
 
+/* ---------------------------------------------------------------------------------------------
+ * The vector-Jacobian product of lfr_batch_evaluate's differentiable outputs: the objective differentiated in its inputs.
+ *
+ * Contract.  With bars cbar_c (per component), rbar_e (per raw residual) and wbar_e (per weight rho'_e), the call returns the
+ * gradient of  sum_c cbar_c F_c + sum_e rbar_e . r_e + sum_e wbar_e rho'_e  with respect to the positions, the flows and the
+ * similarities, at the given positions, with the records as they are NOW - the EXPLICIT partials; the dependence of the positions
+ * on the flows is lfr_batch_backward's.  Per kept directed edge e of component c everything follows from one 2-vector
+ *     q_e = cbar_c w_e rho'_e r_e  +  rbar_e  +  wbar_e 2 rho''_e r_e
+ * where r, rho' and P = I + df/dx_src are exactly lfr_batch_evaluate's (the derivative of the interpolant zeroed outside [-0.5, 0.5]
+ * and kept at exactly +-0.5; nothing is clamped to the +-1 box) and rho'' is lfr_batch_backward's: Cauchy -1 / (b (1 + s/b)^2), Tukey
+ * -6 k / a^4 (1 - s/a^2) inside and 0 where saturated.
+ *   - positions_device: as for lfr_batch_evaluate (NULL = the batch's own; NULL before the first solve: LFR_ERR_ARG; NULL between an
+ *     lfr_batch_set_inputs and the next solve is allowed);
+ *   - cost_bar_device: one double per component in the order of lfr_batch_component_info; residuals_bar_device (n_matches x 4) and
+ *     weights_bar_device (n_matches x 2) in lfr_batch_evaluate's match layout.  Any bar may be NULL = zero; all three NULL:
+ *     LFR_ERR_ARG.  The bars of a direction that is no residual block of this shard (a dropped edge, two constant ends, outside the
+ *     shard) are not read;
+ *   - grad_positions_device (may be NULL): 2 * n_nodes doubles, the whole array is overwritten.  Per edge the destination adds +q_e,
+ *     the source -P_e^T q_e; only variable nodes receive a gradient: constants, unsolved nodes and nodes outside the shard get 0;
+ *   - grad_disp1_device / grad_disp2_device (n_matches x 18, both or neither; one alone: LFR_ERR_ARG): the flow gradient of an edge,
+ *     g[6 i + 2 j + k] = -Lr_i(x_src) Lc_j(x_src) q_k with the basis values of the clamped argument, in row m of grad_disp2 for the
+ *     edge node1->node2 of match m and of grad_disp1 for node2->node1 - the layout of lfr_batch_backward's gradients.  A saturated
+ *     Tukey edge gets nothing from cbar and wbar, but its rbar passes;
+ *   - grad_sim_device (n_matches, may be NULL): the sum over the match's two directions of cbar_c 1/2 rho_e(s_e), node1->node2 first
+ *     (residuals and weights do not depend on the similarity);
+ *   - directions that are no residual block of this shard leave 0 in every per-match output; whole arrays are overwritten;
+ *   - LFR_EVALUATE_F64: every per-match array - bars and gradients - is double; otherwise float32, each float32 output the fp64 value
+ *     rounded once.  cost_bar and grad_positions are always double.  Any other flag bit: LFR_ERR_ARG.  All four outputs NULL:
+ *     LFR_ERR_ARG.  Every argument error is raised before an output is touched;
+ *   - a batch over one rank's connected components (lfr_problem_cc_sharded = 1): LFR_ERR_UNSUPPORTED as soon as a per-match bar or a
+ *     per-match output is given; cost_bar -> grad_positions alone is served.  There is no row limit: nothing here needs a matrix;
+ *   - a bar, flow or similarity that is not finite makes the outputs of its own component not finite and changes no other component
+ *     by a bit, one in the same wavefront included; stats->n_nonfinite counts the components with a q that is not finite;
+ *   - outputs are bitwise repeatable from call to call and identical for host- and device-assembled batches.  No fp64 value goes
+ *     through a global-memory atomic; every match row is written by exactly one record; the two directions' similarity terms go
+ *     through a per-direction scratch and one combine pass in a fixed order;
+ *   - runs on `hip_stream`, asynchronous unless stats != NULL.  Waits BY EVENT for the latest solve and the latest
+ *     lfr_batch_set_inputs; lfr_batch_set_inputs in turn waits for the latest lfr_batch_evaluate_vjp.  A device-assembled batch whose
+ *     records are not yet written materialises them first, and the first call with a per-match argument builds the record -> edge
+ *     map, both as lfr_batch_evaluate does.  Two calls in flight at once on different streams share the similarity scratch: the
+ *     caller orders them.
+ * Kernels (lfr_evaluate.hip): lfr_batch_evaluate's two launches run backwards.  Packed classes: each record lane forms q, stores its
+ * own flow row and its direction's similarity term and accumulates the two position sides in the group's LDS in the evaluate's
+ * order; no barriers.  Workgroup classes: the thread of a node forms q on its out-edges (flow row, similarity term, source side) and
+ * again, from that record's bars, on its in-edges (destination side); constants walk their out-edges only. */
+typedef struct lfr_evaluate_vjp_stats {
+    int64_t n_components;          /* components swept (every solved-program component of the shard, whatever its termination) */
+    int64_t n_nonfinite;           /* components with a q that is not finite */
+    double kernel_ms;              /* HIP-event time of the call's kernels (and its clearing of the outputs) */
+} lfr_evaluate_vjp_stats;
+
+int lfr_batch_evaluate_vjp(lfr_batch *b, const double *positions_device,
+                           const double *cost_bar_device,        /* per component, order of lfr_batch_component_info */
+                           const void *residuals_bar_device,     /* n_matches x 4 */
+                           const void *weights_bar_device,       /* n_matches x 2 */
+                           double *grad_positions_device,        /* 2 * n_nodes */
+                           void *grad_disp1_device, void *grad_disp2_device,   /* n_matches x 18 */
+                           void *grad_sim_device,                /* n_matches */
+                           int flags, void *hip_stream, lfr_evaluate_vjp_stats *stats);
+
 /* Unit-level probe of the device arithmetic (cost.cc:13-48,78-90 + the loss / corrector of solve.cc:111,120): for
  * each of n edges (flows n x 18 float32, sim, kind 0 = intra-track/Cauchy 1 = inter-track/Tukey, x1 = source and
  * x2 = destination position) the kernels' eval_edge on the GPU: out8[8i..] = 0.5*rho, corrected residual r0 r1,

@@ -7,7 +7,8 @@
 //   lfr_backward.hip     implicit-gradient backward pass (lfr_batch_backward): kernels, its own carvings, the launches
 //   lfr_covariance.hip   per-keypoint covariance (lfr_batch_covariance): kernels, the launches
 //   lfr_inputs.hip       new flows / similarities into a live batch (lfr_batch_set_inputs) and the record -> directed-edge map
-//   lfr_evaluate.hip     cost, gradient, residuals and loss weights at given positions (lfr_batch_evaluate): kernels, the launches
+//   lfr_evaluate.hip     cost, gradient, residuals and loss weights at given positions (lfr_batch_evaluate) and their vector-Jacobian
+//                        product (lfr_batch_evaluate_vjp): kernels, the launches
 //   lfr_jvp.hip          forward-mode sensitivity of the positions (lfr_batch_jvp): kernels, the launches
 #pragma once
 
@@ -257,6 +258,7 @@ struct lfr_batch {
     lfr::PassState *bwd = nullptr, *cov = nullptr;       // lfr_backward.hip / lfr_covariance.hip: set up on the first call
     lfr::PassState *eval = nullptr;                      // lfr_evaluate.hip: set up on the first lfr_batch_evaluate (its own entry: needs no solve)
     lfr::PassState *jvp = nullptr;                       // lfr_jvp.hip: set up on the first lfr_batch_jvp
+    lfr::PassState *evjp = nullptr;                      // lfr_evaluate.hip: set up on the first lfr_batch_evaluate_vjp (needs no solve either)
 
     lfr_batch() { for (auto &e : ev_ring) e = nullptr; }
     ~lfr_batch() {
@@ -264,6 +266,7 @@ struct lfr_batch {
         lfr::pass_free(cov);
         lfr::pass_free(eval);
         lfr::pass_free(jvp);
+        lfr::pass_free(evjp);
         if (ctx) {
             (void)hipSetDevice(device);
             if (n_solves > 0) (void)hipStreamSynchronize(last_stream);      // nothing may still use the slab

@@ -259,6 +259,71 @@ class _RefinerStep(torch.autograd.Function):
         return r.jvp(tan_disp1, tan_disp2, tan_sim)
 
 
+class _Objective(torch.autograd.Function):
+    """Refiner.objective: Batch.evaluate forward, Batch.evaluate_vjp backward (the explicit partials of the cost, the residuals and the
+    weights with respect to the positions, the flows and the similarities)."""
+
+    @staticmethod
+    def forward(ctx, positions, disp1, disp2, sim, refiner, want_res, want_w):
+        r = refiner
+        ctx.refiner, ctx.epoch = r, r._epoch
+        ctx.set_materialize_grads(False)
+        ctx.n_in = (positions.shape, positions.dtype, disp1.shape, disp1.dtype, disp2.shape, disp2.dtype,
+                    None if sim is None else (sim.shape, sim.dtype, sim.device))
+        with torch.cuda.device(r.device):
+            pos = positions.detach().to(device=r.device, dtype=torch.float64).reshape(-1, 2).contiguous()
+            out = r._batch.evaluate(pos, cost=True, grad=False, residuals=want_res, weights=want_w, f64=True)
+            ctx.pos = pos
+            res = [out["cost"]]
+            for name, fill in (("residuals", 0.0), ("weights", -1.0)):      # the caller's rows, as Refiner.evaluate gives them
+                if name in out:
+                    t = out[name]
+                    if r._idx is not None:
+                        full = torch.full((r.n_rows,) + tuple(t.shape[1:]), fill, dtype=t.dtype, device=t.device)
+                        full[r._idx] = t
+                        t = full
+                    res.append(t)
+        ctx.names = ("cost",) + (("residuals",) if want_res else ()) + (("weights",) if want_w else ())
+        return tuple(res)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, *bars):
+        r = ctx.refiner
+        bars = dict(zip(ctx.names, bars))
+        if all(b is None for b in bars.values()):
+            return (None,) * 7
+        if r._batch is None:
+            raise RuntimeError("Refiner: backward after close()")
+        if ctx.epoch != r._epoch:
+            raise RuntimeError("Refiner: this forward (step %d) is stale - the shared batch holds only its latest solve (step %d); "
+                               "run backward before the next forward" % (ctx.epoch, r._epoch))
+        sp, tp, s1, t1, s2, t2, ss = ctx.n_in
+        need = ctx.needs_input_grad
+        want = (("positions",) if need[0] else ()) + (("disp",) if need[1] or need[2] else ()) + (("sim",) if ss is not None and need[3] else ())
+        if not want:
+            return (None,) * 7
+        with torch.cuda.device(r.device):
+            def rows(t):       # a bar in the caller's rows -> the graph's rows, float64 (the bars of banned pairs are not read)
+                if t is None:
+                    return None
+                t = t.detach().to(device=r.device, dtype=torch.float64)
+                return (t if r._idx is None else t.index_select(0, r._idx)).contiguous()
+            cbar = bars["cost"]
+            g = r._batch.evaluate_vjp(ctx.pos, cost_bar=None if cbar is None else cbar.detach().to(device=r.device, dtype=torch.float64).contiguous(),
+                                      residuals_bar=rows(bars.get("residuals")), weights_bar=rows(bars.get("weights")), want=want, f64=True)
+            if r._idx is not None:      # back to the caller's rows (matches of banned pairs get 0)
+                for name in ("disp1", "disp2", "sim"):
+                    if name in g:
+                        full = torch.zeros((r.n_rows,) + tuple(g[name].shape[1:]), dtype=g[name].dtype, device=r.device)
+                        full[r._idx] = g[name]
+                        g[name] = full
+        return (g["positions"].reshape(sp).to(tp) if need[0] else None,
+                g["disp1"].reshape(s1).to(t1) if need[1] else None,
+                g["disp2"].reshape(s2).to(t2) if need[2] else None,
+                g["sim"].reshape(ss[0]).to(device=ss[2], dtype=ss[1]) if ss is not None and need[3] else None, None, None, None)
+
+
 class Refiner:
     """refine() for a loop over the same scenes: the graph stage (tracks, roots, components) and the batch assembly run once, in the
     constructor, from the values given there; every call gives the live batch new flows - and similarities, if passed - and solves
@@ -275,6 +340,7 @@ class Refiner:
     hessian: as for refine().  node_image, node_feature, n_nodes: as refine() returns them.  covariance(f64=True): lfr_batch_covariance of the latest solve.
     match_covariance(f64=True): lfr_batch_covariance_matches of the latest solve (cross blocks and relative covariance per match).
     evaluate(positions=None, **kw): lfr_batch_evaluate (cost, dF/dx, residuals, loss weights), detached.
+    objective(positions, disp1, disp2, sim=None): the same cost, residuals and weights, differentiable (lfr_batch_evaluate_vjp).
     jvp(tan_disp1, tan_disp2, tan_sim=None): lfr_batch_jvp of the latest forward (the tangent of the positions), detached;
     torch.autograd.forward_ad through r(...) calls it."""
 
@@ -305,6 +371,7 @@ class Refiner:
         self.n_nodes = self._graph.n_nodes
         self.node_image, self.node_feature = self._graph.nodes()
         self._epoch = 0
+        self._latest = None
 
     def _forward(self, disp1, disp2, sim):
         if self._batch is None:
@@ -331,7 +398,9 @@ class Refiner:
         return self._epoch
 
     def __call__(self, disp1, disp2, sim=None):
-        return _RefinerStep.apply(disp1, disp2, sim, self)
+        pos = _RefinerStep.apply(disp1, disp2, sim, self)
+        self._latest = (disp1, disp2, sim)          # objective() checks that it is given these very tensors
+        return pos
 
     def reset_start(self):
         """warm_start=True: the next forward starts at the origin, like the first one (the ones after it are warm again)."""
@@ -382,7 +451,8 @@ class Refiner:
         """Batch.evaluate (lfr_batch_evaluate) on the shared batch: cost, dF/dx, raw residuals and loss weights at `positions`
         ([n_nodes, 2], None = the latest forward's), with the records of the latest forward - or of the constructor before the first.
         "residuals" and "weights" come back in the caller's rows: the rows of banned pairs read residual 0 and weight -1.  Every
-        tensor is detached: F is not differentiated here, neither with respect to the positions (that is "grad") nor to the flows."""
+        tensor is detached: F is not differentiated here, neither with respect to the positions (that is "grad") nor to the flows -
+        objective() is the differentiable form."""
         if self._batch is None:
             raise RuntimeError("Refiner: evaluate after close()")
         with torch.cuda.device(self.device):
@@ -396,7 +466,31 @@ class Refiner:
                         out[name] = full
         return {k: (v.detach() if isinstance(v, torch.Tensor) else v) for k, v in out.items()}
 
+    def objective(self, positions, disp1, disp2, sim=None, *, residuals=False, weights=False):
+        """The objective of the latest forward as a differentiable function of (positions, disp1, disp2, sim): `cost` [n_components]
+        float64 in the order of Batch.component_info - and, when asked for, `residuals` [rows, 2, 2] and `weights` [rows, 2] (float64,
+        the caller's rows; banned pairs read residual 0 and weight -1) - returned as a dict.  The forward is Batch.evaluate at
+        positions.detach(), the backward Batch.evaluate_vjp (lfr_batch_evaluate_vjp): the EXPLICIT partials.  With `positions` the
+        output of the latest r(...), autograd adds them to J^T dL/dx from lfr_batch_backward: the gradient that reaches the flows is
+        the total derivative.  The records are those of the latest forward, so disp1, disp2 and sim must be the very tensors the
+        latest r(...) received (anything else: ValueError; a missing sim is None in both), and a backward after a later forward
+        raises RuntimeError.  First order only."""
+        if self._batch is None:
+            raise RuntimeError("Refiner: objective after close()")
+        if self._epoch == 0 or self._latest is None:
+            raise RuntimeError("Refiner: objective before the first forward")
+        for name, given, seen in zip(("disp1", "disp2", "sim"), (disp1, disp2, sim), self._latest):
+            if given is not seen:
+                raise ValueError("Refiner.objective: %s is not the tensor the latest forward received - the batch holds that forward's "
+                                 "records, and the gradient would go to a tensor they were not made from" % name)
+        if not isinstance(positions, torch.Tensor) or positions.numel() != 2 * self.n_nodes:
+            raise ValueError("Refiner.objective: positions must be a [%d, 2] tensor" % self.n_nodes)
+        out = _Objective.apply(positions, disp1, disp2, sim, self, bool(residuals), bool(weights))
+        names = ("cost",) + (("residuals",) if residuals else ()) + (("weights",) if weights else ())
+        return dict(zip(names, out))
+
     def close(self):
+        self._latest = None
         for name in ("_batch", "_problem", "_graph"):
             h = getattr(self, name, None)
             if h is not None:

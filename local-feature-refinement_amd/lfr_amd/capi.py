@@ -71,6 +71,13 @@ class EvaluateStats(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+class EvaluateVjpStats(C.Structure):
+    _fields_ = [(n, C.c_int64) for n in ("n_components", "n_nonfinite")] + [("kernel_ms", C.c_double)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
 class JvpStats(C.Structure):
     _fields_ = [(n, C.c_int64) for n in ("n_differentiated", "n_not_usable", "n_indefinite", "n_bound_coordinates")] + [("kernel_ms", C.c_double)]
 
@@ -161,6 +168,7 @@ def lib():
         "lfr_batch_covariance_matches": (C.c_int, [vp, vp, vp, vp, C.c_int, vp, C.POINTER(CovarianceStats)]),
         "lfr_batch_covariance_status": (i64, [vp, vp]),
         "lfr_batch_evaluate": (C.c_int, [vp, vp, vp, vp, vp, vp, C.c_int, vp, C.POINTER(EvaluateStats)]),
+        "lfr_batch_evaluate_vjp": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_int, vp, C.POINTER(EvaluateVjpStats)]),
         "lfr_keypoint_covariances": (C.c_int, [vp, vp, C.c_char_p, vp, i64]),
         "lfr_debug_invert_spd": (C.c_int, [C.c_int, C.c_int, i64, vp, vp, vp, vp]),
         "lfr_batch_spin_timeouts": (i64, [vp]),
@@ -196,7 +204,7 @@ EXPORTS = ["lfr_version", "lfr_last_error", "lfr_graph_from_files", "lfr_graph_f
            "lfr_graph_num_images", "lfr_graph_get_nodes", "lfr_graph_image_name", "lfr_graph_image_fact",
            "lfr_write_matching_file", "lfr_problem_build", "lfr_problem_build_labels", "lfr_problem_build_hip", "lfr_problem_free", "lfr_problem_get_stats",
            "lfr_problem_get_labels", "lfr_problem_shard_components", "lfr_hip_warmup", "lfr_batch_create", "lfr_batch_free", "lfr_batch_solve", "lfr_batch_solve_from",
-           "lfr_batch_download", "lfr_batch_timing", "lfr_batch_spin_timeouts", "lfr_batch_team_runs", "lfr_batch_team_fallbacks", "lfr_debug_occupy", "lfr_batch_tree_stats", "lfr_batch_component_info", "lfr_batch_positions_to_device", "lfr_batch_backward", "lfr_batch_backward_status", "lfr_batch_jvp", "lfr_batch_jvp_status", "lfr_batch_set_inputs", "lfr_batch_covariance", "lfr_batch_covariance_matches", "lfr_batch_covariance_status", "lfr_batch_evaluate", "lfr_keypoint_covariances", "lfr_debug_invert_spd", "lfr_solve_hip", "lfr_solve_hip_multi", "lfr_solve_graph_hip_multi", "lfr_write_solution", "lfr_apply_displacements"]
+           "lfr_batch_download", "lfr_batch_timing", "lfr_batch_spin_timeouts", "lfr_batch_team_runs", "lfr_batch_team_fallbacks", "lfr_debug_occupy", "lfr_batch_tree_stats", "lfr_batch_component_info", "lfr_batch_positions_to_device", "lfr_batch_backward", "lfr_batch_backward_status", "lfr_batch_jvp", "lfr_batch_jvp_status", "lfr_batch_set_inputs", "lfr_batch_covariance", "lfr_batch_covariance_matches", "lfr_batch_covariance_status", "lfr_batch_evaluate", "lfr_batch_evaluate_vjp", "lfr_keypoint_covariances", "lfr_debug_invert_spd", "lfr_solve_hip", "lfr_solve_hip_multi", "lfr_solve_graph_hip_multi", "lfr_write_solution", "lfr_apply_displacements"]
 
 
 def _check(rc):
@@ -941,6 +949,67 @@ class Batch:
         _check(lib().lfr_batch_evaluate(self._h, None if pos is None else C.c_void_p(pos.data_ptr() or 1), ptr("cost"), ptr("grad"),
                                         ptr("residuals"), ptr("weights"), EVALUATE_F64 if f64 else 0,
                                         C.c_void_p(stream) if stream else None, C.byref(st) if want_stats else None))
+        if want_stats:
+            out["stats"] = st.as_dict()
+        return out
+
+    def evaluate_vjp(self, positions=None, *, cost_bar=None, residuals_bar=None, weights_bar=None, want=("positions", "disp", "sim"),
+                     f64=True, stream=None, want_stats=False):
+        """Vector-Jacobian product of evaluate()'s differentiable outputs (lfr_batch_evaluate_vjp, include/lfr.h): the gradient of
+        sum cost_bar * cost + sum residuals_bar * residuals + sum weights_bar * weights with respect to the positions, the flows and
+        the similarities, at `positions` ([n_nodes, 2] float64 on the batch's device, None = the batch's own) with the records as they
+        are now - the explicit partials, to be added to backward()'s implicit ones.  cost_bar: [n_components] float64 in the order of
+        component_info; residuals_bar: [n_matches, 2, 2]; weights_bar: [n_matches, 2] - float64, or float32 with f64=False; None =
+        zero, at least one is needed.  Returns a dict of device tensors, one per name in `want`: "positions" [n_nodes, 2] float64 (0
+        for nodes that are not variable), "disp1" / "disp2" [n_matches, 18] for "disp" and "sim" [n_matches], float64 or float32
+        with f64=False (0 for directions that are no residual block of this batch); with want_stats also "stats" (that waits)."""
+        import torch
+        want = tuple(want)
+        if not want or any(w not in ("positions", "disp", "sim") for w in want):
+            raise ValueError("evaluate_vjp: want takes \"positions\", \"disp\", \"sim\" (at least one), got %r" % (want,))
+        n = self.problem.graph.n_nodes
+        m = self.problem.graph.n_edges // 2
+        dev = torch.device("cuda", self.device)
+        dt = torch.float64 if f64 else torch.float32
+
+        def ptr(t, name, shapes, dtype):
+            if t is None:
+                return None
+            if not isinstance(t, torch.Tensor):
+                raise ValueError("evaluate_vjp: %s must be a torch tensor" % name)
+            if not t.is_cuda or t.device != dev:
+                raise ValueError("evaluate_vjp: %s is on %s, the batch on %s" % (name, t.device, dev))
+            if t.dtype != dtype:
+                raise ValueError("evaluate_vjp: %s is %s, need %s" % (name, t.dtype, dtype))
+            if tuple(t.shape) not in shapes or not t.is_contiguous():
+                raise ValueError("evaluate_vjp: %s has shape %s, need a contiguous %s" % (name, tuple(t.shape), " or ".join(map(str, shapes))))
+            return C.c_void_p(t.data_ptr() or 1)          # (no matches: an empty tensor has no address, and nothing is read)
+
+        nc = lib().lfr_batch_component_info(self._h, None, None, None, None, None, None)
+        if nc < 0:
+            _check(int(nc))
+        pp = ptr(positions, "positions", ((n, 2), (2 * n,)), torch.float64)
+        pc = ptr(cost_bar, "cost_bar", ((nc,),), torch.float64)
+        pr = ptr(residuals_bar, "residuals_bar", ((m, 2, 2), (m, 4)), dt)
+        pw = ptr(weights_bar, "weights_bar", ((m, 2),), dt)
+        out = {}
+        if "positions" in want:
+            out["positions"] = torch.empty((n, 2), dtype=torch.float64, device=dev)
+        if "disp" in want:
+            out["disp1"] = torch.empty((m, 18), dtype=dt, device=dev)
+            out["disp2"] = torch.empty((m, 18), dtype=dt, device=dev)
+        if "sim" in want:
+            out["sim"] = torch.empty((m,), dtype=dt, device=dev)
+        if stream is None:
+            stream = torch.cuda.current_stream(dev).cuda_stream
+
+        def optr(name):
+            return C.c_void_p(out[name].data_ptr() or 1) if name in out else None
+
+        st = EvaluateVjpStats()
+        _check(lib().lfr_batch_evaluate_vjp(self._h, pp, pc, pr, pw, optr("positions"), optr("disp1"), optr("disp2"), optr("sim"),
+                                            EVALUATE_F64 if f64 else 0, C.c_void_p(stream) if stream else None,
+                                            C.byref(st) if want_stats else None))
         if want_stats:
             out["stats"] = st.as_dict()
         return out
