@@ -1,15 +1,20 @@
-"""backward_ref's and covariance_ref's references for ONE large sparse component (a ring of thousands of nodes), where their dense
-factorizations, inverses and eigenvalues take minutes: the same quantities from a banded Cholesky after a reverse Cuthill-McKee
-ordering (a ring without its root is a path: block tridiagonal).  Test infrastructure; tests/test_banded_ref.py pins every function
-here to its dense counterpart on a ring small enough for both.
+"""backward_ref's, jvp_ref's and covariance_ref's references for ONE large sparse component (a ring of thousands of nodes), where
+their dense factorizations, inverses and eigenvalues take minutes: the same quantities from a banded Cholesky after a reverse
+Cuthill-McKee ordering (a ring without its root is a path: block tridiagonal).  Test infrastructure; tests/test_banded_ref.py pins
+every function here to its dense counterpart on a ring small enough for both.
 
   backward(cp, x, ubar)        backward_ref.Component.backward with H^-1 ubar from the banded Cholesky of the exact Hessian
+  jvp(cp, x, flow_dot, sim_dot, gauss_newton=False)
+                               jvp_ref.jvp: its right-hand side (jvp_ref.rhs), H^-1 b from the longdouble banded Cholesky of
+                               reduced_hessian(cp, x, gauss_newton), the matrix of either mode with the identity on bound rows
   normal_matrix(problem, x)    covariance_ref.normal_matrix as a sparse matrix
   Inverse(A)                   what test_gpu_covariance's comparison needs of A^-1: columns in np.longdouble (a longdouble banded
                                Cholesky, accepted by covariance_ref.inverse_refined's own residual criterion) and
                                covariance_ref.component_bound's terms - the float64 inverse is the banded Cholesky's instead of
                                numpy.linalg.inv's (both backward stable), kappa_inf from that full inverse, kappa_2 from the
                                extreme eigenvalues of the band matrix."""
+import functools
+
 import numpy as np
 import scipy.linalg as sla
 import scipy.sparse as sp
@@ -17,8 +22,10 @@ import torch
 from scipy.sparse.csgraph import reverse_cuthill_mckee
 from torch.func import hessian, vmap
 
+import backward_gn_ref as GN
 import backward_ref as BR
 import covariance_ref as CR
+import jvp_ref as JR
 import lfr_ref as R
 import linsolve_ref as LS
 
@@ -41,10 +48,13 @@ def band(S):
     return perm, ab, b
 
 
-def sparse_hessian(cp, x):
-    """backward_ref.Component.hessian as a sparse matrix"""
-    f = lambda z, fl, w, k: BR.edge_cost(z, fl, w, k, cp.variant)
-    he = vmap(hessian(f))(cp._z(x), cp.flow, cp.sim, cp.kind).numpy()            # [E, 4, 4]
+def sparse_hessian(cp, x, gauss_newton=False):
+    """backward_ref.Component.hessian (gauss_newton: backward_gn_ref.Component.hessian) as a sparse matrix"""
+    if gauss_newton:
+        he = GN.Component.of(cp).edge_blocks(x)
+    else:
+        f = lambda z, fl, w, k: BR.edge_cost(z, fl, w, k, cp.variant)
+        he = vmap(hessian(f))(cp._z(x), cp.flow, cp.sim, cp.kind).numpy()        # [E, 4, 4]
     n = 2 * cp.nv
     idx = np.stack([2 * cp.src, 2 * cp.src + 1, 2 * cp.dst, 2 * cp.dst + 1], 1)
     idx[idx < 0] += n + 2                                                        # constant node -> the two spare rows
@@ -53,12 +63,36 @@ def sparse_hessian(cp, x):
     return sp.coo_matrix((he.reshape(-1), (rows, cols)), shape=(n + 2, n + 2)).tocsr()[:n, :n]
 
 
+def reduced_hessian(cp, x, gauss_newton=False):
+    """sparse_hessian with the rows and columns of the bound coordinates replaced by the identity's: the matrix both passes factor"""
+    x = np.asarray(x, np.float64).reshape(-1)
+    fr = cp.free(x)
+    keep = sp.diags(fr.astype(np.float64))
+    return (keep @ sparse_hessian(cp, x, gauss_newton) @ keep + sp.diags((~fr).astype(np.float64))).tocsr()
+
+
+def jvp(cp, x, flow_dot, sim_dot, gauss_newton=False):
+    """(xdot [2 nv], status) as jvp_ref.jvp: the right-hand side is jvp_ref.rhs, the solve the longdouble banded Cholesky of
+    reduced_hessian; status 2 (zeros) where that matrix is not positive definite.  Bound coordinates get an exact 0."""
+    x = np.asarray(x, np.float64).reshape(-1)
+    fr = cp.free(x)
+    b = np.where(fr, JR.rhs(cp, x, flow_dot, sim_dot), 0.0)
+    perm, ab, _ = band(reduced_hessian(cp, x, gauss_newton))
+    try:
+        L = _cholesky_ld(ab)
+    except np.linalg.LinAlgError:
+        return np.zeros(len(x)), 2
+    xdot = np.zeros(len(x))
+    xdot[perm] = _solve_ld(L, b[perm][:, None])[:, 0].astype(np.float64)
+    xdot[~fr] = 0.0
+    return xdot, 0
+
+
 def backward(cp, x, ubar):
     """(grad_flow [E, 18], grad_sim [E], status) as backward_ref.Component.backward: status 2 (zeros) where H is not positive definite"""
     x = np.asarray(x, np.float64).reshape(-1)
     fr = cp.free(x)
-    keep = sp.diags(fr.astype(np.float64))
-    H = keep @ sparse_hessian(cp, x) @ keep + sp.diags((~fr).astype(np.float64))
+    H = reduced_hessian(cp, x)
     rhs = np.where(fr, np.asarray(ubar, np.float64).reshape(-1), 0.0)
     E = len(cp.src)
     perm, ab, _ = band(H)
@@ -149,9 +183,15 @@ class Inverse:
         self.norm_inf = float(np.max(np.asarray(abs(sp.csr_matrix(A)).sum(1))))
         ev = [float(sla.eigvals_banded(self.ab, lower=True, select="i", select_range=(i, i))[0]) for i in (0, self.n - 1)]
         self.kappa2 = ev[1] / ev[0]
-        inv = sla.cho_solve_banded((self.c64, True), np.eye(self.n))                 # (in the band's order; the norm does not care)
-        self.inv_norm_inf = float(np.max(np.sum(np.abs(inv), 1)))
-        self._inv64 = inv
+
+    @functools.cached_property
+    def _inv64(self):
+        """the full float64 inverse in the band's order: only the covariance's bound needs it, the jvp's kappa_2 does not"""
+        return sla.cho_solve_banded((self.c64, True), np.eye(self.n))
+
+    @functools.cached_property
+    def inv_norm_inf(self):
+        return float(np.max(np.sum(np.abs(self._inv64), 1)))                         # (in the band's order; the norm does not care)
 
     def columns(self, cols):
         cols = list(cols)

@@ -1,11 +1,15 @@
-"""tests/banded_ref.py against the dense references it stands in for (backward_ref, covariance_ref), on a ring small enough for both,
-at the oracle's positions: the 6144-row tests of tests/test_gpu_class_limits.py rest on it."""
+"""tests/banded_ref.py against the dense references it stands in for (backward_ref, jvp_ref, covariance_ref), on a ring small enough for
+both, at the oracle's positions: the 6144-row tests of tests/test_gpu_class_limits.py and tests/test_gpu_jvp_class_limits.py rest on it."""
+import copy
+
 import numpy as np
 import pytest
 
+import backward_gn_ref as GN
 import backward_ref as BR
 import banded_ref as BD
 import covariance_ref as CR
+import jvp_ref as JR
 import lfr_oracle as O
 from lfr_amd import synthetic
 
@@ -38,6 +42,38 @@ def test_backward_equals_the_dense_reference(ring):
     bf, bw, bs = BD.backward(cp, xb, ubar)
     assert rs == bs
     assert np.linalg.norm(np.concatenate([(bf - gf).ravel(), bw - gw])) <= 1e-11 * np.linalg.norm(np.concatenate([gf.ravel(), gw]))
+
+
+@pytest.mark.parametrize("gn", [False, True], ids=["exact", "gauss_newton"])
+def test_jvp_equals_the_dense_reference(ring, gn):
+    """banded_ref.jvp against jvp_ref.jvp at the agreement demanded of banded_ref.backward above: the same right-hand side, two
+    backward-stable solves of one system (float64 dense, longdouble banded)"""
+    cp, x = ring
+    rng = np.random.default_rng(2)
+    E = len(cp.src)
+    fdot, sdot = rng.standard_normal((E, 18)), rng.standard_normal(E)
+    H = GN.Component.of(cp).hessian(x) if gn else cp.hessian(x)
+    assert np.abs(BD.sparse_hessian(cp, x, gn).toarray() - H).max() <= 1e-12 * np.abs(H).max()
+    ref, rs = JR.jvp(cp, x, fdot, sdot, gauss_newton=gn)
+    got, bs = BD.jvp(cp, x, fdot, sdot, gauss_newton=gn)
+    assert rs == bs == 0 and ref.any() and got.dtype == np.float64
+    assert np.linalg.norm(got - ref) <= 1e-11 * np.linalg.norm(ref)
+    # coordinates held at the bound: identity rows on both sides, exact zeros in both tangents
+    xb = x.copy()
+    xb[5], xb[40] = 1.0, -1.0
+    ref, rs = JR.jvp(cp, xb, fdot, sdot, gauss_newton=gn)
+    got, bs = BD.jvp(cp, xb, fdot, sdot, gauss_newton=gn)
+    assert rs == bs
+    assert np.linalg.norm(got - ref) <= 1e-11 * np.linalg.norm(ref)
+    assert not got[[5, 40]].any() and not ref[[5, 40]].any()
+    red = BD.reduced_hessian(cp, xb, gn).toarray()
+    assert red[5, 5] == red[40, 40] == 1.0 and np.count_nonzero(red[5]) == np.count_nonzero(red[:, 40]) == 1
+    # a matrix that is not positive definite: zeros and status 2 on both sides
+    cn = copy.copy(cp)
+    cn.sim = -cp.sim
+    ref, rs = JR.jvp(cn, x, fdot, sdot, gauss_newton=gn)
+    got, bs = BD.jvp(cn, x, fdot, sdot, gauss_newton=gn)
+    assert rs == bs == 2 and not ref.any() and not got.any()
 
 
 def test_inverse_and_bound_equal_the_dense_reference(ring):

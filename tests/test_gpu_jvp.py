@@ -56,12 +56,13 @@ def _by_component(info, arr):
 
 
 # ------------------------------------------------------------------------------------------------------ 1. the reference
-def _check_against_reference(ma, g, p, b, ts, which, gn):
+def _check_against_reference(ma, g, p, b, ts, which, gn, variant="ceres1"):
+    """`variant`: the Tukey variant the batch `b` was created with (the reference's components take it)"""
     xdot, st = _jvp(b, ts, gn, want_stats=True)
     x = b.download()
     info = b.component_info()
     term, stat = _by_component(info, info["termination"]), _by_component(info, b.jvp_status())
-    comps = BR.graph_components(ma, *p.labels(), *_nodes(g, ma), which=set(which))
+    comps = BR.graph_components(ma, *p.labels(), *_nodes(g, ma), variant, which=set(which))
     n_checked, worst = 0, 0.0
     usable = [c for c in which if c in comps and term[c] != capi.TERM_FAILURE]
     items = []
