@@ -739,6 +739,62 @@ int lfr_batch_evaluate_vjp(lfr_batch *b, const double *positions_device,
                            void *grad_sim_device,                /* n_matches */
                            int flags, void *hip_stream, lfr_evaluate_vjp_stats *stats);
 
+/* ---------------------------------------------------------------------------------------------
+ * Matrix-free products with the second-order matrix of the objective at given positions: H v per component, nothing assembled.
+ *
+ * Contract.  Per solved-program component c of this shard, whatever its termination, over ALL coordinates of its variable nodes:
+ *   - the matrix.  Default: the exact Hessian of lfr_batch_evaluate's F_c at the given positions, with the records as they are NOW -
+ *     per kept directed edge the block [[P^T M P - w rho' sum_k r_k d2f_k, -P^T M], [-M P, M]] over (x_src, x_dst), M = w (rho' I +
+ *     2 rho'' r r^T), P = I + df/dx_src: the matrix lfr_batch_backward factors, without its row limit and at any positions.
+ *     LFR_HVP_GAUSS_NEWTON: M = w rho' I and no second-derivative term, the J^T J of lfr_batch_covariance and of the LM loop, undamped
+ *     and unscaled.  Both with the derivative of the interpolant zeroed outside [-0.5, 0.5] and kept at exactly +-0.5
+ *     (cost.cc:38-43), the second derivative with it; rho' and rho'' are lfr_batch_backward's (Cauchy: rho' >= DBL_MIN);
+ *   - positions_device: exactly lfr_batch_evaluate's - 2 * n_nodes doubles, or NULL = the batch's own array (NULL before the first
+ *     solve: LFR_ERR_ARG; NULL between an lfr_batch_set_inputs and the next solve is allowed).  Nothing is clamped; constants evaluate
+ *     at 0 whatever the array holds there;
+ *   - vectors_device: n_vectors arrays of 2 * n_nodes doubles in the layout of the positions, one after the other,
+ *     1 <= n_vectors <= LFR_HVP_MAX_VECTORS.  Only the coordinates of variable nodes of this shard's components are read; everything
+ *     else is ignored and counts as 0;
+ *   - the +-1 box is ignored (lfr_batch_covariance's and lfr_batch_evaluate's convention) unless LFR_HVP_FREE_SET is given: then the
+ *     coordinates with |x| >= 1 at the given positions are identity rows and columns, as in lfr_batch_backward - at such an i
+ *     (H v)_i = v_i, and v_i enters no other row;
+ *   - products_device (n_vectors x 2 * n_nodes, may be NULL): the whole array is overwritten; constants, unsolved nodes and nodes
+ *     outside the shard get 0;
+ *   - curvature_device (n_vectors x n_components, may be NULL): curvature[k * n_components + c] = sum_i v_i (H v)_i of vector k over
+ *     component c's variable coordinates, c in the order of lfr_batch_component_info, summed in a fixed order (packed classes: one
+ *     term per lane through the group's butterfly; workgroup classes: a wave-then-block tree);
+ *   - LFR_ERR_ARG, before any output is touched: both outputs NULL, vectors_device NULL, n_vectors out of range, a flag bit other
+ *     than the two defined.  There is no row limit - nothing here needs a matrix - and batches over one rank's connected components
+ *     (lfr_problem_cc_sharded = 1) are served: everything is per node;
+ *   - a vector entry, flow or similarity that is not finite makes the outputs of its own component not finite and changes no other
+ *     component by a bit, one in the same wavefront included; stats->n_nonfinite counts the components with a product entry that is
+ *     not finite;
+ *   - outputs are bitwise repeatable from call to call and identical for host- and device-assembled batches; the outputs of vector k
+ *     are the same bits whether it is passed alone or among others, whatever the others hold.  No fp64 value goes through a
+ *     global-memory atomic;
+ *   - runs on `hip_stream`, asynchronous unless stats != NULL.  Waits BY EVENT for the latest solve and the latest
+ *     lfr_batch_set_inputs; lfr_batch_set_inputs in turn waits for the latest product.  A device-assembled batch whose records are
+ *     not yet written materialises them first, as lfr_batch_evaluate does.
+ * Kernels (lfr_hessian_product.hip): lfr_batch_evaluate's two layouts, the per-edge arithmetic of lfr_batch_backward's assembly
+ * (bwd_eval, bwd_blocks) done once per record for all vectors.  Packed classes: per record and vector t = M (v_dst - P v_src), the
+ * destination adds t, the source -P^T t minus the second-derivative term times v_src, accumulated in the group's LDS.  Workgroup
+ * classes: the thread of a variable node sums its two rows over the node's out- and in-edges in record order. */
+typedef struct lfr_hessian_product_stats {
+    int64_t n_components;          /* components swept (every solved-program component of the shard, whatever its termination) */
+    int64_t n_nonfinite;           /* components with a product entry that is not finite */
+    int64_t n_bound_coordinates;   /* with LFR_HVP_FREE_SET: coordinates treated as bound; else 0 */
+    double kernel_ms;              /* HIP-event time of the call's kernels (and its clearing of the outputs) */
+} lfr_hessian_product_stats;
+
+#define LFR_HVP_GAUSS_NEWTON 2     /* the loss-corrected Gauss-Newton matrix instead of the exact Hessian */
+#define LFR_HVP_FREE_SET 4         /* coordinates at the +-1 bound are identity rows and columns */
+#define LFR_HVP_MAX_VECTORS 4
+
+int lfr_batch_hessian_product(lfr_batch *b, const double *positions_device, const double *vectors_device, int n_vectors,
+                              double *products_device,      /* n_vectors x 2 * n_nodes, may be NULL */
+                              double *curvature_device,     /* n_vectors x n_components, may be NULL */
+                              int flags, void *hip_stream, lfr_hessian_product_stats *stats);
+
 /* Unit-level probe of the device arithmetic (cost.cc:13-48,78-90 + the loss / corrector of solve.cc:111,120): for
  * each of n edges (flows n x 18 float32, sim, kind 0 = intra-track/Cauchy 1 = inter-track/Tukey, x1 = source and
  * x2 = destination position) the kernels' eval_edge on the GPU: out8[8i..] = 0.5*rho, corrected residual r0 r1,

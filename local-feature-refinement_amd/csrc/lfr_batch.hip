@@ -185,6 +185,28 @@ int lfr::pass_end(PassState *s, hipStream_t st) {
     return LFR_OK;
 }
 
+// What the passes that need no solve (lfr_batch.hpp) do before their launches: wait by event for the latest solve and the latest
+// lfr_batch_set_inputs, record the pass's ev0, and write the packed records of a device-assembled batch that still gathers them from
+// the graph's arrays
+int lfr::eval_prologue(lfr_batch *b, PassState &s, hipStream_t st) {
+    // the latest solve (positions; a second solve of a fused batch wrote the records) and the latest set_inputs, whatever streams they ran on
+    if (b->n_solves > 0) HIP_TRY(hipStreamWaitEvent(st, b->ev[1], 0));
+    if (b->ev_inputs && (b->inputs_epoch > 0 || b->inputs_pending)) HIP_TRY(hipStreamWaitEvent(st, b->ev_inputs, 0));
+    HIP_TRY(hipEventRecord(s.ev0, st));
+    if (b->fused) {          // the packed records have not been written yet: write them, as lfr_batch_set_inputs does - one record-reading kernel only
+        if (!b->ev_inputs && !(b->ev_inputs = b->ctx->event_acquire(false))) return LFR_ERR_HIP;
+        lfr::materialize_records(b, st);
+        HIP_TRY(hipGetLastError());
+        b->fused = false;
+        // the next solve reads these records, possibly on another stream: it waits for them as for new inputs (the values are the
+        // graph's own, so the inputs epoch does not move and backward / covariance keep running)
+        HIP_TRY(hipEventRecord(b->ev_inputs, st));
+        b->inputs_stream = st;
+        b->inputs_pending = true;
+    }
+    return LFR_OK;
+}
+
 int64_t lfr::pass_status(lfr_batch *b, PassState *s, const char *name, int32_t *status) {
     if (!b || !s || !s->n_calls) { lfr::set_error("lfr_batch_%s_status: no %s has run on this batch", name, name); return LFR_ERR_ARG; }
     HIP_TRY(hipSetDevice(b->device));

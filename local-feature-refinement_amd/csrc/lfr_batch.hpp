@@ -10,6 +10,7 @@
 //   lfr_evaluate.hip     cost, gradient, residuals and loss weights at given positions (lfr_batch_evaluate) and their vector-Jacobian
 //                        product (lfr_batch_evaluate_vjp): kernels, the launches
 //   lfr_jvp.hip          forward-mode sensitivity of the positions (lfr_batch_jvp): kernels, the launches
+//   lfr_hessian_product.hip   matrix-free H v at given positions (lfr_batch_hessian_product): kernels, the launches
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -259,6 +260,7 @@ struct lfr_batch {
     lfr::PassState *eval = nullptr;                      // lfr_evaluate.hip: set up on the first lfr_batch_evaluate (its own entry: needs no solve)
     lfr::PassState *jvp = nullptr;                       // lfr_jvp.hip: set up on the first lfr_batch_jvp
     lfr::PassState *evjp = nullptr;                      // lfr_evaluate.hip: set up on the first lfr_batch_evaluate_vjp (needs no solve either)
+    lfr::PassState *hvp = nullptr;                       // lfr_hessian_product.hip: set up on the first lfr_batch_hessian_product (needs no solve either)
 
     lfr_batch() { for (auto &e : ev_ring) e = nullptr; }
     ~lfr_batch() {
@@ -267,6 +269,7 @@ struct lfr_batch {
         lfr::pass_free(eval);
         lfr::pass_free(jvp);
         lfr::pass_free(evjp);
+        lfr::pass_free(hvp);
         if (ctx) {
             (void)hipSetDevice(device);
             if (n_solves > 0) (void)hipStreamSynchronize(last_stream);      // nothing may still use the slab
@@ -299,4 +302,8 @@ void materialize_records(lfr_batch *b, hipStream_t st);
 // (LFR_ERR_ARG when that has been freed) - a synchronising call the first time, free afterwards
 int ensure_edge_map(lfr_batch *b);
 inline const uint32_t *edge_map(const lfr_batch *b) { return b->d_edge_ref ? b->d_edge_ref : b->d_eid; }
+// What the passes that need no solve (evaluate, evaluate_vjp, hessian_product) do before their launches: wait by event for the latest
+// solve and the latest lfr_batch_set_inputs, record the pass's ev0, and write the packed records of a device-assembled batch that
+// still gathers them from the graph's arrays
+int eval_prologue(lfr_batch *b, PassState &s, hipStream_t st);
 }  // namespace lfr

@@ -530,27 +530,6 @@ int vjp_setup(lfr_batch *b) {
     return LFR_OK;
 }
 
-// What both entry points do before their launches: wait by event for the latest solve and the latest lfr_batch_set_inputs, record the
-// pass's ev0, and write the packed records of a device-assembled batch that still gathers them from the graph's arrays
-int eval_prologue(lfr_batch *b, lfr::PassState &s, hipStream_t st) {
-    // the latest solve (positions; a second solve of a fused batch wrote the records) and the latest set_inputs, whatever streams they ran on
-    if (b->n_solves > 0) HIP_TRY(hipStreamWaitEvent(st, b->ev[1], 0));
-    if (b->ev_inputs && (b->inputs_epoch > 0 || b->inputs_pending)) HIP_TRY(hipStreamWaitEvent(st, b->ev_inputs, 0));
-    HIP_TRY(hipEventRecord(s.ev0, st));
-    if (b->fused) {          // the packed records have not been written yet: write them, as lfr_batch_set_inputs does - one record-reading kernel only
-        if (!b->ev_inputs && !(b->ev_inputs = b->ctx->event_acquire(false))) return LFR_ERR_HIP;
-        lfr::materialize_records(b, st);
-        HIP_TRY(hipGetLastError());
-        b->fused = false;
-        // the next solve reads these records, possibly on another stream: it waits for them as for new inputs (the values are the
-        // graph's own, so the inputs epoch does not move and backward / covariance keep running)
-        HIP_TRY(hipEventRecord(b->ev_inputs, st));
-        b->inputs_stream = st;
-        b->inputs_pending = true;
-    }
-    return LFR_OK;
-}
-
 }  // namespace
 
 extern "C" {
@@ -577,7 +556,7 @@ int lfr_batch_evaluate(lfr_batch *b, const double *positions_device, double *cos
     hipStream_t st = (hipStream_t)hip_stream;
     const int f64 = (flags & LFR_EVALUATE_F64) ? 1 : 0;
     const size_t M = (size_t)b->n_graph_matches, N = (size_t)b->n_graph_nodes, elt = f64 ? 8 : 4;
-    { const int rc = eval_prologue(b, s, st); if (rc != LFR_OK) return rc; }
+    { const int rc = lfr::eval_prologue(b, s, st); if (rc != LFR_OK) return rc; }
     if (grad_positions_device && N) HIP_TRY(hipMemsetAsync(grad_positions_device, 0, 2 * N * sizeof(double), st));
     if (residuals_device && M) HIP_TRY(hipMemsetAsync(residuals_device, 0, 4 * M * elt, st));
     if (weights_device && M) hipLaunchKernelGGL(k_eval_fill_minus_one, dim3((unsigned)((2 * M + 255) / 256)), dim3(256), 0, st, 2 * M, weights_device, f64);
@@ -647,7 +626,7 @@ int lfr_batch_evaluate_vjp(lfr_batch *b, const double *positions_device, const d
     hipStream_t st = (hipStream_t)hip_stream;
     const int f64 = (flags & LFR_EVALUATE_F64) ? 1 : 0;
     const size_t M = (size_t)b->n_graph_matches, N = (size_t)b->n_graph_nodes, elt = f64 ? 8 : 4;
-    { const int rc = eval_prologue(b, s, st); if (rc != LFR_OK) return rc; }
+    { const int rc = lfr::eval_prologue(b, s, st); if (rc != LFR_OK) return rc; }
     // directions that are no residual block of this shard, and nodes that are not variable, read 0
     if (grad_positions_device && N) HIP_TRY(hipMemsetAsync(grad_positions_device, 0, 2 * N * sizeof(double), st));
     if (grad_disp1_device && M) {

@@ -31,8 +31,9 @@ __device__ __forceinline__ void bwd_basis(double x, double (&l)[3], double (&dl)
     d2l[0] = in ? 4. : 0.; d2l[1] = in ? -8. : 0.; d2l[2] = in ? 4. : 0.;
 }
 
-__device__ __forceinline__ void bwd_eval(const EdgeRec &e, int kind, int tukey_variant, double x1r, double x1c, double x2r, double x2c,
-                                         BwdEdge &o) {
+// (flow, sim: the record's 18 flow values and its similarity, as an EdgeRec holds them or as load_packed_edge hands them over)
+__device__ __forceinline__ void bwd_eval(const float (&flow)[18], const float sim, int kind, int tukey_variant, double x1r, double x1c,
+                                         double x2r, double x2c, BwdEdge &o) {
     bwd_basis(x1r, o.lr, o.dlr, o.d2lr);
     bwd_basis(x1c, o.lc, o.dlc, o.d2lc);
 #pragma unroll
@@ -43,7 +44,7 @@ __device__ __forceinline__ void bwd_eval(const EdgeRec &e, int kind, int tukey_v
         for (int j = 0; j < 3; ++j)
 #pragma unroll
             for (int k = 0; k < 2; ++k) {
-                const double d = (double)e.flow[2 * (3 * i + j) + k];
+                const double d = (double)flow[2 * (3 * i + j) + k];
                 o.f[k] += o.lr[i] * o.lc[j] * d;
                 o.fr[k] += o.dlr[i] * o.lc[j] * d;
                 o.fc[k] += o.lr[i] * o.dlc[j] * d;
@@ -54,7 +55,7 @@ __device__ __forceinline__ void bwd_eval(const EdgeRec &e, int kind, int tukey_v
     o.r[0] = x2r - x1r - o.f[0];
     o.r[1] = x2c - x1c - o.f[1];
     const double s = o.r[0] * o.r[0] + o.r[1] * o.r[1];
-    o.w = (double)e.sim;
+    o.w = (double)sim;
     if (kind == 0) {                                   // CauchyLoss(0.25)
         const double inv = 1.0 / (1.0 + s * kCauchyC);
         o.rho1 = fmax(DBL_MIN, inv);
@@ -66,6 +67,11 @@ __device__ __forceinline__ void bwd_eval(const EdgeRec &e, int kind, int tukey_v
     } else {
         o.rho1 = 0.; o.rho2 = 0.;
     }
+}
+
+__device__ __forceinline__ void bwd_eval(const EdgeRec &e, int kind, int tukey_variant, double x1r, double x1c, double x2r, double x2c,
+                                         BwdEdge &o) {
+    bwd_eval(e.flow, e.sim, kind, tukey_variant, x1r, x1c, x2r, x2c, o);
 }
 
 // M = w (rho' I + 2 rho'' r r^T), P = I + df/dx_src: the edge's Hessian over (x_src, x_dst) is [[P^T M P - w rho' sum_k r_k d2f_k, -P^T M],

@@ -466,6 +466,18 @@ class Refiner:
                         out[name] = full
         return {k: (v.detach() if isinstance(v, torch.Tensor) else v) for k, v in out.items()}
 
+    def hessian_product(self, vectors, positions=None, **kw):
+        """Batch.hessian_product (lfr_batch_hessian_product) on the shared batch: H v of the objective's exact Hessian (or, with
+        gauss_newton=True, its Gauss-Newton matrix) at `positions` ([n_nodes, 2], None = the latest forward's) for `vectors`
+        ([K, n_nodes, 2] or [n_nodes, 2] float64), with the records of the latest forward - or of the constructor before the first.
+        Everything is per node, so nothing is mapped to the caller's rows.  Every tensor is detached: this is no double backward."""
+        if self._batch is None:
+            raise RuntimeError("Refiner: hessian_product after close()")
+        with torch.cuda.device(self.device):
+            out = self._batch.hessian_product(vectors.detach() if isinstance(vectors, torch.Tensor) else vectors,
+                                              positions.detach() if isinstance(positions, torch.Tensor) else positions, **kw)
+        return {k: (v.detach() if isinstance(v, torch.Tensor) else v) for k, v in out.items()}
+
     def objective(self, positions, disp1, disp2, sim=None, *, residuals=False, weights=False):
         """The objective of the latest forward as a differentiable function of (positions, disp1, disp2, sim): `cost` [n_components]
         float64 in the order of Batch.component_info - and, when asked for, `residuals` [rows, 2, 2] and `weights` [rows, 2] (float64,

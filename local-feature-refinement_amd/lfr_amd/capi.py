@@ -78,6 +78,13 @@ class EvaluateVjpStats(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+class HessianProductStats(C.Structure):
+    _fields_ = [(n, C.c_int64) for n in ("n_components", "n_nonfinite", "n_bound_coordinates")] + [("kernel_ms", C.c_double)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
 class JvpStats(C.Structure):
     _fields_ = [(n, C.c_int64) for n in ("n_differentiated", "n_not_usable", "n_indefinite", "n_bound_coordinates")] + [("kernel_ms", C.c_double)]
 
@@ -96,6 +103,9 @@ JVP_OK, JVP_NOT_USABLE, JVP_INDEFINITE, JVP_FALLBACK = 0, 1, 2, 3      # lfr_bat
 COVARIANCE_F64 = 1              # LFR_COVARIANCE_F64
 COVARIANCE_OK, COVARIANCE_NOT_USABLE, COVARIANCE_SINGULAR = 0, 1, 2     # lfr_batch_covariance_status
 EVALUATE_F64 = 1                # LFR_EVALUATE_F64
+HVP_GAUSS_NEWTON = 2            # LFR_HVP_GAUSS_NEWTON
+HVP_FREE_SET = 4                # LFR_HVP_FREE_SET
+HVP_MAX_VECTORS = 4             # LFR_HVP_MAX_VECTORS
 
 
 _lib = None
@@ -169,6 +179,7 @@ def lib():
         "lfr_batch_covariance_status": (i64, [vp, vp]),
         "lfr_batch_evaluate": (C.c_int, [vp, vp, vp, vp, vp, vp, C.c_int, vp, C.POINTER(EvaluateStats)]),
         "lfr_batch_evaluate_vjp": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_int, vp, C.POINTER(EvaluateVjpStats)]),
+        "lfr_batch_hessian_product": (C.c_int, [vp, vp, vp, C.c_int, vp, vp, C.c_int, vp, C.POINTER(HessianProductStats)]),
         "lfr_keypoint_covariances": (C.c_int, [vp, vp, C.c_char_p, vp, i64]),
         "lfr_debug_invert_spd": (C.c_int, [C.c_int, C.c_int, i64, vp, vp, vp, vp]),
         "lfr_batch_spin_timeouts": (i64, [vp]),
@@ -204,7 +215,7 @@ EXPORTS = ["lfr_version", "lfr_last_error", "lfr_graph_from_files", "lfr_graph_f
            "lfr_graph_num_images", "lfr_graph_get_nodes", "lfr_graph_image_name", "lfr_graph_image_fact",
            "lfr_write_matching_file", "lfr_problem_build", "lfr_problem_build_labels", "lfr_problem_build_hip", "lfr_problem_free", "lfr_problem_get_stats",
            "lfr_problem_get_labels", "lfr_problem_shard_components", "lfr_hip_warmup", "lfr_batch_create", "lfr_batch_free", "lfr_batch_solve", "lfr_batch_solve_from",
-           "lfr_batch_download", "lfr_batch_timing", "lfr_batch_spin_timeouts", "lfr_batch_team_runs", "lfr_batch_team_fallbacks", "lfr_debug_occupy", "lfr_batch_tree_stats", "lfr_batch_component_info", "lfr_batch_positions_to_device", "lfr_batch_backward", "lfr_batch_backward_status", "lfr_batch_jvp", "lfr_batch_jvp_status", "lfr_batch_set_inputs", "lfr_batch_covariance", "lfr_batch_covariance_matches", "lfr_batch_covariance_status", "lfr_batch_evaluate", "lfr_batch_evaluate_vjp", "lfr_keypoint_covariances", "lfr_debug_invert_spd", "lfr_solve_hip", "lfr_solve_hip_multi", "lfr_solve_graph_hip_multi", "lfr_write_solution", "lfr_apply_displacements"]
+           "lfr_batch_download", "lfr_batch_timing", "lfr_batch_spin_timeouts", "lfr_batch_team_runs", "lfr_batch_team_fallbacks", "lfr_debug_occupy", "lfr_batch_tree_stats", "lfr_batch_component_info", "lfr_batch_positions_to_device", "lfr_batch_backward", "lfr_batch_backward_status", "lfr_batch_jvp", "lfr_batch_jvp_status", "lfr_batch_set_inputs", "lfr_batch_covariance", "lfr_batch_covariance_matches", "lfr_batch_covariance_status", "lfr_batch_evaluate", "lfr_batch_evaluate_vjp", "lfr_batch_hessian_product", "lfr_keypoint_covariances", "lfr_debug_invert_spd", "lfr_solve_hip", "lfr_solve_hip_multi", "lfr_solve_graph_hip_multi", "lfr_write_solution", "lfr_apply_displacements"]
 
 
 def _check(rc):
@@ -1010,6 +1021,60 @@ class Batch:
         _check(lib().lfr_batch_evaluate_vjp(self._h, pp, pc, pr, pw, optr("positions"), optr("disp1"), optr("disp2"), optr("sim"),
                                             EVALUATE_F64 if f64 else 0, C.c_void_p(stream) if stream else None,
                                             C.byref(st) if want_stats else None))
+        if want_stats:
+            out["stats"] = st.as_dict()
+        return out
+
+    def hessian_product(self, vectors, positions=None, *, gauss_newton=False, free_set=False, products=True, curvature=False,
+                        stream=None, want_stats=False):
+        """Matrix-free H v at `positions` (lfr_batch_hessian_product, include/lfr.h): H the exact Hessian of evaluate()'s objective,
+        or the loss-corrected Gauss-Newton matrix with gauss_newton=True, per component over the coordinates of its variable nodes,
+        with the records as they are now.  vectors: a contiguous [K, n_nodes, 2] (1 <= K <= HVP_MAX_VECTORS) or [n_nodes, 2] float64
+        tensor on the batch's device, in the layout of the positions; entries of nodes that are not variable are ignored.  positions:
+        a contiguous [n_nodes, 2] float64 tensor, or None = the batch's own (after a solve).  free_set=True: coordinates with
+        |x| >= 1 are identity rows and columns, as in backward().  Returns a dict of device tensors: "products" with the shape of
+        `vectors` (0 for nodes that are not variable) and / or "curvature" [K, n_components] ([n_components] for one [n_nodes, 2]
+        vector), v . H v per component in the order of component_info; with want_stats also "stats" (that waits)."""
+        import torch
+        n = self.problem.graph.n_nodes
+        dev = torch.device("cuda", self.device)
+
+        def check(t, name, shapes):
+            if not isinstance(t, torch.Tensor):
+                raise ValueError("hessian_product: %s must be a torch tensor" % name)
+            if not t.is_cuda or t.device != dev:
+                raise ValueError("hessian_product: %s is on %s, the batch on %s" % (name, t.device, dev))
+            if t.dtype != torch.float64:
+                raise ValueError("hessian_product: %s is %s, need torch.float64" % (name, t.dtype))
+            if not t.is_contiguous() or not any(t.dim() == len(s) and all(w is None or w == h for w, h in zip(s, t.shape)) for s in shapes):
+                raise ValueError("hessian_product: %s has shape %s, need a contiguous %s"
+                                 % (name, tuple(t.shape), " or ".join("[%s]" % ", ".join("K" if w is None else str(w) for w in s) for s in shapes)))
+            return C.c_void_p(t.detach().data_ptr() or 1)      # (no nodes: an empty tensor has no address, and nothing is read)
+
+        pv = check(vectors, "vectors", ((None, n, 2), (n, 2)))
+        single = vectors.dim() == 2
+        k = 1 if single else int(vectors.shape[0])
+        if not 1 <= k <= HVP_MAX_VECTORS:
+            raise ValueError("hessian_product: %d vectors, need 1 to %d" % (k, HVP_MAX_VECTORS))
+        pp = None if positions is None else check(positions, "positions", ((n, 2),))
+        out = {}
+        if products:
+            out["products"] = torch.empty(tuple(vectors.shape), dtype=torch.float64, device=dev)
+        if curvature:
+            nc = lib().lfr_batch_component_info(self._h, None, None, None, None, None, None)
+            if nc < 0:
+                _check(int(nc))
+            out["curvature"] = torch.empty((nc,) if single else (k, nc), dtype=torch.float64, device=dev)
+        if stream is None:
+            stream = torch.cuda.current_stream(dev).cuda_stream
+
+        def optr(name):
+            return C.c_void_p(out[name].data_ptr() or 1) if name in out else None
+
+        st = HessianProductStats()
+        flags = (HVP_GAUSS_NEWTON if gauss_newton else 0) | (HVP_FREE_SET if free_set else 0)
+        _check(lib().lfr_batch_hessian_product(self._h, pp, pv, k, optr("products"), optr("curvature"), flags,
+                                               C.c_void_p(stream) if stream else None, C.byref(st) if want_stats else None))
         if want_stats:
             out["stats"] = st.as_dict()
         return out
