@@ -131,10 +131,7 @@ __global__ void k_sum_node_edges(int64_t n_nodes, const int32_t *comp, const uin
 }
 
 __device__ __forceinline__ int classify_dev(uint32_t rows, uint32_t n_edges, uint32_t block_max) {
-    if (rows <= 8 && n_edges <= 24) return KC_G8;
-    if (rows <= 16 && n_edges <= 96) return KC_G16;
-    if (rows <= 24 && n_edges <= 192) return KC_G64_2;
-    if (rows <= 32 && n_edges <= 320) return KC_G64_4;
+    if (const int packed = classify_packed(rows, n_edges); packed >= 0) return packed;
     if (rows <= min((uint32_t)kBlockRowsS, block_max)) return KC_BLOCK;
     if (rows <= min((uint32_t)kBlockRowsM, block_max)) return KC_BLOCK_M;
     if (rows <= block_max) return KC_BLOCK_L;
@@ -558,7 +555,7 @@ struct AsmPlan {                                   // the decisions of one assem
     // batch gathers its records now and never looks at the caller's memory again.
     bool fused;
     // the graph stage's largest component says whether a workgroup class can exist (packed classes take up to 16 variable nodes).
-    // A small component with > 320 edges - duplicated matches - still lands in one: the summary has the last word
+    // A small component with more edges than the largest packed class takes - duplicated matches - still lands in one: the summary has the last word
     // (redo_for_unexpected_workgroup_classes)
     bool expect_workgroup_classes;
     // packed classes only: the matches go through their sort before the counts, by component id, and the runs are the edge counts
@@ -582,7 +579,7 @@ struct AsmPlan {                                   // the decisions of one assem
         aligned8 = (((uintptr_t)dg.disp1 | (uintptr_t)dg.disp2) & 7u) == 0;
         fused = shard_world == 1 && !dg.flows_zero_copy && !dg.flows_external && aligned8 && dg.disp1 && dg.disp2;
         if (const char *e = getenv("LFR_FUSED_GATHER")) fused = fused && e[0] != '0';
-        expect_workgroup_classes = p.stats.max_component_size > 17;
+        expect_workgroup_classes = p.stats.max_component_size > kPackedClass[kPackedClasses - 1].max_rows / 2 + 1;      // (+ the root)
         match_sort_first = !expect_workgroup_classes;
         words_done = match_sort_first && fused;
         check_pairs = !fused || getenv("LFR_CHECK_PAIRS");

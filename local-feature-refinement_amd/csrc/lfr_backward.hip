@@ -156,26 +156,21 @@ struct alignas(16) BwdGnLds {
     double v[NV + 2];          // v = H^-1 ubar; slots 2*n_var, 2*n_var+1 stay 0 (constants)
 };
 
-template <int CLS, int EPL>
+template <int KC>
 __device__ __forceinline__ void bwd_gn_group_body(const BwdArgs &a, const int desc_begin, const int desc_end, const int block_in_class,
                                                   unsigned char *lds_raw) {
-    constexpr int NV = CLS == 0 ? 8 : CLS == 1 ? 16 : 32, LPR = CLS == 3 ? 2 : 1;
-    constexpr int S = NV * LPR, G = 64 / S, LD = NV + 1;
-    const int lane = threadIdx.x & 63;
-    const int gid = lane / S, sl = lane % S;
+    constexpr int NV = PackedClass<KC>::NV, S = PackedClass<KC>::S, EPL = PackedClass<KC>::EPL, LD = NV + 1;
+    PackedGroup<KC> grp;
+    if (!grp.init(a.descs, desc_begin, desc_end, block_in_class)) return;
+    const int gid = grp.gid, sl = grp.sl, ci = grp.ci;
     const int row = sl % NV, part = sl / NV;
-    const int ci0 = desc_begin + block_in_class * G;
-    if (ci0 >= desc_end) return;                      // wave-uniform
-    const int ci = ci0 + gid;
-    const bool have = ci < desc_end;
+    const bool have = grp.have;
+    const CompDesc &d = grp.d;
     BwdGnLds<NV> &B = reinterpret_cast<BwdGnLds<NV> *>(lds_raw)[gid];
     CovLds<NV> &L = B.c;
 
-    CompDesc d;
-    d.edge_off = 0; d.n_edges = 0; d.node_off = 0; d.n_nodes = 0; d.n_var = 0;
-    if (have) d = a.descs[ci];
     const bool usable = have && a.infos[ci].termination != LFR_TERM_FAILURE;
-    const int n_var = usable ? d.n_var : 0, nv2 = 2 * n_var, E = usable ? (int)d.n_edges : 0;     // a group without a usable component inverts the identity
+    const int n_var = usable ? grp.n_var : 0, nv2 = 2 * n_var, E = usable ? grp.E : 0;     // a group without a usable component inverts the identity
     const bool is_row = row < nv2;
     const int nv2_max = cov_wave_max(nv2);
 
@@ -194,7 +189,7 @@ __device__ __forceinline__ void bwd_gn_group_body(const BwdArgs &a, const int de
     // ---- inversion with the bound rows and columns the identity's, lane = row; v = C ubar ----
     const double *A = L.A;
     bool solved = false;
-    cov_invert<CLS>(row, nv2_max,
+    cov_invert<KC>(row, nv2_max,
         [&](int c) -> double {
             double h = 0.0;
             if (is_row && c < nv2) h = (c <= row ? A[row * LD + c] : A[c * LD + row]);
@@ -235,12 +230,9 @@ static_assert(kBwdGnLdsBytes >= 8 * sizeof(BwdGnLds<8>), "LDS budget");
 // all packed classes in ONE launch, the blocks dealt to the classes as in covariance_packed_kernel
 __global__ __launch_bounds__(64, 2) void backward_gn_packed_kernel(const BwdArgs a, const PackedRanges r) {
     __shared__ __attribute__((aligned(16))) unsigned char lds_raw[kBwdGnLdsBytes];
-    const int b = (int)blockIdx.x;
-    if (b < r.blk_begin[1]) bwd_gn_group_body<3, 5>(a, r.desc_begin[0], r.desc_end[0], b - r.blk_begin[0], lds_raw);
-    else if (b < r.blk_begin[2]) bwd_gn_group_body<2, 6>(a, r.desc_begin[1], r.desc_end[1], b - r.blk_begin[1], lds_raw);
-    else if (b < r.blk_begin[3]) { /* retired class, never assigned */ }
-    else if (b < r.blk_begin[4]) bwd_gn_group_body<1, 6>(a, r.desc_begin[3], r.desc_end[3], b - r.blk_begin[3], lds_raw);
-    else bwd_gn_group_body<0, 3>(a, r.desc_begin[4], r.desc_end[4], b - r.blk_begin[4], lds_raw);
+    packed_dispatch(r, [&](auto kc, int desc_begin, int desc_end, int block_in_class) LFR_INLINE_LAMBDA {
+        bwd_gn_group_body<decltype(kc)::value>(a, desc_begin, desc_end, block_in_class, lds_raw);
+    });
 }
 
 __global__ void k_bwd_sim(int64_t n_matches, const double *dir, void *out, int f64) {
@@ -324,11 +316,8 @@ int lfr_batch_backward(lfr_batch *b, const double *grad_positions_device, void *
     // Packed classes (<= 32 rows).  Gauss-Newton mode: ONE launch of one-wave blocks, each wave hosting 64/S = 2-8 components (1 in
     // <32,2>), dealt to the classes as lfr_batch_covariance deals its own.  Exact mode (with or without the fallback): backward_kernel, one wave per component.
     if (gn) {
-        PackedRanges r;
-        int nb = 0;
-        lfr::packed_ranges(b, 1, &r, &nb);
         a.desc_begin = b->class_begin[0]; a.scan_all = 0;
-        if (nb > 0) hipLaunchKernelGGL(backward_gn_packed_kernel, dim3(nb), dim3(64), 0, st, a, r);
+        lfr::launch_packed_pass(b, backward_gn_packed_kernel, a, st);
     } else {
         a.desc_begin = b->class_begin[0];
         const int n = b->class_begin[lfr::KC_BLOCK] - a.desc_begin;

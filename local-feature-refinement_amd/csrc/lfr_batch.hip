@@ -113,16 +113,14 @@ void lfr::materialize_records(lfr_batch *b, hipStream_t st) {
 // the packed launch's blocks; the state of a pass that runs after a solve (lfr_batch.hpp)
 // =============================================================================================
 void lfr::packed_ranges(const lfr_batch *b, int waves_per_block, PackedRanges *r, int *n_blocks) {
-    static const int kPackedOrder[5] = {lfr::KC_G64_4, lfr::KC_G64_2, lfr::KC_G32, lfr::KC_G16, lfr::KC_G8};     // dispatch order: PackedRanges is indexed by it
-    const lfr::SolveGeometry &geo = lfr::solve_geometry();
     int nb = 0;
-    for (int i = 0; i < 5; ++i) {
-        const int cls = kPackedOrder[i], per_block = geo.comps_per_block[cls] / geo.packed_waves * waves_per_block;
+    for (int i = 0; i < lfr::kPackedClasses; ++i) {
+        const int cls = lfr::kPackedOrder[i], per_block = lfr::kPackedClass[cls].G() * waves_per_block;
         r->blk_begin[i] = nb;
         r->desc_begin[i] = b->class_begin[cls]; r->desc_end[i] = b->class_begin[cls + 1];
         nb += (r->desc_end[i] - r->desc_begin[i] + per_block - 1) / per_block;
     }
-    r->blk_begin[5] = nb;
+    r->blk_begin[lfr::kPackedClasses] = nb;
     *n_blocks = nb;
 }
 
@@ -178,6 +176,17 @@ int lfr::pass_begin(lfr_batch *b, PassState **slot, const PassKind &kind, size_t
     return LFR_OK;
 }
 
+// first call of a pass that needs no solve: no workspace for matrices, no status words - a slab for the pass's own carvings
+// (kind.extra makes them) and the two events
+int lfr::pass_setup_unsolved(lfr_batch *b, PassState **slot, const PassKind &kind, size_t slab_bytes) {
+    std::unique_ptr<lfr::PassState, void (*)(lfr::PassState *)> s(kind.make(), lfr::pass_free);      // every error path releases slab and events
+    if (!s->slab.init(b->ctx, slab_bytes)) return LFR_ERR_NOMEM;
+    { const int rc = kind.extra(b, s.get()); if (rc != LFR_OK) return rc; }
+    HIP_TRY(hipEventCreate(&s->ev0)); HIP_TRY(hipEventCreate(&s->ev1));
+    *slot = s.release();
+    return LFR_OK;
+}
+
 int lfr::pass_end(PassState *s, hipStream_t st) {
     HIP_TRY(hipEventRecord(s->ev1, st));
     s->last_stream = st;
@@ -207,6 +216,14 @@ int lfr::eval_prologue(lfr_batch *b, PassState &s, hipStream_t st) {
     return LFR_OK;
 }
 
+int lfr::pass_wait_ms(PassState *s, hipStream_t st, double *kernel_ms) {
+    HIP_TRY(lfr::stream_wait(st));
+    float ms = 0.f;
+    HIP_TRY(hipEventElapsedTime(&ms, s->ev0, s->ev1));
+    *kernel_ms = ms;
+    return LFR_OK;
+}
+
 int64_t lfr::pass_status(lfr_batch *b, PassState *s, const char *name, int32_t *status) {
     if (!b || !s || !s->n_calls) { lfr::set_error("lfr_batch_%s_status: no %s has run on this batch", name, name); return LFR_ERR_ARG; }
     HIP_TRY(hipSetDevice(b->device));
@@ -223,12 +240,9 @@ int lfr::pass_histogram(lfr_batch *b, PassState *s, hipStream_t st, int64_t coun
     HIP_TRY(hipEventSynchronize(s->ev1));
     std::vector<int32_t> status(b->descs.size());
     if (!status.empty()) HIP_TRY(hipMemcpyAsync(status.data(), s->d_status, 4 * status.size(), hipMemcpyDeviceToHost, st));
-    HIP_TRY(lfr::stream_wait(st));
+    { const int rc = lfr::pass_wait_ms(s, st, kernel_ms); if (rc != LFR_OK) return rc; }
     count[0] = count[1] = count[2] = 0;
     for (int32_t v : status) ++count[(v == 0 || v == 3) ? 0 : v == 1 ? 1 : 2];      // (3: differentiated with the Gauss-Newton fallback)
-    float ms = 0.f;
-    HIP_TRY(hipEventElapsedTime(&ms, s->ev0, s->ev1));
-    *kernel_ms = ms;
     return LFR_OK;
 }
 
@@ -846,7 +860,7 @@ int launch_serial(lfr_batch *b, KernelArgs &a, uint32_t &recorded, hipStream_t s
         HIP_TRY(hipEventRecord(b->ev[2 + 2 * cls], st));
         {
             const int grid = (n + comps_per_block[cls] - 1) / comps_per_block[cls];
-            if (cls < lfr::KC_BLOCK) lfr::launch_group_class(cls, a, b->fused, grid, st);       // (KC_G32: retired class, never assigned)
+            if (cls < lfr::KC_BLOCK) lfr::launch_group_class(cls, a, b->fused, grid, st);       // (KC_G32 is retired: no component)
             else { const int rc = launch_wg_class(b, a, cls, st); if (rc != LFR_OK) return rc; }
             HIP_TRY(hipGetLastError());
         }

@@ -4,13 +4,15 @@
 //   lfr_solve.hip        the forward kernels, their debug probes, and the launch functions declared in this header
 //   lfr_batch.hip        batch creation, the launch plan of lfr_batch_solve (packed_ranges deals the packed launch), its diagnostic
 //                        read-backs and statistics, the PassState functions, timing, downloads, warm-up, multi-GPU entry points
-//   lfr_backward.hip     implicit-gradient backward pass (lfr_batch_backward): kernels, its own carvings, the launches
-//   lfr_covariance.hip   per-keypoint covariance (lfr_batch_covariance): kernels, the launches
 //   lfr_inputs.hip       new flows / similarities into a live batch (lfr_batch_set_inputs) and the record -> directed-edge map
+// the analysis passes, each its kernels and launches; their packed kernels share one frame (lfr_packed_frame.hpp: the classes'
+// traits from lfr_internal.hpp's table, the dispatcher, the group identity) and their host code the helpers at the end of this header:
 //   lfr_evaluate.hip     cost, gradient, residuals and loss weights at given positions (lfr_batch_evaluate) and their vector-Jacobian
-//                        product (lfr_batch_evaluate_vjp): kernels, the launches
-//   lfr_jvp.hip          forward-mode sensitivity of the positions (lfr_batch_jvp): kernels, the launches
-//   lfr_hessian_product.hip   matrix-free H v at given positions (lfr_batch_hessian_product): kernels, the launches
+//                        product (lfr_batch_evaluate_vjp)
+//   lfr_hessian_product.hip   matrix-free H v at given positions (lfr_batch_hessian_product)
+//   lfr_jvp.hip          forward-mode sensitivity of the positions (lfr_batch_jvp)
+//   lfr_backward.hip     implicit-gradient backward pass (lfr_batch_backward)
+//   lfr_covariance.hip   per-keypoint and per-match covariance (lfr_batch_covariance, lfr_batch_covariance_matches)
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -101,10 +103,10 @@ constexpr size_t kProfWords = kProfFactor + kProfFactorWords * (KC_COUNT - KC_BL
 __host__ __device__ inline unsigned int *queue_block(unsigned long long *prof) { return reinterpret_cast<unsigned int *>(prof + kProfQueue); }
 __host__ __device__ inline unsigned long long *factor_profile(unsigned long long *prof, int cls) { return prof + kProfFactor + kProfFactorWords * (cls - KC_BLOCK); }
 
-// solve_packed_kernel / covariance_packed_kernel: blocks [blk_begin[i], blk_begin[i+1]) of the one launch belong to packed class i
+// one launch for all packed classes: blocks [blk_begin[i], blk_begin[i+1]) belong to packed class kPackedOrder[i]
 struct PackedRanges {
-    int blk_begin[6];          // G64_4, G64_2, G32, G16, G8 in dispatch order
-    int desc_begin[5], desc_end[5];
+    int blk_begin[kPackedClasses + 1];
+    int desc_begin[kPackedClasses], desc_end[kPackedClasses];
 };
 
 // ---- lfr_solve.hip: the forward kernels' launch functions.  The caller (the launch plan of lfr_batch_solve) chooses streams, events,
@@ -162,7 +164,11 @@ hipEvent_t pass_last_event(const PassState *s);         // end of the latest cal
 // first call (*slot is installed only after every step has succeeded; slab and events are released on every error path), the wait
 // for the latest solve, the record of ev0 on st.
 int pass_begin(lfr_batch *b, PassState **slot, const PassKind &kind, size_t extra_bytes, hipStream_t st);
+// The same for the passes that need no solve (evaluate, evaluate_vjp, hessian_product), whose entry is their own: the first call's
+// setup with a slab of slab_bytes for kind.extra to carve (installed in *slot as above)
+int pass_setup_unsolved(lfr_batch *b, PassState **slot, const PassKind &kind, size_t slab_bytes);
 int pass_end(PassState *s, hipStream_t st);             // records ev1; the call is now the pass's latest
+int pass_wait_ms(PassState *s, hipStream_t st, double *kernel_ms);      // waits for st (read-backs queued on it are in): the time between the call's events
 int64_t pass_status(lfr_batch *b, PassState *s, const char *name, int32_t *status);     // lfr_batch_<name>_status
 int pass_histogram(lfr_batch *b, PassState *s, hipStream_t st, int64_t count[3], double *kernel_ms);     // waits for the latest call: descriptors with status 0 or 3, 1, 2 and the time between its events
 // deals the blocks of the one packed launch to the packed classes, waves_per_block waves each (components per wave: solve_geometry())
@@ -306,4 +312,23 @@ inline const uint32_t *edge_map(const lfr_batch *b) { return b->d_edge_ref ? b->
 // solve and the latest lfr_batch_set_inputs, record the pass's ev0, and write the packed records of a device-assembled batch that
 // still gathers them from the graph's arrays
 int eval_prologue(lfr_batch *b, PassState &s, hipStream_t st);
+
+// ---- the launches of a pass.  Errors: hipGetLastError(). ----
+// packed classes: ONE launch of one-wave blocks, dealt to the classes by packed_ranges; packed(a, ranges)
+template <class Packed, class Args>
+void launch_packed_pass(const lfr_batch *b, Packed packed, const Args &a, hipStream_t st) {
+    PackedRanges r;
+    int nb = 0;
+    packed_ranges(b, 1, &r, &nb);
+    if (nb > 0) hipLaunchKernelGGL(packed, dim3(nb), dim3(64), 0, st, a, r);
+}
+// the two layouts of a pass without a matrix: the packed launch, then one workgroup per component of every workgroup class in one
+// launch (they are contiguous in the batch order); block(a) with a.desc_begin its first descriptor
+template <class Packed, class Block, class Args>
+void launch_two_layouts(const lfr_batch *b, Packed packed, Block block, int block_threads, Args a, hipStream_t st) {
+    launch_packed_pass(b, packed, a, st);
+    a.desc_begin = b->class_begin[KC_BLOCK];
+    const int n = b->class_begin[KC_COUNT] - a.desc_begin;
+    if (n > 0) hipLaunchKernelGGL(block, dim3(n), dim3(block_threads), 0, st, a);
+}
 }  // namespace lfr

@@ -46,26 +46,21 @@ __device__ __forceinline__ void cov_store(const CovArgs &a, const uint32_t node,
     else { float *o = static_cast<float *>(a.cov) + 3 * (size_t)node; o[0] = (float)c00; o[1] = (float)c01; o[2] = (float)c11; }
 }
 
-template <int CLS, int EPL, bool FUSED>
+template <int KC, bool FUSED>
 __device__ __forceinline__ void cov_group_body(const CovArgs &ca, const int desc_begin, const int desc_end, const int block_in_class,
                                                unsigned char *lds_raw) {
-    constexpr int NV = CLS == 0 ? 8 : CLS == 1 ? 16 : 32, LPR = CLS == 3 ? 2 : 1;
-    constexpr int S = NV * LPR, G = 64 / S, LD = NV + 1;
+    constexpr int NV = PackedClass<KC>::NV, S = PackedClass<KC>::S, EPL = PackedClass<KC>::EPL, LD = NV + 1;
     const KernelArgs &a = ca.k;
-    const int lane = threadIdx.x & 63;
-    const int gid = lane / S, sl = lane % S;
+    PackedGroup<KC> grp;
+    if (!grp.init(a.descs, desc_begin, desc_end, block_in_class)) return;
+    const int sl = grp.sl, ci = grp.ci;
     const int row = sl % NV, part = sl / NV;
-    const int ci0 = desc_begin + block_in_class * G;
-    if (ci0 >= desc_end) return;                      // wave-uniform
-    const int ci = ci0 + gid;
-    const bool have = ci < desc_end;
-    CovLds<NV> &L = reinterpret_cast<CovLds<NV> *>(lds_raw)[gid];
+    const bool have = grp.have;
+    const CompDesc &d = grp.d;
+    CovLds<NV> &L = reinterpret_cast<CovLds<NV> *>(lds_raw)[grp.gid];
 
-    CompDesc d;
-    d.edge_off = 0; d.n_edges = 0; d.node_off = 0; d.n_nodes = 0; d.n_var = 0;
-    if (have) d = a.descs[ci];
     const bool usable = have && a.infos[ci].termination != LFR_TERM_FAILURE;
-    const int n_var = usable ? d.n_var : 0, nv2 = 2 * n_var, E = usable ? (int)d.n_edges : 0;     // a group without a usable component inverts the identity
+    const int n_var = usable ? grp.n_var : 0, nv2 = 2 * n_var, E = usable ? grp.E : 0;     // a group without a usable component inverts the identity
     const bool is_row = row < nv2;
     const int nv2_max = cov_wave_max(nv2);
     const uint32_t node = is_row ? a.node_ids[d.node_off + (row >> 1)] : 0u;
@@ -77,7 +72,7 @@ __device__ __forceinline__ void cov_group_body(const CovArgs &ca, const int desc
 
     // ---- inversion, lane = row ----
     const double *A = L.A;
-    cov_invert<CLS>(row, nv2_max,
+    cov_invert<KC>(row, nv2_max,
         [&](int c) -> double {
             double v = 0.0;
             if (is_row && c < nv2) v = (c <= row ? A[row * LD + c] : A[c * LD + row]);
@@ -101,20 +96,16 @@ static_assert(kCovPackedLdsBytes >= 8 * sizeof(CovLds<8>), "LDS budget");
 template <bool FUSED>
 __global__ __launch_bounds__(64, 2) void covariance_packed_kernel(const CovArgs a, const PackedRanges r) {
     __shared__ __attribute__((aligned(16))) unsigned char lds_raw[kCovPackedLdsBytes];
-    const int b = (int)blockIdx.x;
-    if (b < r.blk_begin[1]) cov_group_body<3, 5, FUSED>(a, r.desc_begin[0], r.desc_end[0], b - r.blk_begin[0], lds_raw);
-    else if (b < r.blk_begin[2]) cov_group_body<2, 6, FUSED>(a, r.desc_begin[1], r.desc_end[1], b - r.blk_begin[1], lds_raw);
-    else if (b < r.blk_begin[3]) { /* retired class, never assigned */ }
-    else if (b < r.blk_begin[4]) cov_group_body<1, 6, FUSED>(a, r.desc_begin[3], r.desc_end[3], b - r.blk_begin[3], lds_raw);
-    else cov_group_body<0, 3, FUSED>(a, r.desc_begin[4], r.desc_end[4], b - r.blk_begin[4], lds_raw);
+    packed_dispatch(r, [&](auto kc, int desc_begin, int desc_end, int block_in_class) LFR_INLINE_LAMBDA {
+        cov_group_body<decltype(kc)::value, FUSED>(a, desc_begin, desc_end, block_in_class, lds_raw);
+    });
 }
 
 // lfr_debug_invert_spd: the inversion alone, systems placed as the groups of a wave
-template <int CLS>
+template <int KC>
 __global__ __launch_bounds__(64) void debug_invert_kernel(int64_t n_sys, const int32_t *n_rows, const int64_t *tri_off, const double *A,
                                                           double *Cinv, int32_t *status) {
-    constexpr int NV = CLS == 0 ? 8 : CLS == 1 ? 16 : 32, LPR = CLS == 3 ? 2 : 1;
-    constexpr int S = NV * LPR, G = 64 / S;
+    constexpr int NV = PackedClass<KC>::NV, S = PackedClass<KC>::S, G = PackedClass<KC>::G;
     const int lane = threadIdx.x & 63;
     const int gid = lane / S, sl = lane % S;
     const int row = sl % NV, part = sl / NV;
@@ -124,7 +115,7 @@ __global__ __launch_bounds__(64) void debug_invert_kernel(int64_t n_sys, const i
     const int64_t to = have ? tri_off[sys] : 0;
     const bool is_row = row < n;
     const int n_max = cov_wave_max(n);
-    cov_invert<CLS>(row, n_max,
+    cov_invert<KC>(row, n_max,
         [&](int c) -> double {
             double v = 0.0;
             if (is_row && c < n) v = A[to + (int64_t)bwd_tri(max(row, c), min(row, c))];
@@ -252,27 +243,22 @@ struct CovMatchArgs {
 
 // cov_group_body, and behind the inversion: every row lane puts its row of C into the group's LDS matrix (the assembled A is dead by
 // then), then sub-lane sl re-reads the words of records sl + S k and the node1 -> node2 records write their match
-template <int CLS, int EPL, bool FUSED>
+template <int KC, bool FUSED>
 __device__ __forceinline__ void cov_match_group_body(const CovMatchArgs &ma, const int desc_begin, const int desc_end, const int block_in_class,
                                                      unsigned char *lds_raw) {
-    constexpr int NV = CLS == 0 ? 8 : CLS == 1 ? 16 : 32, LPR = CLS == 3 ? 2 : 1;
-    constexpr int S = NV * LPR, G = 64 / S, LD = NV + 1;
+    constexpr int NV = PackedClass<KC>::NV, S = PackedClass<KC>::S, EPL = PackedClass<KC>::EPL, LD = NV + 1;
     const CovArgs &ca = ma.c;
     const KernelArgs &a = ca.k;
-    const int lane = threadIdx.x & 63;
-    const int gid = lane / S, sl = lane % S;
+    PackedGroup<KC> grp;
+    if (!grp.init(a.descs, desc_begin, desc_end, block_in_class)) return;
+    const int sl = grp.sl, ci = grp.ci;
     const int row = sl % NV, part = sl / NV;
-    const int ci0 = desc_begin + block_in_class * G;
-    if (ci0 >= desc_end) return;                      // wave-uniform
-    const int ci = ci0 + gid;
-    const bool have = ci < desc_end;
-    CovLds<NV> &L = reinterpret_cast<CovLds<NV> *>(lds_raw)[gid];
+    const bool have = grp.have;
+    const CompDesc &d = grp.d;
+    CovLds<NV> &L = reinterpret_cast<CovLds<NV> *>(lds_raw)[grp.gid];
 
-    CompDesc d;
-    d.edge_off = 0; d.n_edges = 0; d.node_off = 0; d.n_nodes = 0; d.n_var = 0;
-    if (have) d = a.descs[ci];
     const bool usable = have && a.infos[ci].termination != LFR_TERM_FAILURE;
-    const int n_var = usable ? d.n_var : 0, nv2 = 2 * n_var, E = usable ? (int)d.n_edges : 0;     // a group without a usable component inverts the identity
+    const int n_var = usable ? grp.n_var : 0, nv2 = 2 * n_var, E = usable ? grp.E : 0;     // a group without a usable component inverts the identity
     const bool is_row = row < nv2;
     const int nv2_max = cov_wave_max(nv2);
     const uint32_t node = is_row ? a.node_ids[d.node_off + (row >> 1)] : 0u;
@@ -285,7 +271,7 @@ __device__ __forceinline__ void cov_match_group_body(const CovMatchArgs &ma, con
     // ---- inversion, lane = row ----
     double *A = L.A;
     bool solved = false;
-    cov_invert<CLS>(row, nv2_max,
+    cov_invert<KC>(row, nv2_max,
         [&](int c) -> double {
             double v = 0.0;
             if (is_row && c < nv2) v = (c <= row ? A[row * LD + c] : A[c * LD + row]);
@@ -336,12 +322,9 @@ __device__ __forceinline__ void cov_match_group_body(const CovMatchArgs &ma, con
 template <bool FUSED>
 __global__ __launch_bounds__(64, 2) void covariance_matches_packed_kernel(const CovMatchArgs a, const PackedRanges r) {
     __shared__ __attribute__((aligned(16))) unsigned char lds_raw[kCovPackedLdsBytes];
-    const int b = (int)blockIdx.x;
-    if (b < r.blk_begin[1]) cov_match_group_body<3, 5, FUSED>(a, r.desc_begin[0], r.desc_end[0], b - r.blk_begin[0], lds_raw);
-    else if (b < r.blk_begin[2]) cov_match_group_body<2, 6, FUSED>(a, r.desc_begin[1], r.desc_end[1], b - r.blk_begin[1], lds_raw);
-    else if (b < r.blk_begin[3]) { /* retired class, never assigned */ }
-    else if (b < r.blk_begin[4]) cov_match_group_body<1, 6, FUSED>(a, r.desc_begin[3], r.desc_end[3], b - r.blk_begin[3], lds_raw);
-    else cov_match_group_body<0, 3, FUSED>(a, r.desc_begin[4], r.desc_end[4], b - r.blk_begin[4], lds_raw);
+    packed_dispatch(r, [&](auto kc, int desc_begin, int desc_end, int block_in_class) LFR_INLINE_LAMBDA {
+        cov_match_group_body<decltype(kc)::value, FUSED>(a, desc_begin, desc_end, block_in_class, lds_raw);
+    });
 }
 
 // ---- workgroup classes ----
@@ -533,22 +516,17 @@ int lfr_batch_covariance(lfr_batch *b, void *cov_device, int flags, void *hip_st
     lfr::PassState &s = *b->cov;
     if (b->n_graph_nodes) HIP_TRY(hipMemsetAsync(cov_device, 0, 3 * (size_t)b->n_graph_nodes * (f64 ? 8 : 4), st));
     {   // packed classes: one launch of one-wave blocks, dealt as lfr_batch_solve deals its own
-        PackedRanges r;
-        int nb = 0;
-        lfr::packed_ranges(b, 1, &r, &nb);
         CovArgs a;
         memset(&a, 0, sizeof(a));
         a.k.descs = b->d_descs; a.k.edges = b->d_edges; a.k.node_ids = b->d_node_ids; a.k.positions = b->d_positions; a.k.infos = b->d_infos;
         a.k.tukey_variant = b->tukey_variant; a.k.edge_ref = b->d_edge_ref; a.k.edge_word = b->d_edge_word;
         a.cov = cov_device; a.status = s.d_status; a.f64 = f64;
-        if (nb > 0) {
-            if (b->fused) {                  // the packed records have not been written yet: gather from the graph's arrays, as the solve did
-                const lfr::DevGraph &dgr = *b->dev_hold->graph;
-                a.k.f_row = dgr.flow_row; a.k.f_disp1 = dgr.disp1; a.k.f_disp2 = dgr.disp2; a.k.f_sim = dgr.sim;
-                hipLaunchKernelGGL(covariance_packed_kernel<true>, dim3(nb), dim3(64), 0, st, a, r);
-            } else {
-                hipLaunchKernelGGL(covariance_packed_kernel<false>, dim3(nb), dim3(64), 0, st, a, r);
-            }
+        if (b->fused) {                      // the packed records have not been written yet: gather from the graph's arrays, as the solve did
+            const lfr::DevGraph &dgr = *b->dev_hold->graph;
+            a.k.f_row = dgr.flow_row; a.k.f_disp1 = dgr.disp1; a.k.f_disp2 = dgr.disp2; a.k.f_sim = dgr.sim;
+            lfr::launch_packed_pass(b, covariance_packed_kernel<true>, a, st);
+        } else {
+            lfr::launch_packed_pass(b, covariance_packed_kernel<false>, a, st);
         }
     }
     CovBlockArgs c;
@@ -614,23 +592,18 @@ int lfr_batch_covariance_matches(lfr_batch *b, void *cov_device, void *cross_dev
     MatchOut mo;
     mo.eid = lfr::edge_map(b); mo.cross = cross_device; mo.rel = rel_device; mo.n_matches = (uint32_t)M; mo.f64 = f64;
     {   // packed classes: one launch of one-wave blocks, dealt as lfr_batch_covariance deals its own
-        PackedRanges r;
-        int nb = 0;
-        lfr::packed_ranges(b, 1, &r, &nb);
         CovMatchArgs a;
         memset(&a, 0, sizeof(a));
         a.c.k.descs = b->d_descs; a.c.k.edges = b->d_edges; a.c.k.node_ids = b->d_node_ids; a.c.k.positions = b->d_positions; a.c.k.infos = b->d_infos;
         a.c.k.tukey_variant = b->tukey_variant; a.c.k.edge_ref = b->d_edge_ref; a.c.k.edge_word = b->d_edge_word;
         a.c.cov = cov_device; a.c.status = s.d_status; a.c.f64 = f64;
         a.m = mo;
-        if (nb > 0) {
-            if (b->fused) {                  // the packed records have not been written yet: flows and words from the graph's arrays, as the solve did
-                const lfr::DevGraph &dgr = *b->dev_hold->graph;
-                a.c.k.f_row = dgr.flow_row; a.c.k.f_disp1 = dgr.disp1; a.c.k.f_disp2 = dgr.disp2; a.c.k.f_sim = dgr.sim;
-                hipLaunchKernelGGL(covariance_matches_packed_kernel<true>, dim3(nb), dim3(64), 0, st, a, r);
-            } else {
-                hipLaunchKernelGGL(covariance_matches_packed_kernel<false>, dim3(nb), dim3(64), 0, st, a, r);
-            }
+        if (b->fused) {                      // the packed records have not been written yet: flows and words from the graph's arrays, as the solve did
+            const lfr::DevGraph &dgr = *b->dev_hold->graph;
+            a.c.k.f_row = dgr.flow_row; a.c.k.f_disp1 = dgr.disp1; a.c.k.f_disp2 = dgr.disp2; a.c.k.f_sim = dgr.sim;
+            lfr::launch_packed_pass(b, covariance_matches_packed_kernel<true>, a, st);
+        } else {
+            lfr::launch_packed_pass(b, covariance_matches_packed_kernel<false>, a, st);
         }
     }
     CovMatchBlockArgs c;
@@ -666,16 +639,16 @@ int lfr_batch_covariance_matches(lfr_batch *b, void *cov_device, void *cross_dev
 int64_t lfr_batch_covariance_status(lfr_batch *b, int32_t *status) { return lfr::pass_status(b, b ? b->cov : nullptr, "covariance", status); }
 
 int lfr_debug_invert_spd(int device, int solver, int64_t n_sys, const int32_t *n_rows, const double *A, double *Cinv, int32_t *status) {
-    static const int kLimit[4] = {8, 16, 24, 32};
-    static const int kGroups[4] = {8, 4, 2, 1};
+    static const int kClass[4] = {lfr::KC_G8, lfr::KC_G16, lfr::KC_G64_2, lfr::KC_G64_4};      // `solver`: the live packed classes in enum order
     if (solver < 0 || solver > 3 || n_sys < 0 || n_sys > (1 << 24) || (n_sys > 0 && (!n_rows || !A || !Cinv || !status))) {
         lfr::set_error("bad argument"); return LFR_ERR_ARG;
     }
+    const lfr::PackedClassDef &pc = lfr::kPackedClass[kClass[solver]];
     std::vector<int64_t> off((size_t)n_sys);
     int64_t n_tri = 0;
     for (int64_t s = 0; s < n_sys; ++s) {
         const int n = n_rows[s];
-        if (n < 0 || n > kLimit[solver] || (n & 1)) { lfr::set_error("n_rows[%lld] = %d: not an even row count the solver takes", (long long)s, n); return LFR_ERR_ARG; }
+        if (n < 0 || n > pc.max_rows || (n & 1)) { lfr::set_error("n_rows[%lld] = %d: not an even row count the solver takes", (long long)s, n); return LFR_ERR_ARG; }
         off[s] = n_tri;
         n_tri += (int64_t)n * (n + 1) / 2;
     }
@@ -693,12 +666,12 @@ int lfr_debug_invert_spd(int device, int solver, int64_t n_sys, const int32_t *n
     HIP_TRY(hipMemcpyAsync(d_rows, n_rows, 4 * (size_t)n_sys, hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemcpyAsync(d_off, off.data(), 8 * (size_t)n_sys, hipMemcpyHostToDevice, st));
     if (n_tri) HIP_TRY(hipMemcpyAsync(d_A, A, 8 * (size_t)n_tri, hipMemcpyHostToDevice, st));
-    const dim3 grid((unsigned)((n_sys + kGroups[solver] - 1) / kGroups[solver]));
+    const dim3 grid((unsigned)((n_sys + pc.G() - 1) / pc.G()));
     switch (solver) {
-        case 0: hipLaunchKernelGGL(debug_invert_kernel<0>, grid, dim3(64), 0, st, n_sys, d_rows, d_off, d_A, d_C, d_status); break;
-        case 1: hipLaunchKernelGGL(debug_invert_kernel<1>, grid, dim3(64), 0, st, n_sys, d_rows, d_off, d_A, d_C, d_status); break;
-        case 2: hipLaunchKernelGGL(debug_invert_kernel<2>, grid, dim3(64), 0, st, n_sys, d_rows, d_off, d_A, d_C, d_status); break;
-        default: hipLaunchKernelGGL(debug_invert_kernel<3>, grid, dim3(64), 0, st, n_sys, d_rows, d_off, d_A, d_C, d_status); break;
+        case 0: hipLaunchKernelGGL(debug_invert_kernel<lfr::KC_G8>, grid, dim3(64), 0, st, n_sys, d_rows, d_off, d_A, d_C, d_status); break;
+        case 1: hipLaunchKernelGGL(debug_invert_kernel<lfr::KC_G16>, grid, dim3(64), 0, st, n_sys, d_rows, d_off, d_A, d_C, d_status); break;
+        case 2: hipLaunchKernelGGL(debug_invert_kernel<lfr::KC_G64_2>, grid, dim3(64), 0, st, n_sys, d_rows, d_off, d_A, d_C, d_status); break;
+        default: hipLaunchKernelGGL(debug_invert_kernel<lfr::KC_G64_4>, grid, dim3(64), 0, st, n_sys, d_rows, d_off, d_A, d_C, d_status); break;
     }
     HIP_TRY(hipGetLastError());
     if (n_tri) HIP_TRY(hipMemcpyAsync(Cinv, d_C, 8 * (size_t)n_tri, hipMemcpyDeviceToHost, st));

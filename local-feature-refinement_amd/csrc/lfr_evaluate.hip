@@ -29,6 +29,7 @@
 
 #include "lfr_batch.hpp"
 #include "lfr_device.hpp"
+#include "lfr_packed_frame.hpp"
 
 using namespace lfrdev;
 using lfr::CompDesc;
@@ -128,24 +129,20 @@ struct alignas(16) EvalLds {
     double x[NV + 2];          // positions; slots 2*n_var, 2*n_var+1 stay 0 (constants)
     double g[NV + 2];          // dF/dx
 };
+constexpr size_t kEvalPackedLdsBytes = PackedClass<lfr::KC_G8>::G * sizeof(EvalLds<PackedClass<lfr::KC_G8>::NV>);
 
-template <int CLS, int EPL>
+template <int KC>
 __device__ __forceinline__ void eval_group_body(const EvalArgs &a, const int desc_begin, const int desc_end, const int block_in_class,
                                                 unsigned char *lds_raw) {
-    constexpr int NV = CLS == 0 ? 8 : CLS == 1 ? 16 : 32, LPR = CLS == 3 ? 2 : 1;
-    constexpr int S = NV * LPR, G = 64 / S;
-    const int lane = threadIdx.x & 63;
-    const int gid = lane / S, sl = lane % S;
-    const int ci0 = desc_begin + block_in_class * G;
-    if (ci0 >= desc_end) return;                      // wave-uniform
-    const int ci = ci0 + gid;
-    const bool have = ci < desc_end;
-    EvalLds<NV> &L = reinterpret_cast<EvalLds<NV> *>(lds_raw)[gid];
+    constexpr int NV = PackedClass<KC>::NV, S = PackedClass<KC>::S, EPL = PackedClass<KC>::EPL;
+    PackedGroup<KC> grp;
+    if (!grp.init(a.descs, desc_begin, desc_end, block_in_class)) return;
+    const int sl = grp.sl, ci = grp.ci, n_var = grp.n_var, nv2 = grp.nv2, E = grp.E;
+    const bool have = grp.have;
+    const CompDesc &d = grp.d;
+    static_assert(PackedClass<KC>::G * sizeof(EvalLds<NV>) <= kEvalPackedLdsBytes, "LDS budget");
+    EvalLds<NV> &L = reinterpret_cast<EvalLds<NV> *>(lds_raw)[grp.gid];
 
-    CompDesc d;
-    d.edge_off = 0; d.n_edges = 0; d.node_off = 0; d.n_nodes = 0; d.n_var = 0;
-    if (have) d = a.descs[ci];
-    const int n_var = min((int)d.n_var, NV / 2), nv2 = 2 * n_var, E = min((int)d.n_edges, S * EPL);      // (the class limits: classify())
     for (int i = sl; i < NV + 2; i += S) {
         L.x[i] = (i < nv2) ? a.positions[2 * (size_t)a.node_ids[d.node_off + (i >> 1)] + (i & 1)] : 0.0;
         L.g[i] = 0.0;
@@ -176,18 +173,12 @@ __device__ __forceinline__ void eval_group_body(const EvalArgs &a, const int des
     if (a.grad && sl < nv2) a.grad[2 * (size_t)a.node_ids[d.node_off + (sl >> 1)] + (sl & 1)] = L.g[sl];
 }
 
-constexpr size_t kEvalPackedLdsBytes = 8 * sizeof(EvalLds<8>);
-static_assert(kEvalPackedLdsBytes >= 4 * sizeof(EvalLds<16>) && kEvalPackedLdsBytes >= 2 * sizeof(EvalLds<32>), "LDS budget");
-
 // all packed classes in ONE launch, the blocks dealt to the classes as in solve_packed_kernel
 __global__ __launch_bounds__(64) void evaluate_packed_kernel(const EvalArgs a, const PackedRanges r) {
     __shared__ __attribute__((aligned(16))) unsigned char lds_raw[kEvalPackedLdsBytes];
-    const int b = (int)blockIdx.x;
-    if (b < r.blk_begin[1]) eval_group_body<3, 5>(a, r.desc_begin[0], r.desc_end[0], b - r.blk_begin[0], lds_raw);
-    else if (b < r.blk_begin[2]) eval_group_body<2, 6>(a, r.desc_begin[1], r.desc_end[1], b - r.blk_begin[1], lds_raw);
-    else if (b < r.blk_begin[3]) { /* retired class, never assigned */ }
-    else if (b < r.blk_begin[4]) eval_group_body<1, 6>(a, r.desc_begin[3], r.desc_end[3], b - r.blk_begin[3], lds_raw);
-    else eval_group_body<0, 3>(a, r.desc_begin[4], r.desc_end[4], b - r.blk_begin[4], lds_raw);
+    packed_dispatch(r, [&](auto kc, int desc_begin, int desc_end, int block_in_class) LFR_INLINE_LAMBDA {
+        eval_group_body<decltype(kc)::value>(a, desc_begin, desc_end, block_in_class, lds_raw);
+    });
 }
 
 // ---- workgroup classes ----
@@ -205,9 +196,7 @@ __global__ __launch_bounds__(T) void evaluate_block_kernel(const EvalArgs a) {
         const lfr::NodeInc ni = a.node_inc[d.node_off + l];
         const double xr = xof(l, 0), xc = xof(l, 1);
         double g0 = 0.0, g1 = 0.0;
-        for (uint32_t k = 0; k < ni.out_count; ++k) {         // l -> m
-            const uint32_t p = ni.out_begin + k;
-            if (p >= ne) break;                               // (cannot happen: a run lies inside its component)
+        for_out_records(ni, ne, [&](const uint32_t p) {       // l -> m
             float fl[18]; float sm; uint32_t pk;
             load_packed_edge<false>(a, d.edge_off + p, fl, sm, pk);
             const int m = (int)((pk >> 16) & 0x7fffu), kind = (int)(pk >> 31);
@@ -216,19 +205,16 @@ __global__ __launch_bounds__(T) void evaluate_block_kernel(const EvalArgs a) {
             cost += o.term;
             g0 += o.gs0; g1 += o.gs1;
             if (a.eid) eval_store_match(a, a.eid[d.edge_off + p], o);
-        }
+        });
         if (!a.grad || l >= nv) continue;
-        for (uint32_t k = 0; k < ni.in_count; ++k) {          // m -> l
-            if (ni.in_begin + k >= ne) break;
-            const uint32_t p = a.in_idx[d.edge_off + ni.in_begin + k];
-            if (p >= ne) break;
+        for_in_records(ni, a.in_idx, d.edge_off, ne, [&](const uint32_t p) {      // m -> l
             float fl[18]; float sm; uint32_t pk;
             load_packed_edge<false>(a, d.edge_off + p, fl, sm, pk);
             const int m = (int)(pk & 0xffffu), kind = (int)(pk >> 31);
             EvalEdge o;
             eval_block(fl, sm, kind, a.tukey_variant, xof(m, 0), xof(m, 1), xr, xc, o);
             g0 += o.gd0; g1 += o.gd1;
-        }
+        });
         a.grad[2 * (size_t)ids[l]] = g0; a.grad[2 * (size_t)ids[l] + 1] = g1;
     }
     // the cost: a butterfly inside each wave, then the waves in order
@@ -360,24 +346,18 @@ __device__ __forceinline__ void vjp_store_match(const VjpArgs &a, const uint32_t
 }
 
 // ---- packed classes: eval_group_body's layout, the position gradient accumulated in the group's LDS in the same order ----
-template <int CLS, int EPL>
+template <int KC>
 __device__ __forceinline__ void vjp_group_body(const VjpArgs &a, const int desc_begin, const int desc_end, const int block_in_class,
                                                unsigned char *lds_raw) {
-    constexpr int NV = CLS == 0 ? 8 : CLS == 1 ? 16 : 32, LPR = CLS == 3 ? 2 : 1;
-    constexpr int S = NV * LPR, G = 64 / S;
-    const int lane = threadIdx.x & 63;
-    const int gid = lane / S, sl = lane % S;
-    const int ci0 = desc_begin + block_in_class * G;
-    if (ci0 >= desc_end) return;                      // wave-uniform
-    const int ci = ci0 + gid;
-    const bool have = ci < desc_end;
-    EvalLds<NV> &L = reinterpret_cast<EvalLds<NV> *>(lds_raw)[gid];
+    constexpr int NV = PackedClass<KC>::NV, S = PackedClass<KC>::S, EPL = PackedClass<KC>::EPL;
+    PackedGroup<KC> grp;
+    if (!grp.init(a.descs, desc_begin, desc_end, block_in_class)) return;
+    const int sl = grp.sl, ci = grp.ci, n_var = grp.n_var, nv2 = grp.nv2, E = grp.E;
+    const CompDesc &d = grp.d;
+    static_assert(PackedClass<KC>::G * sizeof(EvalLds<NV>) <= kEvalPackedLdsBytes, "LDS budget");
+    EvalLds<NV> &L = reinterpret_cast<EvalLds<NV> *>(lds_raw)[grp.gid];
 
-    CompDesc d;
-    d.edge_off = 0; d.n_edges = 0; d.node_off = 0; d.n_nodes = 0; d.n_var = 0;
-    if (have) d = a.descs[ci];
-    const double cbar = (have && a.cbar) ? a.cbar[ci] : 0.0;                                              // one address per group
-    const int n_var = min((int)d.n_var, NV / 2), nv2 = 2 * n_var, E = min((int)d.n_edges, S * EPL);      // (the class limits: classify())
+    const double cbar = (grp.have && a.cbar) ? a.cbar[ci] : 0.0;                                          // one address per group
     for (int i = sl; i < NV + 2; i += S) {
         L.x[i] = (i < nv2) ? a.positions[2 * (size_t)a.node_ids[d.node_off + (i >> 1)] + (i & 1)] : 0.0;
         L.g[i] = 0.0;
@@ -414,12 +394,9 @@ __device__ __forceinline__ void vjp_group_body(const VjpArgs &a, const int desc_
 // all packed classes in ONE launch, the blocks dealt to the classes as in evaluate_packed_kernel
 __global__ __launch_bounds__(64) void evaluate_vjp_packed_kernel(const VjpArgs a, const PackedRanges r) {
     __shared__ __attribute__((aligned(16))) unsigned char lds_raw[kEvalPackedLdsBytes];
-    const int b = (int)blockIdx.x;
-    if (b < r.blk_begin[1]) vjp_group_body<3, 5>(a, r.desc_begin[0], r.desc_end[0], b - r.blk_begin[0], lds_raw);
-    else if (b < r.blk_begin[2]) vjp_group_body<2, 6>(a, r.desc_begin[1], r.desc_end[1], b - r.blk_begin[1], lds_raw);
-    else if (b < r.blk_begin[3]) { /* retired class, never assigned */ }
-    else if (b < r.blk_begin[4]) vjp_group_body<1, 6>(a, r.desc_begin[3], r.desc_end[3], b - r.blk_begin[3], lds_raw);
-    else vjp_group_body<0, 3>(a, r.desc_begin[4], r.desc_end[4], b - r.blk_begin[4], lds_raw);
+    packed_dispatch(r, [&](auto kc, int desc_begin, int desc_end, int block_in_class) LFR_INLINE_LAMBDA {
+        vjp_group_body<decltype(kc)::value>(a, desc_begin, desc_end, block_in_class, lds_raw);
+    });
 }
 
 // ---- workgroup classes: evaluate_block_kernel's walk.  The out-edge visit forms q, stores the record's per-match outputs and adds
@@ -438,11 +415,9 @@ __global__ __launch_bounds__(T) void evaluate_vjp_block_kernel(const VjpArgs a) 
         const lfr::NodeInc ni = a.node_inc[d.node_off + l];
         const double xr = xof(l, 0), xc = xof(l, 1);
         double g0 = 0.0, g1 = 0.0;
-        for (uint32_t k = 0; k < ni.out_count; ++k) {         // l -> m
-            const uint32_t p = ni.out_begin + k;
-            if (p >= ne) break;                               // (cannot happen: a run lies inside its component)
+        for_out_records(ni, ne, [&](const uint32_t p) {       // l -> m
             const uint32_t id = a.eid ? a.eid[d.edge_off + p] : 0u;
-            if (id >= a.n_dir && a.eid) continue;             // (cannot happen: every record maps to an edge of the graph)
+            if (id >= a.n_dir && a.eid) return;               // (cannot happen: every record maps to an edge of the graph)
             float fl[18]; float sm; uint32_t pk;
             load_packed_edge<false>(a, d.edge_off + p, fl, sm, pk);
             const int m = (int)((pk >> 16) & 0x7fffu), kind = (int)(pk >> 31);
@@ -453,14 +428,11 @@ __global__ __launch_bounds__(T) void evaluate_vjp_block_kernel(const VjpArgs a) 
             bad |= !(isfinite(q0) && isfinite(q1));
             g0 -= o.p00 * q0 + o.p10 * q1; g1 -= o.p01 * q0 + o.p11 * q1;
             if (a.eid) vjp_store_match(a, id, o, q0, q1, cbar);
-        }
+        });
         if (!a.grad || l >= nv) continue;
-        for (uint32_t k = 0; k < ni.in_count; ++k) {          // m -> l
-            if (ni.in_begin + k >= ne) break;
-            const uint32_t p = a.in_idx[d.edge_off + ni.in_begin + k];
-            if (p >= ne) break;
+        for_in_records(ni, a.in_idx, d.edge_off, ne, [&](const uint32_t p) {      // m -> l
             const uint32_t id = a.eid ? a.eid[d.edge_off + p] : 0u;
-            if (id >= a.n_dir && a.eid) continue;
+            if (id >= a.n_dir && a.eid) return;
             float fl[18]; float sm; uint32_t pk;
             load_packed_edge<false>(a, d.edge_off + p, fl, sm, pk);
             const int m = (int)(pk & 0xffffu), kind = (int)(pk >> 31);
@@ -469,7 +441,7 @@ __global__ __launch_bounds__(T) void evaluate_vjp_block_kernel(const VjpArgs a) 
             double q0, q1;
             vjp_q(a, o, cbar, id, q0, q1);
             g0 += q0; g1 += q1;
-        }
+        });
         a.grad[2 * (size_t)ids[l]] = g0; a.grad[2 * (size_t)ids[l] + 1] = g1;
     }
     if (bad) a.bad[di] = 1u;
@@ -491,23 +463,19 @@ __global__ void k_eval_fill_minus_one(size_t n, void *out, int f64) {
 }
 
 // the shared state of a pass (events, latest stream: lfr_batch.hpp) + a cost per descriptor for calls without cost_device.  Set up by
-// this unit, not by pass_begin: the evaluate needs neither a solve nor unchanged inputs, and no workspace for matrices.
+// pass_setup_unsolved, not by pass_begin: the evaluate needs neither a solve nor unchanged inputs, and no workspace for matrices.
 struct EvalState : lfr::PassState {
     double *d_cost = nullptr;
     std::vector<double> h_cost;
 };
 
-int eval_setup(lfr_batch *b) {
-    std::unique_ptr<lfr::PassState, void (*)(lfr::PassState *)> guard(new EvalState(), lfr::pass_free);      // every error path releases slab and events
-    EvalState *s = static_cast<EvalState *>(guard.get());
-    const size_t nd = std::max<size_t>((size_t)b->n_desc, 1);
-    if (!s->slab.init(b->ctx, 8 * nd + 4096)) return LFR_ERR_NOMEM;
-    s->d_cost = s->slab.take_n<double>(nd);
+int eval_carve(lfr_batch *b, lfr::PassState *ps) {
+    EvalState *s = static_cast<EvalState *>(ps);
+    s->d_cost = s->slab.take_n<double>(std::max<size_t>((size_t)b->n_desc, 1));
     if (!s->d_cost) { lfr::set_error("evaluate slab exhausted"); return LFR_ERR_NOMEM; }
-    HIP_TRY(hipEventCreate(&s->ev0)); HIP_TRY(hipEventCreate(&s->ev1));
-    b->eval = guard.release();
     return LFR_OK;
 }
+const lfr::PassKind kEvaluate = {"evaluate", [] { return static_cast<lfr::PassState *>(new EvalState()); }, eval_carve};
 
 // lfr_batch_evaluate_vjp's own pass state (its events order lfr_batch_set_inputs behind it): the similarity term per directed edge
 // and the non-finite mark per descriptor
@@ -517,18 +485,14 @@ struct VjpState : lfr::PassState {
     std::vector<uint32_t> h_bad;
 };
 
-int vjp_setup(lfr_batch *b) {
-    std::unique_ptr<lfr::PassState, void (*)(lfr::PassState *)> guard(new VjpState(), lfr::pass_free);      // every error path releases slab and events
-    VjpState *s = static_cast<VjpState *>(guard.get());
-    const size_t nd = std::max<size_t>((size_t)b->n_desc, 1), nm = std::max<size_t>((size_t)b->n_graph_matches, 1);
-    if (!s->slab.init(b->ctx, 16 * nm + 4 * nd + 4096)) return LFR_ERR_NOMEM;
-    s->d_gsim = s->slab.take_n<double>(2 * nm);
-    s->d_bad = s->slab.take_n<uint32_t>(nd);
+int vjp_carve(lfr_batch *b, lfr::PassState *ps) {
+    VjpState *s = static_cast<VjpState *>(ps);
+    s->d_gsim = s->slab.take_n<double>(2 * std::max<size_t>((size_t)b->n_graph_matches, 1));
+    s->d_bad = s->slab.take_n<uint32_t>(std::max<size_t>((size_t)b->n_desc, 1));
     if (!s->d_gsim || !s->d_bad) { lfr::set_error("evaluate_vjp slab exhausted"); return LFR_ERR_NOMEM; }
-    HIP_TRY(hipEventCreate(&s->ev0)); HIP_TRY(hipEventCreate(&s->ev1));
-    b->evjp = guard.release();
     return LFR_OK;
 }
+const lfr::PassKind kEvaluateVjp = {"evaluate_vjp", [] { return static_cast<lfr::PassState *>(new VjpState()); }, vjp_carve};
 
 }  // namespace
 
@@ -551,7 +515,10 @@ int lfr_batch_evaluate(lfr_batch *b, const double *positions_device, double *cos
     }
     HIP_TRY(hipSetDevice(b->device));
     if (per_match) { const int rc = lfr::ensure_edge_map(b); if (rc != LFR_OK) return rc; }
-    if (!b->eval) { const int rc = eval_setup(b); if (rc != LFR_OK) return rc; }
+    if (!b->eval) {
+        const int rc = lfr::pass_setup_unsolved(b, &b->eval, kEvaluate, 8 * std::max<size_t>((size_t)b->n_desc, 1) + 4096);
+        if (rc != LFR_OK) return rc;
+    }
     EvalState &s = *static_cast<EvalState *>(b->eval);
     hipStream_t st = (hipStream_t)hip_stream;
     const int f64 = (flags & LFR_EVALUATE_F64) ? 1 : 0;
@@ -569,31 +536,18 @@ int lfr_batch_evaluate(lfr_batch *b, const double *positions_device, double *cos
     a.cost = cost_device ? cost_device : s.d_cost;
     a.grad = grad_positions_device; a.res = residuals_device; a.wts = weights_device;
     a.n_dir = (uint32_t)(2 * M); a.tukey_variant = b->tukey_variant; a.f64 = f64;
-    {   // packed classes: one launch of one-wave blocks, dealt as lfr_batch_solve deals its own
-        PackedRanges r;
-        int nb = 0;
-        lfr::packed_ranges(b, 1, &r, &nb);
-        if (nb > 0) hipLaunchKernelGGL(evaluate_packed_kernel, dim3(nb), dim3(64), 0, st, a, r);
-    }
-    {   // workgroup classes: one workgroup per component, all classes in one launch (they are contiguous in the batch order)
-        a.desc_begin = b->class_begin[lfr::KC_BLOCK];
-        const int n = b->class_begin[lfr::KC_COUNT] - a.desc_begin;
-        if (n > 0) hipLaunchKernelGGL((evaluate_block_kernel<kEvalThreads>), dim3(n), dim3(kEvalThreads), 0, st, a);
-    }
+    lfr::launch_two_layouts(b, evaluate_packed_kernel, evaluate_block_kernel<kEvalThreads>, kEvalThreads, a, st);
     HIP_TRY(hipGetLastError());
     { const int rc = lfr::pass_end(&s, st); if (rc != LFR_OK) return rc; }
     if (stats) {
         memset(stats, 0, sizeof(*stats));
         s.h_cost.assign((size_t)b->n_desc, 0.0);
         if (b->n_desc) HIP_TRY(hipMemcpyAsync(s.h_cost.data(), a.cost, 8 * (size_t)b->n_desc, hipMemcpyDeviceToHost, st));
-        HIP_TRY(lfr::stream_wait(st));
+        { const int rc = lfr::pass_wait_ms(&s, st, &stats->kernel_ms); if (rc != LFR_OK) return rc; }
         for (const double c : s.h_cost) {
             if (std::isfinite(c)) stats->sum_cost += c; else ++stats->n_nonfinite;
         }
         stats->n_components = b->n_desc;
-        float ms = 0.f;
-        HIP_TRY(hipEventElapsedTime(&ms, s.ev0, s.ev1));
-        stats->kernel_ms = ms;
     }
     return LFR_OK;
 }
@@ -621,7 +575,11 @@ int lfr_batch_evaluate_vjp(lfr_batch *b, const double *positions_device, const d
     }
     HIP_TRY(hipSetDevice(b->device));
     if (per_match) { const int rc = lfr::ensure_edge_map(b); if (rc != LFR_OK) return rc; }
-    if (!b->evjp) { const int rc = vjp_setup(b); if (rc != LFR_OK) return rc; }
+    if (!b->evjp) {
+        const size_t nd = std::max<size_t>((size_t)b->n_desc, 1), nm = std::max<size_t>((size_t)b->n_graph_matches, 1);
+        const int rc = lfr::pass_setup_unsolved(b, &b->evjp, kEvaluateVjp, 16 * nm + 4 * nd + 4096);
+        if (rc != LFR_OK) return rc;
+    }
     VjpState &s = *static_cast<VjpState *>(b->evjp);
     hipStream_t st = (hipStream_t)hip_stream;
     const int f64 = (flags & LFR_EVALUATE_F64) ? 1 : 0;
@@ -647,17 +605,7 @@ int lfr_batch_evaluate_vjp(lfr_batch *b, const double *positions_device, const d
     a.bad = s.d_bad;
     a.n_dir = (uint32_t)(2 * M); a.tukey_variant = b->tukey_variant; a.f64 = f64;
     a.wide = (((uintptr_t)grad_disp1_device | (uintptr_t)grad_disp2_device) & (f64 ? 15u : 7u)) == 0;       // (a row is 144 / 72 bytes)
-    {   // packed classes: one launch of one-wave blocks, dealt as lfr_batch_evaluate deals its own
-        PackedRanges r;
-        int nb = 0;
-        lfr::packed_ranges(b, 1, &r, &nb);
-        if (nb > 0) hipLaunchKernelGGL(evaluate_vjp_packed_kernel, dim3(nb), dim3(64), 0, st, a, r);
-    }
-    {   // workgroup classes: one workgroup per component, all classes in one launch (they are contiguous in the batch order)
-        a.desc_begin = b->class_begin[lfr::KC_BLOCK];
-        const int n = b->class_begin[lfr::KC_COUNT] - a.desc_begin;
-        if (n > 0) hipLaunchKernelGGL((evaluate_vjp_block_kernel<kEvalThreads>), dim3(n), dim3(kEvalThreads), 0, st, a);
-    }
+    lfr::launch_two_layouts(b, evaluate_vjp_packed_kernel, evaluate_vjp_block_kernel<kEvalThreads>, kEvalThreads, a, st);
     if (grad_sim_device && M) hipLaunchKernelGGL(k_vjp_sim, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, st, (int64_t)M, s.d_gsim, grad_sim_device, f64);
     HIP_TRY(hipGetLastError());
     { const int rc = lfr::pass_end(&s, st); if (rc != LFR_OK) return rc; }
@@ -665,12 +613,9 @@ int lfr_batch_evaluate_vjp(lfr_batch *b, const double *positions_device, const d
         memset(stats, 0, sizeof(*stats));
         s.h_bad.assign((size_t)b->n_desc, 0u);
         if (b->n_desc) HIP_TRY(hipMemcpyAsync(s.h_bad.data(), s.d_bad, 4 * (size_t)b->n_desc, hipMemcpyDeviceToHost, st));
-        HIP_TRY(lfr::stream_wait(st));
+        { const int rc = lfr::pass_wait_ms(&s, st, &stats->kernel_ms); if (rc != LFR_OK) return rc; }
         for (const uint32_t v : s.h_bad) stats->n_nonfinite += v != 0;
         stats->n_components = b->n_desc;
-        float ms = 0.f;
-        HIP_TRY(hipEventElapsedTime(&ms, s.ev0, s.ev1));
-        stats->kernel_ms = ms;
     }
     return LFR_OK;
 }

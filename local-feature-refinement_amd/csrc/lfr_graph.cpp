@@ -582,10 +582,7 @@ int block_max_rows() {
 }
 
 static int classify(int rows, int64_t n_edges) {
-    if (rows <= 8 && n_edges <= 24) return KC_G8;
-    if (rows <= 16 && n_edges <= 96) return KC_G16;
-    if (rows <= 24 && n_edges <= 192) return KC_G64_2;
-    if (rows <= 32 && n_edges <= 320) return KC_G64_4;
+    if (const int packed = classify_packed(rows, n_edges); packed >= 0) return packed;
     const int lds_max = block_max_rows();
     if (rows <= std::min(kBlockRowsS, lds_max)) return KC_BLOCK;
     if (rows <= std::min(kBlockRowsM, lds_max)) return KC_BLOCK_M;

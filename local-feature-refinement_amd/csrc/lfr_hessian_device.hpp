@@ -114,7 +114,7 @@ __host__ __device__ __forceinline__ size_t bwd_tri(int i, int j) { return (size_
 template <int T, bool EXACT, bool BOUNDS = EXACT>
 __device__ __forceinline__ void bwd_assemble(const BwdArgs &a, const CompDesc &d, const int nv, const EdgeRec *E, const uint32_t *ids,
                                              double *H, const uint8_t *fr, const int tid) {
-    // The workgroup classes' records come by source node (out-edges contiguous, NodeInc); the packed classes' in edge-id order: a thread scans them all (<= 320)
+    // The workgroup classes' records come by source node (out-edges contiguous, NodeInc); the packed classes' in edge-id order: a thread scans them all (at most the largest packed class's max_edges)
     auto xof = [&](int m, int c) -> double { return m < nv ? a.positions[2 * (size_t)ids[m] + c] : 0.0; };
     for (int l = tid; l < nv; l += T) {
         lfr::NodeInc ni = a.node_inc[d.node_off + l];

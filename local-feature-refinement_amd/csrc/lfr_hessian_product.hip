@@ -28,6 +28,7 @@
 #include "lfr_batch.hpp"
 #include "lfr_device.hpp"
 #include "lfr_hessian_device.hpp"
+#include "lfr_packed_frame.hpp"
 
 using namespace lfrdev;
 using lfr::CompDesc;
@@ -120,26 +121,20 @@ struct alignas(16) HvpLds {
 };
 
 template <int K>
-constexpr size_t hvp_packed_lds_bytes() { return 8 * sizeof(HvpLds<8, K>); }
+constexpr size_t hvp_packed_lds_bytes() { return PackedClass<lfr::KC_G8>::G * sizeof(HvpLds<PackedClass<lfr::KC_G8>::NV, K>); }
 
-template <int CLS, int EPL, bool EXACT, int K>
+template <int KC, bool EXACT, int K>
 __device__ __forceinline__ void hvp_group_body(const HvpArgs &a, const int desc_begin, const int desc_end, const int block_in_class,
                                                unsigned char *lds_raw) {
-    constexpr int NV = CLS == 0 ? 8 : CLS == 1 ? 16 : 32, LPR = CLS == 3 ? 2 : 1;
-    constexpr int S = NV * LPR, G = 64 / S;
-    static_assert(G * sizeof(HvpLds<NV, K>) <= hvp_packed_lds_bytes<K>(), "LDS budget");
-    const int lane = threadIdx.x & 63;
-    const int gid = lane / S, sl = lane % S;
-    const int ci0 = desc_begin + block_in_class * G;
-    if (ci0 >= desc_end) return;                      // wave-uniform
-    const int ci = ci0 + gid;
-    const bool have = ci < desc_end;
-    HvpLds<NV, K> &L = reinterpret_cast<HvpLds<NV, K> *>(lds_raw)[gid];
+    constexpr int NV = PackedClass<KC>::NV, S = PackedClass<KC>::S, EPL = PackedClass<KC>::EPL;
+    static_assert(PackedClass<KC>::G * sizeof(HvpLds<NV, K>) <= hvp_packed_lds_bytes<K>(), "LDS budget");
+    PackedGroup<KC> grp;
+    if (!grp.init(a.descs, desc_begin, desc_end, block_in_class)) return;
+    const int sl = grp.sl, ci = grp.ci, n_var = grp.n_var, nv2 = grp.nv2, E = grp.E;
+    const bool have = grp.have;
+    const CompDesc &d = grp.d;
+    HvpLds<NV, K> &L = reinterpret_cast<HvpLds<NV, K> *>(lds_raw)[grp.gid];
 
-    CompDesc d;
-    d.edge_off = 0; d.n_edges = 0; d.node_off = 0; d.n_nodes = 0; d.n_var = 0;
-    if (have) d = a.descs[ci];
-    const int n_var = min((int)d.n_var, NV / 2), nv2 = 2 * n_var, E = min((int)d.n_edges, S * EPL);      // (the class limits: classify())
     // lane sl owns coordinate sl of the component (NV <= S): it loads it, and stores its product at the end
     const bool own = sl < nv2;
     const size_t gi = own ? 2 * (size_t)a.node_ids[d.node_off + (sl >> 1)] + (sl & 1) : 0;
@@ -194,12 +189,9 @@ __device__ __forceinline__ void hvp_group_body(const HvpArgs &a, const int desc_
 template <bool EXACT, int K>
 __global__ __launch_bounds__(64) void hessian_product_packed_kernel(const HvpArgs a, const PackedRanges r) {
     __shared__ __attribute__((aligned(16))) unsigned char lds_raw[hvp_packed_lds_bytes<K>()];
-    const int b = (int)blockIdx.x;
-    if (b < r.blk_begin[1]) hvp_group_body<3, 5, EXACT, K>(a, r.desc_begin[0], r.desc_end[0], b - r.blk_begin[0], lds_raw);
-    else if (b < r.blk_begin[2]) hvp_group_body<2, 6, EXACT, K>(a, r.desc_begin[1], r.desc_end[1], b - r.blk_begin[1], lds_raw);
-    else if (b < r.blk_begin[3]) { /* retired class, never assigned */ }
-    else if (b < r.blk_begin[4]) hvp_group_body<1, 6, EXACT, K>(a, r.desc_begin[3], r.desc_end[3], b - r.blk_begin[3], lds_raw);
-    else hvp_group_body<0, 3, EXACT, K>(a, r.desc_begin[4], r.desc_end[4], b - r.blk_begin[4], lds_raw);
+    packed_dispatch(r, [&](auto kc, int desc_begin, int desc_end, int block_in_class) LFR_INLINE_LAMBDA {
+        hvp_group_body<decltype(kc)::value, EXACT, K>(a, desc_begin, desc_end, block_in_class, lds_raw);
+    });
 }
 
 // ---- workgroup classes ----
@@ -235,9 +227,7 @@ __global__ __launch_bounds__(T) void hessian_product_block_kernel(const HvpArgs 
             vl[k][0] = b0 ? 0.0 : raw[k][0]; vl[k][1] = b1 ? 0.0 : raw[k][1];
             acc[k][0] = 0.0; acc[k][1] = 0.0;
         }
-        for (uint32_t j = 0; j < ni.out_count; ++j) {         // l -> m: the source side
-            const uint32_t p = ni.out_begin + j;
-            if (p >= ne) break;                               // (cannot happen: a run lies inside its component)
+        for_out_records(ni, ne, [&](const uint32_t p) {       // l -> m: the source side
             float fl[18]; float sm; uint32_t pk;
             load_packed_edge<false>(a, d.edge_off + p, fl, sm, pk);
             const int m = (int)((pk >> 16) & 0x7fffu), kind = (int)(pk >> 31);
@@ -250,11 +240,8 @@ __global__ __launch_bounds__(T) void hessian_product_block_kernel(const HvpArgs 
                 hvp_apply<EXACT>(h, vl[k][0], vl[k][1], vof(k, m, 0, yr), vof(k, m, 1, yc), hs0, hs1, hd0, hd1);
                 acc[k][0] += hs0; acc[k][1] += hs1;
             }
-        }
-        for (uint32_t j = 0; j < ni.in_count; ++j) {          // m -> l: the destination side
-            if (ni.in_begin + j >= ne) break;
-            const uint32_t p = a.in_idx[d.edge_off + ni.in_begin + j];
-            if (p >= ne) break;
+        });
+        for_in_records(ni, a.in_idx, d.edge_off, ne, [&](const uint32_t p) {      // m -> l: the destination side
             float fl[18]; float sm; uint32_t pk;
             load_packed_edge<false>(a, d.edge_off + p, fl, sm, pk);
             const int m = (int)(pk & 0xffffu), kind = (int)(pk >> 31);
@@ -267,7 +254,7 @@ __global__ __launch_bounds__(T) void hessian_product_block_kernel(const HvpArgs 
                 hvp_apply<EXACT>(h, vof(k, m, 0, yr), vof(k, m, 1, yc), vl[k][0], vl[k][1], hs0, hs1, hd0, hd1);
                 acc[k][0] += hd0; acc[k][1] += hd1;
             }
-        }
+        });
 #pragma unroll
         for (int k = 0; k < K; ++k) {
             const double h0 = b0 ? raw[k][0] : acc[k][0], h1 = b1 ? raw[k][1] : acc[k][1];
@@ -296,18 +283,8 @@ __global__ __launch_bounds__(T) void hessian_product_block_kernel(const HvpArgs 
 }
 
 template <bool EXACT, int K>
-void hvp_launch(const lfr_batch *b, HvpArgs a, hipStream_t st) {
-    {   // packed classes: one launch of one-wave blocks, dealt as lfr_batch_evaluate deals its own
-        PackedRanges r;
-        int nb = 0;
-        lfr::packed_ranges(b, 1, &r, &nb);
-        if (nb > 0) hipLaunchKernelGGL((hessian_product_packed_kernel<EXACT, K>), dim3(nb), dim3(64), 0, st, a, r);
-    }
-    {   // workgroup classes: one workgroup per component, all classes in one launch (they are contiguous in the batch order)
-        a.desc_begin = b->class_begin[lfr::KC_BLOCK];
-        const int n = b->class_begin[lfr::KC_COUNT] - a.desc_begin;
-        if (n > 0) hipLaunchKernelGGL((hessian_product_block_kernel<kHvpThreads, EXACT, K>), dim3(n), dim3(kHvpThreads), 0, st, a);
-    }
+void hvp_launch(const lfr_batch *b, const HvpArgs &a, hipStream_t st) {
+    lfr::launch_two_layouts(b, hessian_product_packed_kernel<EXACT, K>, hessian_product_block_kernel<kHvpThreads, EXACT, K>, kHvpThreads, a, st);
 }
 
 template <bool EXACT>
@@ -322,25 +299,21 @@ void hvp_launch_k(const lfr_batch *b, const HvpArgs &a, int n_vectors, hipStream
 }
 
 // the shared state of a pass (events, latest stream: lfr_batch.hpp) + the non-finite mark per descriptor and the bound-coordinate
-// count.  Set up by this unit, not by pass_begin: the product needs neither a solve nor unchanged inputs, and no workspace for matrices.
+// count.  Set up by pass_setup_unsolved, not by pass_begin: the product needs neither a solve nor unchanged inputs, and no workspace for matrices.
 struct HvpState : lfr::PassState {
     uint32_t *d_bad = nullptr;
     unsigned long long *d_bound = nullptr;
     std::vector<uint32_t> h_bad;
 };
 
-int hvp_setup(lfr_batch *b) {
-    std::unique_ptr<lfr::PassState, void (*)(lfr::PassState *)> guard(new HvpState(), lfr::pass_free);      // every error path releases slab and events
-    HvpState *s = static_cast<HvpState *>(guard.get());
-    const size_t nd = std::max<size_t>((size_t)b->n_desc, 1);
-    if (!s->slab.init(b->ctx, 4 * nd + 8 + 4096)) return LFR_ERR_NOMEM;
+int hvp_carve(lfr_batch *b, lfr::PassState *ps) {
+    HvpState *s = static_cast<HvpState *>(ps);
     s->d_bound = s->slab.take_n<unsigned long long>(1);
-    s->d_bad = s->slab.take_n<uint32_t>(nd);
+    s->d_bad = s->slab.take_n<uint32_t>(std::max<size_t>((size_t)b->n_desc, 1));
     if (!s->d_bound || !s->d_bad) { lfr::set_error("hessian_product slab exhausted"); return LFR_ERR_NOMEM; }
-    HIP_TRY(hipEventCreate(&s->ev0)); HIP_TRY(hipEventCreate(&s->ev1));
-    b->hvp = guard.release();
     return LFR_OK;
 }
+const lfr::PassKind kHessianProduct = {"hessian_product", [] { return static_cast<lfr::PassState *>(new HvpState()); }, hvp_carve};
 
 }  // namespace
 
@@ -364,7 +337,10 @@ int lfr_batch_hessian_product(lfr_batch *b, const double *positions_device, cons
         lfr::set_error("lfr_batch_hessian_product: the batch has not been solved and no positions are given"); return LFR_ERR_ARG;
     }
     HIP_TRY(hipSetDevice(b->device));
-    if (!b->hvp) { const int rc = hvp_setup(b); if (rc != LFR_OK) return rc; }
+    if (!b->hvp) {
+        const int rc = lfr::pass_setup_unsolved(b, &b->hvp, kHessianProduct, 4 * std::max<size_t>((size_t)b->n_desc, 1) + 8 + 4096);
+        if (rc != LFR_OK) return rc;
+    }
     HvpState &s = *static_cast<HvpState *>(b->hvp);
     hipStream_t st = (hipStream_t)hip_stream;
     const size_t N = (size_t)b->n_graph_nodes, nd = (size_t)b->n_desc;
@@ -391,13 +367,10 @@ int lfr_batch_hessian_product(lfr_batch *b, const double *positions_device, cons
         unsigned long long n_bound = 0;
         if (nd) HIP_TRY(hipMemcpyAsync(s.h_bad.data(), s.d_bad, 4 * nd, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipMemcpyAsync(&n_bound, s.d_bound, 8, hipMemcpyDeviceToHost, st));
-        HIP_TRY(lfr::stream_wait(st));
+        { const int rc = lfr::pass_wait_ms(&s, st, &stats->kernel_ms); if (rc != LFR_OK) return rc; }
         for (const uint32_t v : s.h_bad) stats->n_nonfinite += v != 0;
         stats->n_components = b->n_desc;
         stats->n_bound_coordinates = (int64_t)n_bound;
-        float ms = 0.f;
-        HIP_TRY(hipEventElapsedTime(&ms, s.ev0, s.ev1));
-        stats->kernel_ms = ms;
     }
     return LFR_OK;
 }

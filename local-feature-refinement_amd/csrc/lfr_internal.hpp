@@ -117,11 +117,12 @@ static_assert(sizeof(NodeInc) == 16, "NodeInc must be 16 bytes");
 
 // kernel classes
 enum KernelClass : int {
-    KC_G8 = 0,      // packed <NV=8, LPR=1, EPL=3>:  8 comps/wave, <=8 rows,  <=24 edges
-    KC_G16,         // packed <16,1,6>: 4 comps/wave, <=16 rows, <=96 edges (3 slots resident, 3 re-read per sweep)
-    KC_G32,         // retired (was <16,2,3>: 2 comps/wave); kept so that the class indices of the C ABI stay put
-    KC_G64_2,       // packed <32,1,6>: 2 comps/wave, <=24 rows, <=192 edges (2 slots resident, 4 re-read per sweep)
-    KC_G64_4,       // packed <32,2,5>: 1 comp/wave,  <=32 rows, <=320 edges (2 slots resident, 3 re-read per sweep)
+    // packed: 64 / S components per wave64.  Geometry and limits of each: kPackedClass below, the one statement of them
+    KC_G8 = 0,
+    KC_G16,
+    KC_G32,         // retired; kept so that the class indices of the C ABI stay put
+    KC_G64_2,
+    KC_G64_4,
     // workgroup per component, normal matrix in LDS - three classes by LDS footprint so that small systems share a CU:
     KC_BLOCK,       //   <= 88 rows : <= 39.6 KB of LDS, 128 threads -> 4 workgroups per CU
     KC_BLOCK_M,     //   <= 130 rows: <= 79 KB, 256 threads        -> 2 workgroups per CU
@@ -129,7 +130,51 @@ enum KernelClass : int {
     KC_GLOBAL,      // workgroup per component, normal matrix in HBM workspace
     KC_COUNT
 };
-constexpr uint32_t kNoClass = 15;            // sort key of components that are not solved (by this shard)
+// ---- the packed classes, stated once for classify() (lfr_graph.cpp), classify_dev() (lfr_assemble.hip), the launch plan
+// (lfr_batch.hip) and the analysis kernels (lfr_packed_frame.hpp).  A group of S = NV * LPR lanes hosts one component: NV matrix
+// rows (NV / 2 nodes) in LDS, LPR lanes per row, sub-lane sl takes records sl + S k, k < EPL.  A component goes to the first live
+// class, in enum order, whose max_rows and max_edges it fits. ----
+struct PackedClassDef {
+    int NV, LPR, EPL, max_rows, max_edges;
+    bool retired;
+    constexpr int S() const { return NV * LPR; }
+    constexpr int G() const { return 64 / S(); }         // components per wave
+};
+constexpr int kPackedClasses = KC_BLOCK;
+constexpr PackedClassDef kPackedClass[kPackedClasses] = {
+    /* KC_G8    */ {8, 1, 3, 8, 24, false},
+    /* KC_G16   */ {16, 1, 6, 16, 96, false},
+    /* KC_G32   */ {16, 2, 3, 0, 0, true},
+    /* KC_G64_2 */ {32, 1, 6, 24, 192, false},
+    /* KC_G64_4 */ {32, 2, 5, 32, 320, false},
+};
+// the order in which one packed launch deals its blocks to the classes: PackedRanges (lfr_batch.hpp) is indexed by it
+constexpr int kPackedOrder[kPackedClasses] = {KC_G64_4, KC_G64_2, KC_G32, KC_G16, KC_G8};
+constexpr bool packed_table_ok() {
+    int seen = 0, rows = 0, edges = 0;
+    for (int i = 0; i < kPackedClasses; ++i) {
+        const PackedClassDef &c = kPackedClass[i];
+        if (64 % c.S() != 0) return false;
+        if (!c.retired) {
+            // a live class holds what it admits: a lane slot per record, an LDS row per matrix row; the limits grow with the enum
+            if (c.max_edges != c.S() * c.EPL || c.max_rows > c.NV || (c.max_rows & 1)) return false;
+            if (c.max_rows < rows || c.max_edges < edges) return false;
+            rows = c.max_rows; edges = c.max_edges;
+        }
+        if (kPackedOrder[i] < 0 || kPackedOrder[i] >= kPackedClasses) return false;
+        seen |= 1 << kPackedOrder[i];
+    }
+    return seen == (1 << kPackedClasses) - 1;           // the dispatch order names every class once
+}
+static_assert(packed_table_ok(), "packed class table");
+static_assert(KC_G8 == 0 && KC_G64_4 == kPackedClasses - 1 && kPackedClass[KC_G32].retired, "the table is keyed by KC_*");
+// the packed class of a component with `rows` matrix rows and n_edges records, or -1: one of the workgroup classes
+constexpr int classify_packed(int64_t rows, int64_t n_edges) {
+    for (int i = 0; i < kPackedClasses; ++i)
+        if (!kPackedClass[i].retired && rows <= kPackedClass[i].max_rows && n_edges <= kPackedClass[i].max_edges) return i;
+    return -1;
+}
+constexpr uint32_t kNoClass = 15;           // sort key of components that are not solved (by this shard)
 constexpr int kClassBits = 4;
 #ifndef LFR_ROWS_S
 #define LFR_ROWS_S 88

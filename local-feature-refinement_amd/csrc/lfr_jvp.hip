@@ -159,28 +159,22 @@ struct alignas(16) JvpGnLds {
     double b[NV + 2];          // the right-hand side; slots 2*n_var, 2*n_var+1 take the constants' rows (never read)
 };
 
-template <int CLS, int EPL>
+template <int KC>
 __device__ __forceinline__ void jvp_gn_group_body(const JvpArgs &ja, const int desc_begin, const int desc_end, const int block_in_class,
                                                   unsigned char *lds_raw) {
-    constexpr int NV = CLS == 0 ? 8 : CLS == 1 ? 16 : 32, LPR = CLS == 3 ? 2 : 1;
-    constexpr int S = NV * LPR, G = 64 / S, LD = NV + 1;
+    constexpr int NV = PackedClass<KC>::NV, S = PackedClass<KC>::S, EPL = PackedClass<KC>::EPL, LD = NV + 1;
     const BwdArgs &a = ja.h;
-    const int lane = threadIdx.x & 63;
-    const int gid = lane / S, sl = lane % S;
+    PackedGroup<KC> grp;
+    if (!grp.init(a.descs, desc_begin, desc_end, block_in_class)) return;
+    const int gid = grp.gid, sl = grp.sl, ci = grp.ci;
     const int row = sl % NV, part = sl / NV;
-    const int ci0 = desc_begin + block_in_class * G;
-    if (ci0 >= desc_end) return;                      // wave-uniform
-    const int ci = ci0 + gid;
-    const bool have = ci < desc_end;
+    const bool have = grp.have;
+    const CompDesc &d = grp.d;
     JvpGnLds<NV> &B = reinterpret_cast<JvpGnLds<NV> *>(lds_raw)[gid];
     CovLds<NV> &L = B.c;
 
-    CompDesc d;
-    d.edge_off = 0; d.n_edges = 0; d.node_off = 0; d.n_nodes = 0; d.n_var = 0;
-    if (have) d = a.descs[ci];
     const bool usable = have && a.infos[ci].termination != LFR_TERM_FAILURE;
-    // (the class limits, classify(): the clamps keep every LDS index inside the group whatever the descriptor says)
-    const int n_var = usable ? min((int)d.n_var, NV / 2) : 0, nv2 = 2 * n_var, E = usable ? min((int)d.n_edges, S * EPL) : 0;
+    const int n_var = usable ? grp.n_var : 0, nv2 = 2 * n_var, E = usable ? grp.E : 0;     // a group without a usable component inverts the identity
     const bool is_row = row < nv2;
     const int nv2_max = cov_wave_max(nv2);
 
@@ -216,7 +210,7 @@ __device__ __forceinline__ void jvp_gn_group_body(const JvpArgs &ja, const int d
     const double *A = L.A;
     bool solved = false;
     double xd = 0.0;
-    cov_invert<CLS>(row, nv2_max,
+    cov_invert<KC>(row, nv2_max,
         [&](int c) -> double {
             double h = 0.0;
             if (is_row && c < nv2) h = (c <= row ? A[row * LD + c] : A[c * LD + row]);
@@ -245,12 +239,9 @@ static_assert(kJvpGnLdsBytes >= 8 * sizeof(JvpGnLds<8>), "LDS budget");
 // all packed classes in ONE launch, the blocks dealt to the classes as in covariance_packed_kernel
 __global__ __launch_bounds__(64, 2) void jvp_gn_packed_kernel(const JvpArgs a, const PackedRanges r) {
     __shared__ __attribute__((aligned(16))) unsigned char lds_raw[kJvpGnLdsBytes];
-    const int b = (int)blockIdx.x;
-    if (b < r.blk_begin[1]) jvp_gn_group_body<3, 5>(a, r.desc_begin[0], r.desc_end[0], b - r.blk_begin[0], lds_raw);
-    else if (b < r.blk_begin[2]) jvp_gn_group_body<2, 6>(a, r.desc_begin[1], r.desc_end[1], b - r.blk_begin[1], lds_raw);
-    else if (b < r.blk_begin[3]) { /* retired class, never assigned */ }
-    else if (b < r.blk_begin[4]) jvp_gn_group_body<1, 6>(a, r.desc_begin[3], r.desc_end[3], b - r.blk_begin[3], lds_raw);
-    else jvp_gn_group_body<0, 3>(a, r.desc_begin[4], r.desc_end[4], b - r.blk_begin[4], lds_raw);
+    packed_dispatch(r, [&](auto kc, int desc_begin, int desc_end, int block_in_class) LFR_INLINE_LAMBDA {
+        jvp_gn_group_body<decltype(kc)::value>(a, desc_begin, desc_end, block_in_class, lds_raw);
+    });
 }
 
 size_t jvp_lds_bytes(int rows, bool lds_matrix) {             // (backward_kernel's carving)
@@ -320,11 +311,8 @@ int lfr_batch_jvp(lfr_batch *b, const void *tan_disp1_device, const void *tan_di
     // Packed classes (<= 32 rows).  Gauss-Newton mode: ONE launch of one-wave blocks, each wave hosting 64/S = 2-8 components (1 in
     // <32,2>), dealt to the classes as lfr_batch_covariance deals its own.  Exact mode (with or without the fallback): jvp_kernel, one wave per component.
     if (gn) {
-        PackedRanges r;
-        int nb = 0;
-        lfr::packed_ranges(b, 1, &r, &nb);
         a.desc_begin = b->class_begin[0]; a.scan_all = 0;
-        if (nb > 0) hipLaunchKernelGGL(jvp_gn_packed_kernel, dim3(nb), dim3(64), 0, st, ja, r);
+        lfr::launch_packed_pass(b, jvp_gn_packed_kernel, ja, st);
     } else {
         a.desc_begin = b->class_begin[0];
         const int n = b->class_begin[lfr::KC_BLOCK] - a.desc_begin;

@@ -11,6 +11,7 @@
 
 #include "lfr_batch.hpp"
 #include "lfr_device.hpp"
+#include "lfr_packed_frame.hpp"
 
 namespace lfrdev {
 
@@ -65,12 +66,12 @@ struct CovGaussJordan {
     }
 };
 
-// The inversion of a packed class (CLS 0-3 = <8,1>, <16,1>, <32,1>, <32,2>) in the instantiation sized for the largest system of the
-// wave (n_max, wave-uniform): build(c) = the lane's entry of column c, sink(h, ok) takes the lane's row of the inverse; ok = false: a
-// pivot of the lane's group was not positive.  Every lane of the wave must be active.
-template <int CLS, class Build, class Sink>
+// The inversion of packed class KC in the instantiation sized for the largest system of the wave (n_max, wave-uniform, at most the
+// class's max_rows): build(c) = the lane's entry of column c, sink(h, ok) takes the lane's row of the inverse; ok = false: a pivot of
+// the lane's group was not positive.  Every lane of the wave must be active.
+template <int KC, class Build, class Sink>
 __device__ __forceinline__ void cov_invert(const int row, const int n_max, Build &&build, Sink &&sink) {
-    constexpr int NV = CLS == 0 ? 8 : CLS == 1 ? 16 : 32;
+    constexpr int NV = PackedClass<KC>::NV, kRows = PackedClass<KC>::max_rows;
     auto run = [&](auto cl_tag) {
         constexpr int CL = decltype(cl_tag)::value;
         double h[CL];
@@ -81,15 +82,16 @@ __device__ __forceinline__ void cov_invert(const int row, const int n_max, Build
         sink(h, minpiv > 0.0);
     };
 #define LFR_COV_CL(n) run(std::integral_constant<int, n>{})
-    if constexpr (CLS == 0) {
-        if (n_max <= 2) LFR_COV_CL(2); else if (n_max <= 4) LFR_COV_CL(4); else if (n_max <= 6) LFR_COV_CL(6); else LFR_COV_CL(8);
-    } else if constexpr (CLS == 1) {
-        if (n_max <= 10) LFR_COV_CL(10); else if (n_max <= 12) LFR_COV_CL(12); else if (n_max <= 14) LFR_COV_CL(14); else LFR_COV_CL(16);
-    } else if constexpr (CLS == 2) {                   // the class holds <= 24 rows (classify())
-        if (n_max <= 18) LFR_COV_CL(18); else if (n_max <= 20) LFR_COV_CL(20); else if (n_max <= 22) LFR_COV_CL(22); else LFR_COV_CL(24);
+    if constexpr (KC == lfr::KC_G8) {
+        if (n_max <= 2) LFR_COV_CL(2); else if (n_max <= 4) LFR_COV_CL(4); else if (n_max <= 6) LFR_COV_CL(6); else LFR_COV_CL(kRows);
+    } else if constexpr (KC == lfr::KC_G16) {
+        if (n_max <= 10) LFR_COV_CL(10); else if (n_max <= 12) LFR_COV_CL(12); else if (n_max <= 14) LFR_COV_CL(14); else LFR_COV_CL(kRows);
+    } else if constexpr (KC == lfr::KC_G64_2) {
+        if (n_max <= 18) LFR_COV_CL(18); else if (n_max <= 20) LFR_COV_CL(20); else if (n_max <= 22) LFR_COV_CL(22); else LFR_COV_CL(kRows);
     } else {
+        static_assert(KC == lfr::KC_G64_4, "one ladder per live class");
         if (n_max <= 20) LFR_COV_CL(20); else if (n_max <= 26) LFR_COV_CL(26); else if (n_max <= 28) LFR_COV_CL(28);
-        else if (n_max <= 30) LFR_COV_CL(30); else LFR_COV_CL(32);
+        else if (n_max <= 30) LFR_COV_CL(30); else LFR_COV_CL(kRows);
     }
 #undef LFR_COV_CL
 }

@@ -9,8 +9,9 @@ n - 1 pairs are a path, so any m >= n - 1 is connected - then the chords by ring
 complete track, m = n the ring.  The d duplicates repeat the first d matches (the reference keeps duplicates, solve.cc:476-478).
 Sigmas are the defaults of `tracks()`: easy problems whose trajectories do not hang on a rounding.
 
-Edge slots of the packed classes (solve_group_body<NV, LPR, EPL> in lfr_solve.hip: S = NV * LPR lanes per group, edge e of a
-component sits in lane e % S, slot e / S; the first RES slots stay in registers, the others are re-read from memory by every sweep):
+Edge slots of the packed classes (<NV, LPR, EPL> and the limits are the rows of kPackedClass in lfr_internal.hpp, the one statement
+of them: S = NV * LPR lanes per group, edge e of a component sits in lane e % S, slot e / S; in the forward solve_group_body the first
+RES slots stay in registers, the others are re-read from memory by every sweep):
   8-row class   <8, 1, 3>   S =  8, 3 slots, RES 3: 24 edges, all resident
   16-row class  <16, 1, 6>  S = 16, 6 slots, RES 3: 96 edges, 48 resident - the pair 12/48 and 12/50 of the table
   24-row class  <32, 1, 6>  S = 32, 6 slots, RES 2 (LFR_RES4): 192 edges, 2 x 32 = 64 resident.  A complete track of 10 nodes (the
