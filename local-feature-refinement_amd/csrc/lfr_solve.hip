@@ -382,8 +382,20 @@ __device__ __forceinline__ void solve_group_body(const KernelArgs &a, const int 
                 // the full step's trial point (the decision after the sweep reads the last two from LDS; a line-search contraction
                 // recomputes them for its point, and only it needs max |delta| and g_new . delta)
                 const double xt_full = clampb(__dadd_rn(xi, dl));
-                double mcc = own ? (-rhs0 * step + dd * step * step) : 0.0, gdd = own ? gi * dl : 0.0;
-                double sn2 = own ? (xi - xt_full) * (xi - xt_full) : 0.0, xn2 = own ? xt_full * xt_full : 0.0;
+                // One lane per row (LPR == 1): the lanes beyond the system need no mask in front of the sums, their terms are +0 already.
+                // There step = 0 (packed_step), rhs0 = gi = 0 (the gradient is read behind is_row), xi = xt_full = 0 (never moved
+                // from the start), and dd is finite wherever the sums are used: such a lane keeps scale = inv_scale = 1 and
+                // a_ii = 1, so diag stays in [kMinLmDiag, kMaxLmDiag], and a group in PH_SOLVE has kMinRadius < radius <= kMaxRadius
+                // (the iteration entry above ends it otherwise) - 0 times a finite value, not a select (a compare and eight
+                // v_cndmask per LM step).  A group outside PH_SOLVE may carry any radius; its sums are computed and dropped.
+                // Two lanes per row: the second lane of a row holds the same values and has to be masked out.
+                auto own_term = [&](double v) { return (LPR == 1 || own) ? v : 0.0; };
+                double mcc = own_term(-rhs0 * step + dd * step * step), gdd = own_term(gi * dl);
+                double sn2 = own_term((xi - xt_full) * (xi - xt_full)), xn2 = own_term(xt_full * xt_full);
+                // The terms enter the butterflies as finished values.  Left visible (the selects used to stand in between), the product is
+                // fused into the first addition of a butterfly - fma(d, d, partner's d^2) in one lane, fma(d', d', this lane's d^2) in its
+                // partner: two roundings of one sum, and the lanes of a group would no longer hold the same bits.
+                if constexpr (LPR == 1) asm volatile("" : "+v"(mcc), "+v"(gdd), "+v"(sn2), "+v"(xn2));
 #ifdef LFR_ABL_RED             // every reduction twice
                 { double a_ = mcc, b_ = gdd, c_ = sn2, d_ = xn2; asm volatile("" : "+v"(a_), "+v"(b_), "+v"(c_), "+v"(d_)); group_sum4<S>(a_, b_, c_, d_);
                   asm volatile("" :: "v"(a_), "v"(b_), "v"(c_), "v"(d_)); }
@@ -451,7 +463,10 @@ __device__ __forceinline__ void solve_group_body(const KernelArgs &a, const int 
                 asm volatile("" : "+v"(pk));              // decode here, do not hoist 5 derived values per slot
                 const int es = (int)(pk & 0xffffu), ed = (int)((pk >> 16) & 0x7fffu), ekind = (int)(pk >> 31);
                 const int xa = 2 * min(es, n_var), xb = 2 * min(ed, n_var);      // constants read the zero slot
-                const int ra = es < n_var ? 2 * es : -1, rb = ed < n_var ? 2 * ed : -1;
+                // rows of the two end points; a constant (node >= n_var) assembles nothing.  The tests are the compares themselves: as
+                // `es < n_var ? 2 * es : -1` and a later `ra >= 0` each end point cost a select and a second compare per slot pass.
+                const bool va = es < n_var, vb = ed < n_var;
+                const int ra = 2 * es, rb = 2 * ed;
                 EdgeOut o;
                 ISA_MARK("eval");
                 eval_edge<true>(flow_k, sim_k, ekind, tv, L.x[xa], L.x[xa + 1], L.x[xb], L.x[xb + 1], o, at_zero, lcp, kcp);
@@ -482,20 +497,27 @@ __device__ __forceinline__ void solve_group_body(const KernelArgs &a, const int 
                 const double c_own1 = o.sq * (q ? o.j10 : o.j00), c_own2 = o.sq * (q ? o.j01 : o.j11);
                 const double c1 = c_own1 + dpp_f64<kDppQuadXor1>(c_send1);
                 const double c2 = c_own2 + dpp_f64<kDppQuadXor1>(c_send2);
-                if (ra >= 0) {
-                    atomicAdd(&A[ra * LD + ra], o.j00 * o.j00 + o.j10 * o.j10 + p_w);
-                    atomicAdd(&A[(ra + 1) * LD + ra], o.j01 * o.j00 + o.j11 * o.j10);
-                    atomicAdd(&A[(ra + 1) * LD + ra + 1], o.j01 * o.j01 + o.j11 * o.j11 + p_w);
-                    atomicAdd(&g[ra], o.j00 * o.r0 + o.j10 * o.r1 + p_g0);
-                    atomicAdd(&g[ra + 1], o.j01 * o.r0 + o.j11 * o.r1 + p_g1);
+                if (va) {
+                    // one address per block, the other entries at constant offsets of it (the ds_add's own offset field): as
+                    // `A[(ra + 1) * LD + ra]` every entry had an index product of its own
+                    double *Ad = A + ra * (LD + 1), *gd = g + ra;
+                    atomicAdd(Ad, o.j00 * o.j00 + o.j10 * o.j10 + p_w);
+                    atomicAdd(Ad + LD, o.j01 * o.j00 + o.j11 * o.j10);
+                    atomicAdd(Ad + LD + 1, o.j01 * o.j01 + o.j11 * o.j11 + p_w);
+                    atomicAdd(gd, o.j00 * o.r0 + o.j10 * o.r1 + p_g0);
+                    atomicAdd(gd + 1, o.j01 * o.r0 + o.j11 * o.r1 + p_g1);
                 }
-                if (ra >= 0 && rb >= 0) {
-                    const int r1 = rb + q, k1 = ra, r2 = rb + 1 - q, k2 = ra + 1;
-                    // (row and column selected, then one index: as `below ? r * LD + k : k * LD + r` the two sides became a divergent
-                    // if / else with its exec bracket, 5 SALU per slot)
-                    const bool below = rb > ra;
-                    atomicAdd(&A[(below ? r1 : k1) * LD + (below ? k1 : r1)], c1);
-                    atomicAdd(&A[(below ? r2 : k2) * LD + (below ? k2 : r2)], c2);
+                if (va && vb) {
+                    // The cross block (rows rb, rb + 1 x columns ra, ra + 1) as the lower triangle stores it starts at
+                    // C = A[max][min].  This lane's first entry is (rb + q, ra): q rows down when the block lies below the diagonal,
+                    // q columns right when it is stored transposed; its second, (rb + 1 - q, ra + 1), is the same distance back
+                    // from the block's far corner C + LD + 1.  Two selects of an index pair and two index products per entry before.
+                    // (from the node numbers and in bytes: one multiply-add and one shift-add for C, and the two distances are lane
+                    // constants the select takes as they are)
+                    char *C = reinterpret_cast<char *>(A) + max(es, ed) * (2 * LD * (int)sizeof(double)) + min(es, ed) * (2 * (int)sizeof(double));
+                    const int qs = ed > es ? q * (LD * (int)sizeof(double)) : q * (int)sizeof(double);
+                    atomicAdd(reinterpret_cast<double *>(C + qs), c1);
+                    atomicAdd(reinterpret_cast<double *>(C - qs) + (LD + 1), c2);
                 }
             }
         } else {
@@ -514,9 +536,7 @@ __device__ __forceinline__ void solve_group_body(const KernelArgs &a, const int 
                 asm volatile("" : "+v"(pk));              // decode here, do not hoist 5 derived values per slot
                 const int es = (int)(pk & 0xffffu), ed = (int)((pk >> 16) & 0x7fffu), ekind = (int)(pk >> 31);
                 const int xa = 2 * min(es, n_var), xb = 2 * min(ed, n_var);      // constants read the zero slot
-                const int ra = es < n_var ? 2 * es : -1, rb = ed < n_var ? 2 * ed : -1;
                 EdgeOut o;
-                (void)ra; (void)rb;
                 ISA_MARK("eval_cost_only");
                 eval_edge<false>(flow_k, sim_k, ekind, tv, L.x[xa], L.x[xa + 1], L.x[xb], L.x[xb + 1], o, false, lcp, kcp);
                 ISA_MARK("cost_only_loop");
@@ -552,6 +572,11 @@ __device__ __forceinline__ void solve_group_body(const KernelArgs &a, const int 
             scale = 1.0 / inv_scale;                                                // jacobi scaling, once
             a_dirty = false; phase = PH_SOLVE;
         } else if (phase == PH_REEVAL) {
+            // x was accepted at a finite cost, so a non-finite one here is an input the first sweep's closed form at the origin did not
+            // read (a corner of a flow grid).  When the edge's source is the fixed root the bad value reaches only the cost and J^T r,
+            // which this round drops: J^T J stays finite and the solve would shrink its radius to a "converged" zero step.  include/lfr.h
+            // has such a component fail; a NaN gradient makes every step from here invalid (LFR_TERM_FAILURE after kMaxInvalid of them).
+            if (!isfinite(cost_e)) gi = __builtin_nan("");                  // (a constant: a select, no fp64 instruction)
             a_dirty = false; phase = PH_SOLVE;
         } else if (phase == PH_EVAL_LS && cost_only) {
             // Speculative cost-only round: without the jacobian only the two "converged, candidate discarded"

@@ -2,6 +2,10 @@
 phase boundaries, no GPU needed), walks the ISA of the kernel in textual order and counts the instructions of every phase by kind, per
 packed class.  The counts are STATIC (one pass over the unrolled code: every edge slot, every elimination step, every instantiation of
 the elimination once); next to the s_memtime phase profile (-DLFR_PROFILE_PHASES) they say what a phase's cycles are spent on.
+Every class gets a second table, "VALU by family": its vector-ALU instructions again, per phase, split into fp64 arithmetic, conversions,
+int32, plain v_mov, DPP moves, v_cndmask, v_cmp, lane moves (v_readlane / v_writelane / v_readfirstlane), v_accvgpr and the rest (listed
+by mnemonic under the table); `non_arith` is everything but the first two.  Blocks are attributed in TEXTUAL order and the compiler lays
+them out in its own: a class sum is reliable, a phase row approximate.
 usage: python scripts/isa_account.py [kernel-substring [existing.s]] > profiles/r04_isa_account_packed_kernel.txt
 (an existing ISA file given as the second argument is read instead of compiling; the default substring meets the warm-start
 instantiation first: solve_packed_kernelILb0ELb0E names the cold record-reading kernel the bench runs).  The first line of the output
@@ -41,6 +45,26 @@ def kind(op):
     return "other"
 
 
+VALU_KINDS = ["f64_arith", "convert", "int32", "mov", "dpp_mov", "cndmask", "cmp", "lane", "accvgpr", "else"]
+INT32 = re.compile(r"v_(add|sub|subrev|addc|subb|subbrev|mul_lo|mul_hi|mul_u32|mul_i32|mad|lshl|lshr|ashr|lshlrev|lshrrev|ashrrev|and|or|xor|xnor|not|bfe|bfi|bfm|alignbit|alignbyte|perm|"
+                   r"min|max|med3|min3|max3|add3|lshl_add|lshl_or|add_lshl|and_or|or3|xad|mbcnt|bcnt|ffbh|ffbl|sad)\w*_(u32|i32|b32|u24|i24|u16|i16|b16|u64|i64|b64|u32_u24|i32_i24|lo_u32_b32|hi_u32_b32)(_e32|_e64|_sdwa)?$")
+
+
+def valu_kind(op, text):
+    """The split of the VALU row (the old table's valu_f64 + valu_other + lane): by mnemonic family alone.  A DPP operand on an fp64 instruction
+    (the elimination's v_fmac_f64 row_newbcast) leaves it arithmetic; dpp_mov is a v_mov that exists to move a value across lanes."""
+    is_dpp = "dpp" in op or "row_" in text or "quad_perm" in text or "wave_" in text
+    if op.startswith("v_readlane") or op.startswith("v_readfirstlane") or op.startswith("v_writelane"): return "lane"
+    if op.startswith("v_accvgpr"): return "accvgpr"
+    if op.startswith("v_cmp"): return "cmp"
+    if op.startswith("v_cndmask"): return "cndmask"
+    if op.startswith("v_cvt"): return "convert"
+    if op.startswith("v_mov_b"): return "dpp_mov" if is_dpp else "mov"
+    if "f64" in op: return "f64_arith"
+    if INT32.match(op): return "int32"
+    return "else"
+
+
 NAMES = {"0": "prologue: edges -> registers", "loop_top": "iteration entry: convergence tests, LM diagonal, rows of A -> registers (all instantiations)", "1": "LM step tail (model change, transitions of A)", "5": "step setup: diagonal, build rows of A in registers",
          "gauss_jordan": "Gauss-Jordan elimination (all instantiations)", "step_reductions": "step: reductions, validity, trial point",
          "6": "zero J^T J in LDS", "sweep_setup": "sweep: slot setup", "eval": "sweep: edge evaluation (cost.cc model: interpolant, loss, corrector)",
@@ -48,6 +72,8 @@ NAMES = {"0": "prologue: edges -> registers", "loop_top": "iteration entry: conv
          "2": "after the sweep: LDS sync", "3": "post-sweep reductions", "4": "transitions (convergence tests, line search bookkeeping)", "entry": "kernel entry / class dispatch"}
 cls, mark = "entry", "entry"
 acc = collections.defaultdict(lambda: collections.Counter())
+vacc = collections.defaultdict(lambda: collections.Counter())          # the VALU row split by family
+velse = collections.defaultdict(lambda: collections.Counter())         # what the split's last column holds, by mnemonic
 dpp = collections.Counter()
 for l in lines[start:end]:
     t = l.strip()
@@ -60,6 +86,10 @@ for l in lines[start:end]:
     if not t or t[0] in ";." or t.endswith(":"): continue
     op = t.split()[0]
     acc[(cls, mark)][kind(op)] += 1
+    if op.startswith("v_") and kind(op) != "mfma":
+        vk = valu_kind(op, t)
+        vacc[(cls, mark)][vk] += 1
+        if vk == "else": velse[cls][re.sub(r"_(e32|e64|dpp|sdwa)$", "", op)] += 1
     if "dpp" in op or "row_" in t or "quad_perm" in t: dpp[(cls, mark)] += 1
 kinds = ["valu_f64", "valu_other", "lane", "lds", "lds_atomic", "lds_xbar", "vmem", "scratch", "smem", "salu", "waitcnt", "branch", "other"]
 print("solve_packed_kernel<false>: static instruction counts per phase (compile-time unrolled code, one pass), from the ISA of this tree\n")
@@ -82,4 +112,15 @@ for c in sorted({k[0] for k in acc}):
         tot.update(a)
         print("  %-62s %6d | %s | %4d" % (NAMES.get(mk, mk)[:62], n, " ".join("%9d" % a[k] for k in kinds), dpp[(c, mk)]))
     print("  %-62s %6d | %s" % ("sum", sum(tot.values()), " ".join("%9d" % tot[k] for k in kinds)))
+    # the VALU instructions of the class again (valu_f64 + valu_other + lane above), split by family: what is arithmetic and what only
+    # moves, selects and compares.  non_arith = everything but f64_arith and convert
+    print("  %-62s %6s | %s | non_arith" % ("VALU by family", "valu", " ".join("%9s" % k[:9] for k in VALU_KINDS)))
+    vtot = collections.Counter()
+    for mk in order + sorted({k[1] for k in vacc if k[0] == c} - set(order)):
+        a = vacc.get((c, mk))
+        if not a: continue
+        vtot.update(a)
+        print("  %-62s %6d | %s | %6d" % (NAMES.get(mk, mk)[:62], sum(a.values()), " ".join("%9d" % a[k] for k in VALU_KINDS), sum(a.values()) - a["f64_arith"] - a["convert"]))
+    print("  %-62s %6d | %s | %6d" % ("sum", sum(vtot.values()), " ".join("%9d" % vtot[k] for k in VALU_KINDS), sum(vtot.values()) - vtot["f64_arith"] - vtot["convert"]))
+    print("  else: " + "  ".join("%s %d" % kv for kv in velse[c].most_common()))
     print()

@@ -12,7 +12,8 @@ for pass in "SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_
             "SQC_ICACHE_REQ SQC_ICACHE_HITS SQC_ICACHE_MISSES SQC_ICACHE_BUSY_CYCLES SQ_IFETCH SQ_INSTS_BRANCH SQ_THREAD_CYCLES_VALU SQ_ACTIVE_INST_MISC" \
             "SQ_INSTS_VALU_FMA_F64 SQ_INSTS_VALU_MUL_F64 SQ_INSTS_VALU_ADD_F64 SQ_INSTS_VALU_TRANS_F64 SQ_INSTS_VALU_CVT SQ_INSTS_VALU_INT32 SQ_INSTS_VALU_INT64 SQ_ACTIVE_INST_VALU2"; do
   i=$((i+1))
-  rocprofv3 --pmc $pass --kernel-trace --output-format csv -d $O/p$i -o pmc -- python $R/scripts/ab_packed.py --child 147000 4 /tmp/pmc_ref_$$.npy c4 > $O/p$i.log 2>&1 || echo "pass $i failed" >> $O/pmc.txt
+  # every pass under its own time limit; a pass that fails, faults or hangs ends the script - nothing more is started on that GPU
+  timeout -k 10 300 rocprofv3 --pmc $pass --kernel-trace --output-format csv -d $O/p$i -o pmc -- python $R/scripts/ab_packed.py --child 147000 4 /tmp/pmc_ref_$$.npy c4 > $O/p$i.log 2>&1 || { echo "pass $i failed ($?): stopping" | tee -a $O/pmc.txt; tail -5 $O/p$i.log; exit 1; }
   rm -f /tmp/pmc_ref_$$.npy
 done
 python - <<PY > $O/pmc.txt
