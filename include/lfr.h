@@ -795,6 +795,68 @@ int lfr_batch_hessian_product(lfr_batch *b, const double *positions_device, cons
                               double *curvature_device,     /* n_vectors x n_components, may be NULL */
                               int flags, void *hip_stream, lfr_hessian_product_stats *stats);
 
+/* ---------------------------------------------------------------------------------------------
+ * Matrix-free linear solves with that matrix: (H + damping I) y = b per component by preconditioned conjugate gradients, the whole
+ * iteration inside the kernel, every component stopping on its own.
+ *
+ * Contract.  Per solved-program component c of this shard, whatever its termination:
+ *   - the matrix.  A = H + damping I, H exactly the matrix of lfr_batch_hessian_product under the same flags (the exact Hessian, or
+ *     J^T J with LFR_HSOLVE_GAUSS_NEWTON; LFR_HSOLVE_FREE_SET makes the coordinates with |x| >= 1 identity rows and columns), with
+ *     the records as they are NOW and lfr_batch_hessian_product's rules for positions_device (NULL = the batch's own array; NULL
+ *     before the first solve: LFR_ERR_ARG).  With the free set a bound coordinate gets y_i = b_i, the very bits: it enters no other
+ *     row and no norm, and the damping is not added there;
+ *   - the method.  Preconditioned conjugate gradients from y = 0.  The preconditioner is the inverse of every variable node's own
+ *     2x2 diagonal block of A: M summed over the node's in-edges, P^T M P minus the second-derivative term over its out-edges, plus
+ *     the damping; a bound coordinate is the identity's in its block.  A block that is not finite, or has a00 <= 0 or det <= 0
+ *     (the exact mode can), is replaced by the identity for that node;
+ *   - the stop.  After every step the residual r of the recurrence is tested: LFR_HSOLVE_OK when |r|_2 <= rel_tolerance |b|_2, both
+ *     norms over the component's variable coordinates that are not bound.  b = 0 there: y = 0, LFR_HSOLVE_OK, 0 iterations.
+ *     LFR_HSOLVE_MAX_ITERATIONS after max_iterations steps: y is the last iterate;
+ *   - negative curvature.  LFR_HSOLVE_NEGATIVE_CURVATURE when a search direction p has p . A p <= 0: y is the iterate reached BEFORE
+ *     that direction (zeros when it was the first), the rule of a truncated Newton step.  LFR_HSOLVE_OK does NOT certify that H is
+ *     positive definite: conjugate gradients only ever see the Krylov space of b;
+ *   - LFR_HSOLVE_NONFINITE when b (off the bound coordinates), a record or an intermediate of the component is not finite; its
+ *     outputs may be non-finite.  No other component changes by a bit, one in the same wavefront included;
+ *   - rhs_device / solutions_device: n_rhs arrays of 2 * n_nodes doubles in the layout of the positions, 1 <= n_rhs <=
+ *     LFR_HVP_MAX_VECTORS.  The whole solutions array is overwritten; constants, unsolved nodes and nodes outside the shard get 0;
+ *   - status_device, iterations_device, residual_device (each may be NULL): n_rhs x n_components, entry [k * n_components + c], c in
+ *     the order of lfr_batch_component_info: the status above, the steps taken, the final |r|_2 / |b|_2 of the recurrence (0 for
+ *     b = 0);
+ *   - LFR_ERR_ARG, before any output is touched: no batch, rhs_device or solutions_device NULL, n_rhs out of range, a flag bit other
+ *     than the two defined, damping negative or not finite, rel_tolerance negative or NaN, max_iterations < 1, NULL positions before
+ *     the first solve.  There is no row limit and batches over one rank's connected components are served;
+ *   - every sum has a fixed order (packed classes: the group's butterfly; workgroup classes: a wave-then-block tree and rows summed
+ *     by their owner in record order) and no fp64 value goes through a global-memory atomic: outputs are bitwise repeatable from
+ *     call to call and identical for host- and device-assembled batches; the outputs of right-hand side k are the same bits whether
+ *     it is passed alone or among others, whatever the others hold - one that is done is frozen while the others go on;
+ *   - runs on `hip_stream`, asynchronous unless stats != NULL; waits by event as lfr_batch_hessian_product does, and
+ *     lfr_batch_set_inputs waits for the latest solve of this kind.  All calls on a batch iterate in one workspace: a call on
+ *     another stream waits by event for the latest call, so calls of one batch run one after the other, in the order they were made.
+ * Kernels (lfr_hessian_solve.hip): every record's blocks M, P, S are formed once per call.  Packed classes: in the registers of the
+ * record's lane, p and A p in the group's LDS.  Workgroup classes: one persistent workgroup per component, the blocks in an 80-byte
+ * slot per record of the pass's workspace, r, p, A p by global node id there, y in solutions_device. */
+typedef struct lfr_hessian_solve_stats {
+    int64_t n_components;          /* components swept */
+    int64_t n_converged, n_max_iterations, n_negative_curvature, n_nonfinite;   /* over all (rhs, component) pairs */
+    int64_t sum_iterations, max_iterations_used;
+    int64_t n_bound_coordinates;   /* with LFR_HSOLVE_FREE_SET: coordinates treated as bound; else 0 */
+    double kernel_ms;              /* HIP-event time of the call's kernels (and its clearing of the solutions) */
+} lfr_hessian_solve_stats;
+
+#define LFR_HSOLVE_GAUSS_NEWTON 2  /* same bit values as LFR_HVP_* */
+#define LFR_HSOLVE_FREE_SET 4
+#define LFR_HSOLVE_OK 0
+#define LFR_HSOLVE_MAX_ITERATIONS 1
+#define LFR_HSOLVE_NEGATIVE_CURVATURE 2
+#define LFR_HSOLVE_NONFINITE 3
+
+int lfr_batch_hessian_solve(lfr_batch *b, const double *positions_device,
+                            const double *rhs_device, int n_rhs,          /* n_rhs x 2 * n_nodes, 1..LFR_HVP_MAX_VECTORS */
+                            double damping, double rel_tolerance, int max_iterations,
+                            double *solutions_device,                     /* n_rhs x 2 * n_nodes, required */
+                            int32_t *status_device, int32_t *iterations_device, double *residual_device, /* n_rhs x n_components, each may be NULL */
+                            int flags, void *hip_stream, lfr_hessian_solve_stats *stats);
+
 /* Unit-level probe of the device arithmetic (cost.cc:13-48,78-90 + the loss / corrector of solve.cc:111,120): for
  * each of n edges (flows n x 18 float32, sim, kind 0 = intra-track/Cauchy 1 = inter-track/Tukey, x1 = source and
  * x2 = destination position) the kernels' eval_edge on the GPU: out8[8i..] = 0.5*rho, corrected residual r0 r1,

@@ -10,6 +10,7 @@
 //   lfr_evaluate.hip     cost, gradient, residuals and loss weights at given positions (lfr_batch_evaluate) and their vector-Jacobian
 //                        product (lfr_batch_evaluate_vjp)
 //   lfr_hessian_product.hip   matrix-free H v at given positions (lfr_batch_hessian_product)
+//   lfr_hessian_solve.hip     matrix-free (H + damping I) y = b by preconditioned conjugate gradients (lfr_batch_hessian_solve)
 //   lfr_jvp.hip          forward-mode sensitivity of the positions (lfr_batch_jvp)
 //   lfr_backward.hip     implicit-gradient backward pass (lfr_batch_backward)
 //   lfr_covariance.hip   per-keypoint and per-match covariance (lfr_batch_covariance, lfr_batch_covariance_matches)
@@ -164,7 +165,7 @@ hipEvent_t pass_last_event(const PassState *s);         // end of the latest cal
 // first call (*slot is installed only after every step has succeeded; slab and events are released on every error path), the wait
 // for the latest solve, the record of ev0 on st.
 int pass_begin(lfr_batch *b, PassState **slot, const PassKind &kind, size_t extra_bytes, hipStream_t st);
-// The same for the passes that need no solve (evaluate, evaluate_vjp, hessian_product), whose entry is their own: the first call's
+// The same for the passes that need no solve (evaluate, evaluate_vjp, hessian_product, hessian_solve), whose entry is their own: the first call's
 // setup with a slab of slab_bytes for kind.extra to carve (installed in *slot as above)
 int pass_setup_unsolved(lfr_batch *b, PassState **slot, const PassKind &kind, size_t slab_bytes);
 int pass_end(PassState *s, hipStream_t st);             // records ev1; the call is now the pass's latest
@@ -267,6 +268,7 @@ struct lfr_batch {
     lfr::PassState *jvp = nullptr;                       // lfr_jvp.hip: set up on the first lfr_batch_jvp
     lfr::PassState *evjp = nullptr;                      // lfr_evaluate.hip: set up on the first lfr_batch_evaluate_vjp (needs no solve either)
     lfr::PassState *hvp = nullptr;                       // lfr_hessian_product.hip: set up on the first lfr_batch_hessian_product (needs no solve either)
+    lfr::PassState *hsolve = nullptr;                    // lfr_hessian_solve.hip: set up on the first lfr_batch_hessian_solve (needs no solve either)
 
     lfr_batch() { for (auto &e : ev_ring) e = nullptr; }
     ~lfr_batch() {
@@ -276,6 +278,7 @@ struct lfr_batch {
         lfr::pass_free(jvp);
         lfr::pass_free(evjp);
         lfr::pass_free(hvp);
+        lfr::pass_free(hsolve);
         if (ctx) {
             (void)hipSetDevice(device);
             if (n_solves > 0) (void)hipStreamSynchronize(last_stream);      // nothing may still use the slab
@@ -308,7 +311,7 @@ void materialize_records(lfr_batch *b, hipStream_t st);
 // (LFR_ERR_ARG when that has been freed) - a synchronising call the first time, free afterwards
 int ensure_edge_map(lfr_batch *b);
 inline const uint32_t *edge_map(const lfr_batch *b) { return b->d_edge_ref ? b->d_edge_ref : b->d_eid; }
-// What the passes that need no solve (evaluate, evaluate_vjp, hessian_product) do before their launches: wait by event for the latest
+// What the passes that need no solve (evaluate, evaluate_vjp, hessian_product, hessian_solve) do before their launches: wait by event for the latest
 // solve and the latest lfr_batch_set_inputs, record the pass's ev0, and write the packed records of a device-assembled batch that
 // still gathers them from the graph's arrays
 int eval_prologue(lfr_batch *b, PassState &s, hipStream_t st);

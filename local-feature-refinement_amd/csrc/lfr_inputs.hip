@@ -145,9 +145,9 @@ int lfr_batch_set_inputs(lfr_batch *b, const float *disp1_device, const float *d
     if (!b->d_edge_ref && !b->d_eid) { const int rc = lfr::ensure_edge_map(b); if (rc != LFR_OK) return rc; }
     if (!b->ev_inputs && !(b->ev_inputs = b->ctx->event_acquire(false))) return LFR_ERR_HIP;
     hipStream_t st = (hipStream_t)hip_stream;
-    // everything that reads the records: the latest solve, backward, covariance, evaluate, evaluate_vjp, jvp and hessian_product, whatever streams they ran on
+    // everything that reads the records: the latest solve, backward, covariance, evaluate, evaluate_vjp, jvp, hessian_product and hessian_solve, whatever streams they ran on
     if (b->n_solves > 0) HIP_TRY(hipStreamWaitEvent(st, b->ev[1], 0));
-    for (const lfr::PassState *pass : {b->bwd, b->cov, b->eval, b->evjp, b->jvp, b->hvp})
+    for (const lfr::PassState *pass : {b->bwd, b->cov, b->eval, b->evjp, b->jvp, b->hvp, b->hsolve})
         if (hipEvent_t e = lfr::pass_last_event(pass)) HIP_TRY(hipStreamWaitEvent(st, e, 0));
     if (b->inputs_epoch > 0 && b->inputs_stream != st) HIP_TRY(hipStreamWaitEvent(st, b->ev_inputs, 0));
     if (b->fused) {          // complete records first (words, and whichever of flows / similarity this call keeps), from the graph's arrays

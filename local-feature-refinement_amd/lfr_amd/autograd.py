@@ -478,6 +478,18 @@ class Refiner:
                                               positions.detach() if isinstance(positions, torch.Tensor) else positions, **kw)
         return {k: (v.detach() if isinstance(v, torch.Tensor) else v) for k, v in out.items()}
 
+    def hessian_solve(self, rhs, positions=None, **kw):
+        """Batch.hessian_solve (lfr_batch_hessian_solve) on the shared batch: (H + damping I) y = rhs per component by preconditioned
+        conjugate gradients, H the matrix of hessian_product() at `positions` ([n_nodes, 2], None = the latest forward's) with the
+        records of the latest forward - or of the constructor before the first.  Everything is per node, so nothing is mapped to the
+        caller's rows.  Every tensor is detached: this is no double backward."""
+        if self._batch is None:
+            raise RuntimeError("Refiner: hessian_solve after close()")
+        with torch.cuda.device(self.device):
+            out = self._batch.hessian_solve(rhs.detach() if isinstance(rhs, torch.Tensor) else rhs,
+                                            positions.detach() if isinstance(positions, torch.Tensor) else positions, **kw)
+        return {k: (v.detach() if isinstance(v, torch.Tensor) else v) for k, v in out.items()}
+
     def objective(self, positions, disp1, disp2, sim=None, *, residuals=False, weights=False):
         """The objective of the latest forward as a differentiable function of (positions, disp1, disp2, sim): `cost` [n_components]
         float64 in the order of Batch.component_info - and, when asked for, `residuals` [rows, 2, 2] and `weights` [rows, 2] (float64,

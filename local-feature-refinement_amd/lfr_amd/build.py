@@ -14,7 +14,7 @@ ROOT = os.path.dirname(os.path.dirname(_HERE))
 CSRC = os.path.join(os.path.dirname(_HERE), "csrc")
 OBJ = os.path.join(CSRC, "_obj")
 SOURCES = ["lfr_wire.cpp", "lfr_graph.cpp", "lfr_treeplan.cpp", "lfr_devctx.cpp", "lfr_solve.hip", "lfr_batch.hip", "lfr_backward.hip",
-           "lfr_covariance.hip", "lfr_inputs.hip", "lfr_evaluate.hip", "lfr_jvp.hip", "lfr_hessian_product.hip", "lfr_assemble.hip", "lfr_graphstage.hip", "lfr_graphbuild.hip"]
+           "lfr_covariance.hip", "lfr_inputs.hip", "lfr_evaluate.hip", "lfr_jvp.hip", "lfr_hessian_product.hip", "lfr_hessian_solve.hip", "lfr_assemble.hip", "lfr_graphstage.hip", "lfr_graphbuild.hip"]
 OUT = os.path.join(_HERE, "liblfr_hip.so")
 
 

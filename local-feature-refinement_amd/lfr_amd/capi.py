@@ -85,6 +85,14 @@ class HessianProductStats(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+class HessianSolveStats(C.Structure):
+    _fields_ = [(n, C.c_int64) for n in ("n_components", "n_converged", "n_max_iterations", "n_negative_curvature", "n_nonfinite",
+                                         "sum_iterations", "max_iterations_used", "n_bound_coordinates")] + [("kernel_ms", C.c_double)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
 class JvpStats(C.Structure):
     _fields_ = [(n, C.c_int64) for n in ("n_differentiated", "n_not_usable", "n_indefinite", "n_bound_coordinates")] + [("kernel_ms", C.c_double)]
 
@@ -106,6 +114,9 @@ EVALUATE_F64 = 1                # LFR_EVALUATE_F64
 HVP_GAUSS_NEWTON = 2            # LFR_HVP_GAUSS_NEWTON
 HVP_FREE_SET = 4                # LFR_HVP_FREE_SET
 HVP_MAX_VECTORS = 4             # LFR_HVP_MAX_VECTORS
+HSOLVE_GAUSS_NEWTON = 2         # LFR_HSOLVE_GAUSS_NEWTON
+HSOLVE_FREE_SET = 4             # LFR_HSOLVE_FREE_SET
+HSOLVE_OK, HSOLVE_MAX_ITERATIONS, HSOLVE_NEGATIVE_CURVATURE, HSOLVE_NONFINITE = 0, 1, 2, 3      # status of lfr_batch_hessian_solve
 
 
 _lib = None
@@ -180,6 +191,8 @@ def lib():
         "lfr_batch_evaluate": (C.c_int, [vp, vp, vp, vp, vp, vp, C.c_int, vp, C.POINTER(EvaluateStats)]),
         "lfr_batch_evaluate_vjp": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_int, vp, C.POINTER(EvaluateVjpStats)]),
         "lfr_batch_hessian_product": (C.c_int, [vp, vp, vp, C.c_int, vp, vp, C.c_int, vp, C.POINTER(HessianProductStats)]),
+        "lfr_batch_hessian_solve": (C.c_int, [vp, vp, vp, C.c_int, C.c_double, C.c_double, C.c_int, vp, vp, vp, vp, C.c_int, vp,
+                                              C.POINTER(HessianSolveStats)]),
         "lfr_keypoint_covariances": (C.c_int, [vp, vp, C.c_char_p, vp, i64]),
         "lfr_debug_invert_spd": (C.c_int, [C.c_int, C.c_int, i64, vp, vp, vp, vp]),
         "lfr_batch_spin_timeouts": (i64, [vp]),
@@ -215,12 +228,28 @@ EXPORTS = ["lfr_version", "lfr_last_error", "lfr_graph_from_files", "lfr_graph_f
            "lfr_graph_num_images", "lfr_graph_get_nodes", "lfr_graph_image_name", "lfr_graph_image_fact",
            "lfr_write_matching_file", "lfr_problem_build", "lfr_problem_build_labels", "lfr_problem_build_hip", "lfr_problem_free", "lfr_problem_get_stats",
            "lfr_problem_get_labels", "lfr_problem_shard_components", "lfr_hip_warmup", "lfr_batch_create", "lfr_batch_free", "lfr_batch_solve", "lfr_batch_solve_from",
-           "lfr_batch_download", "lfr_batch_timing", "lfr_batch_spin_timeouts", "lfr_batch_team_runs", "lfr_batch_team_fallbacks", "lfr_debug_occupy", "lfr_batch_tree_stats", "lfr_batch_component_info", "lfr_batch_positions_to_device", "lfr_batch_backward", "lfr_batch_backward_status", "lfr_batch_jvp", "lfr_batch_jvp_status", "lfr_batch_set_inputs", "lfr_batch_covariance", "lfr_batch_covariance_matches", "lfr_batch_covariance_status", "lfr_batch_evaluate", "lfr_batch_evaluate_vjp", "lfr_batch_hessian_product", "lfr_keypoint_covariances", "lfr_debug_invert_spd", "lfr_solve_hip", "lfr_solve_hip_multi", "lfr_solve_graph_hip_multi", "lfr_write_solution", "lfr_apply_displacements"]
+           "lfr_batch_download", "lfr_batch_timing", "lfr_batch_spin_timeouts", "lfr_batch_team_runs", "lfr_batch_team_fallbacks", "lfr_debug_occupy", "lfr_batch_tree_stats", "lfr_batch_component_info", "lfr_batch_positions_to_device", "lfr_batch_backward", "lfr_batch_backward_status", "lfr_batch_jvp", "lfr_batch_jvp_status", "lfr_batch_set_inputs", "lfr_batch_covariance", "lfr_batch_covariance_matches", "lfr_batch_covariance_status", "lfr_batch_evaluate", "lfr_batch_evaluate_vjp", "lfr_batch_hessian_product", "lfr_batch_hessian_solve", "lfr_keypoint_covariances", "lfr_debug_invert_spd", "lfr_solve_hip", "lfr_solve_hip_multi", "lfr_solve_graph_hip_multi", "lfr_write_solution", "lfr_apply_displacements"]
 
 
 def _check(rc):
     if rc != 0:
         raise LfrError(rc, lib().lfr_last_error().decode("utf-8", "replace"))
+
+
+def _f64_device_tensor(caller, t, name, shapes, dev):
+    """Argument check of Batch.hessian_product / Batch.hessian_solve: t is a contiguous float64 torch tensor on `dev` with one of
+    `shapes` (None = any extent, printed as K); returns its address for the C call.  ValueError otherwise, in the caller's name."""
+    import torch
+    if not isinstance(t, torch.Tensor):
+        raise ValueError("%s: %s must be a torch tensor" % (caller, name))
+    if not t.is_cuda or t.device != dev:
+        raise ValueError("%s: %s is on %s, the batch on %s" % (caller, name, t.device, dev))
+    if t.dtype != torch.float64:
+        raise ValueError("%s: %s is %s, need torch.float64" % (caller, name, t.dtype))
+    if not t.is_contiguous() or not any(t.dim() == len(s) and all(w is None or w == h for w, h in zip(s, t.shape)) for s in shapes):
+        raise ValueError("%s: %s has shape %s, need a contiguous %s"
+                         % (caller, name, tuple(t.shape), " or ".join("[%s]" % ", ".join("K" if w is None else str(w) for w in s) for s in shapes)))
+    return C.c_void_p(t.detach().data_ptr() or 1)      # (no nodes: an empty tensor has no address, and nothing is read)
 
 
 def _ptr(a):
@@ -1040,16 +1069,7 @@ class Batch:
         dev = torch.device("cuda", self.device)
 
         def check(t, name, shapes):
-            if not isinstance(t, torch.Tensor):
-                raise ValueError("hessian_product: %s must be a torch tensor" % name)
-            if not t.is_cuda or t.device != dev:
-                raise ValueError("hessian_product: %s is on %s, the batch on %s" % (name, t.device, dev))
-            if t.dtype != torch.float64:
-                raise ValueError("hessian_product: %s is %s, need torch.float64" % (name, t.dtype))
-            if not t.is_contiguous() or not any(t.dim() == len(s) and all(w is None or w == h for w, h in zip(s, t.shape)) for s in shapes):
-                raise ValueError("hessian_product: %s has shape %s, need a contiguous %s"
-                                 % (name, tuple(t.shape), " or ".join("[%s]" % ", ".join("K" if w is None else str(w) for w in s) for s in shapes)))
-            return C.c_void_p(t.detach().data_ptr() or 1)      # (no nodes: an empty tensor has no address, and nothing is read)
+            return _f64_device_tensor("hessian_product", t, name, shapes, dev)
 
         pv = check(vectors, "vectors", ((None, n, 2), (n, 2)))
         single = vectors.dim() == 2
@@ -1075,6 +1095,66 @@ class Batch:
         flags = (HVP_GAUSS_NEWTON if gauss_newton else 0) | (HVP_FREE_SET if free_set else 0)
         _check(lib().lfr_batch_hessian_product(self._h, pp, pv, k, optr("products"), optr("curvature"), flags,
                                                C.c_void_p(stream) if stream else None, C.byref(st) if want_stats else None))
+        if want_stats:
+            out["stats"] = st.as_dict()
+        return out
+
+    def hessian_solve(self, rhs, positions=None, *, gauss_newton=False, free_set=False, damping=0.0, rel_tolerance=1e-10,
+                      max_iterations=None, want_info=True, want_stats=False, stream=None):
+        """Matrix-free (H + damping I) y = rhs per component by block-Jacobi preconditioned conjugate gradients inside the kernel
+        (lfr_batch_hessian_solve, include/lfr.h), H the matrix of hessian_product() under the same gauss_newton / free_set at
+        `positions` (a contiguous [n_nodes, 2] float64 tensor, or None = the batch's own after a solve).  rhs: a contiguous
+        [K, n_nodes, 2] (1 <= K <= HVP_MAX_VECTORS) or [n_nodes, 2] float64 tensor on the batch's device.  A component stops when
+        |r|_2 <= rel_tolerance |rhs|_2 (status HSOLVE_OK), after max_iterations steps (HSOLVE_MAX_ITERATIONS; None = 4 x the rows of
+        the largest component), at a direction of non-positive curvature (HSOLVE_NEGATIVE_CURVATURE: the iterate before it) or at a
+        value that is not finite (HSOLVE_NONFINITE).  Returns a dict of device tensors: "solutions" with the shape of `rhs` and, with
+        want_info, "status", "iterations" (int32) and "residual" (float64), [K, n_components] ([n_components] for one [n_nodes, 2]
+        right-hand side) in the order of component_info; with want_stats also "stats" (that waits)."""
+        import torch
+        n = self.problem.graph.n_nodes
+        dev = torch.device("cuda", self.device)
+
+        def check(t, name, shapes):
+            return _f64_device_tensor("hessian_solve", t, name, shapes, dev)
+
+        pr = check(rhs, "rhs", ((None, n, 2), (n, 2)))
+        single = rhs.dim() == 2
+        k = 1 if single else int(rhs.shape[0])
+        if not 1 <= k <= HVP_MAX_VECTORS:
+            raise ValueError("hessian_solve: %d right-hand sides, need 1 to %d" % (k, HVP_MAX_VECTORS))
+        pp = None if positions is None else check(positions, "positions", ((n, 2),))
+        damping, rel_tolerance = float(damping), float(rel_tolerance)
+        if not (0.0 <= damping < float("inf")):
+            raise ValueError("hessian_solve: damping %r, need a finite value >= 0" % damping)
+        if not rel_tolerance >= 0.0:
+            raise ValueError("hessian_solve: rel_tolerance %r, need a value >= 0" % rel_tolerance)
+        nc = lib().lfr_batch_component_info(self._h, None, None, None, None, None, None)
+        if nc < 0:
+            _check(int(nc))
+        if max_iterations is None:
+            nvar = np.zeros(nc, np.int32)
+            lib().lfr_batch_component_info(self._h, None, None, None, None, _ptr(nvar), None)
+            max_iterations = max(1, 8 * int(nvar.max(initial=0)))          # 4 x the rows (two per node) of the largest component
+        max_iterations = int(max_iterations)
+        if max_iterations < 1:
+            raise ValueError("hessian_solve: max_iterations %d, need at least 1" % max_iterations)
+        out = {"solutions": torch.empty(tuple(rhs.shape), dtype=torch.float64, device=dev)}
+        if want_info:
+            shape = (nc,) if single else (k, nc)
+            out["status"] = torch.empty(shape, dtype=torch.int32, device=dev)
+            out["iterations"] = torch.empty(shape, dtype=torch.int32, device=dev)
+            out["residual"] = torch.empty(shape, dtype=torch.float64, device=dev)
+        if stream is None:
+            stream = torch.cuda.current_stream(dev).cuda_stream
+
+        def optr(name):
+            return C.c_void_p(out[name].data_ptr() or 1) if name in out else None
+
+        st = HessianSolveStats()
+        flags = (HSOLVE_GAUSS_NEWTON if gauss_newton else 0) | (HSOLVE_FREE_SET if free_set else 0)
+        _check(lib().lfr_batch_hessian_solve(self._h, pp, pr, k, damping, rel_tolerance, max_iterations, optr("solutions"), optr("status"),
+                                             optr("iterations"), optr("residual"), flags, C.c_void_p(stream) if stream else None,
+                                             C.byref(st) if want_stats else None))
         if want_stats:
             out["stats"] = st.as_dict()
         return out
