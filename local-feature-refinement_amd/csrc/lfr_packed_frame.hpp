@@ -2,9 +2,9 @@
 // covariance_matches): the traits of a packed class, the dispatcher of the one launch that hosts all of them, and the identity of a
 // group of lanes inside its wave.  Everything a pass computes stays in its own unit.  The numbers come from ONE table, kPackedClass of
 // lfr_internal.hpp, which classify() and classify_dev() read too.
-// The forward kernel (lfr_solve.hip: solve_packed_kernel, launch_group_class, solve_geometry) still carries its own copy of the table
-// and of the dispatcher: its bytes key the committed PMC profiles (bench.py).  The next change that has to edit lfr_solve.hip anyway
-// folds it in.
+// The forward kernel (lfr_solve.hip: solve_packed_kernel, launch_group_class, solve_geometry, the debug launch) takes every number
+// from the same table through PackedClass<KC>.  It does not use packed_dispatch: its chain over the blocks' ranges is written out in
+// the kernel, indexed by kPackedOrder, because the compiler emits other instructions for it through the dispatcher's lambda.
 // Also here: the two guarded record walks of the workgroup layout (a node's out-edges and in-edges).
 #pragma once
 

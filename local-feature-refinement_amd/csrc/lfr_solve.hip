@@ -26,15 +26,18 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cassert>
 #include <type_traits>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <utility>
 #include <vector>
 
 #include "lfr_batch.hpp"
 #include "lfr_device.hpp"
 #include "lfr_internal.hpp"
+#include "lfr_packed_frame.hpp"
 
 using namespace lfrdev;
 using lfr::CompDesc;
@@ -682,8 +685,15 @@ __device__ __forceinline__ void solve_group_body(const KernelArgs &a, const int 
     }
 }
 
-constexpr size_t kPackedLdsBytes = kPackedWaves * (sizeof(GroupLds<16>) * 4 > 2 * sizeof(GroupLds<32>) ? sizeof(GroupLds<16>) * 4 : 2 * sizeof(GroupLds<32>));
-static_assert(kPackedLdsBytes >= kPackedWaves * 8 * sizeof(GroupLds<8>) && kPackedLdsBytes >= kPackedWaves * 2 * sizeof(GroupLds<16>), "LDS budget");
+// LDS of the one launch of all classes: the largest footprint of a live class's wave (kPackedClass), per wave of the workgroup
+template <int KC>
+constexpr size_t wave_lds_bytes() {
+    if constexpr (lfr::kPackedClass[KC].retired) return 0;
+    else return PackedClass<KC>::G * sizeof(GroupLds<PackedClass<KC>::NV>);
+}
+template <int... KC>
+constexpr size_t max_wave_lds_bytes(std::integer_sequence<int, KC...>) { return std::max({wave_lds_bytes<KC>()...}); }
+constexpr size_t kPackedLdsBytes = kPackedWaves * max_wave_lds_bytes(std::make_integer_sequence<int, lfr::kPackedClasses>{});
 
 // one class per launch (diagnostics: LFR_SERIAL_CLASSES=1 gives per-class timings)
 template <int NV, int LPR, int EPL, bool FUSED>
@@ -703,22 +713,29 @@ __global__ __launch_bounds__(64 * kPackedWaves, LFR_GROUP_WAVES) void solve_pack
     // microsecond, 95 % of the 2048 wave slots busy in the steady state and a 15-us tail; resident waves pulling blocks from an
     // atomic queue - what pays for the 160-KB workgroups of the long-track classes - cost this kernel 76 spilled VGPRs
     // and 38 %: 0.650 against 0.470 ms)
+    // slot i of PackedRanges is class kPackedOrder[i]: its numbers from the table (lfr_packed_frame.hpp).  The chain itself is written
+    // out: through packed_dispatch, or any helper between the kernel and the bodies, the compiler emits other instructions.  A class
+    // that is added, retired or moved in kPackedOrder is edited here by hand; the assertion below and PackedClass (which refuses a
+    // retired class) stop the build until it is
+    using lfr::kPackedOrder;
+    using P0 = PackedClass<kPackedOrder[0]>; using P1 = PackedClass<kPackedOrder[1]>; using P3 = PackedClass<kPackedOrder[3]>; using P4 = PackedClass<kPackedOrder[4]>;
+    static_assert(lfr::kPackedClasses == 5 && lfr::kPackedClass[kPackedOrder[2]].retired, "one branch per class, the third one retired");
     const int b = (int)blockIdx.x;
     if (b < r.blk_begin[1]) {
-        a.desc_begin = r.desc_begin[0]; a.desc_end = r.desc_end[0]; a.cls = lfr::KC_G64_4;
-        solve_group_body<32, 2, 5, FUSED, WARM>(a, b - r.blk_begin[0], lds_raw);
+        a.desc_begin = r.desc_begin[0]; a.desc_end = r.desc_end[0]; a.cls = kPackedOrder[0];
+        solve_group_body<P0::NV, P0::LPR, P0::EPL, FUSED, WARM>(a, b - r.blk_begin[0], lds_raw);
     } else if (b < r.blk_begin[2]) {
-        a.desc_begin = r.desc_begin[1]; a.desc_end = r.desc_end[1]; a.cls = lfr::KC_G64_2;
-        solve_group_body<32, 1, 6, FUSED, WARM>(a, b - r.blk_begin[1], lds_raw);
+        a.desc_begin = r.desc_begin[1]; a.desc_end = r.desc_end[1]; a.cls = kPackedOrder[1];
+        solve_group_body<P1::NV, P1::LPR, P1::EPL, FUSED, WARM>(a, b - r.blk_begin[1], lds_raw);
     } else if (b < r.blk_begin[3]) {
-        a.desc_begin = r.desc_begin[2]; a.desc_end = r.desc_end[2]; a.cls = lfr::KC_G32;
+        a.desc_begin = r.desc_begin[2]; a.desc_end = r.desc_end[2]; a.cls = kPackedOrder[2];
         // (KC_G32, formerly <16,2,3>, is retired: <16,1,6> takes every <=16-row component up to 96 edges)
     } else if (b < r.blk_begin[4]) {
-        a.desc_begin = r.desc_begin[3]; a.desc_end = r.desc_end[3]; a.cls = lfr::KC_G16;
-        solve_group_body<16, 1, 6, FUSED, WARM>(a, b - r.blk_begin[3], lds_raw);
+        a.desc_begin = r.desc_begin[3]; a.desc_end = r.desc_end[3]; a.cls = kPackedOrder[3];
+        solve_group_body<P3::NV, P3::LPR, P3::EPL, FUSED, WARM>(a, b - r.blk_begin[3], lds_raw);
     } else {
-        a.desc_begin = r.desc_begin[4]; a.desc_end = r.desc_end[4]; a.cls = lfr::KC_G8;
-        solve_group_body<8, 1, 3, FUSED, WARM>(a, b - r.blk_begin[4], lds_raw);
+        a.desc_begin = r.desc_begin[4]; a.desc_end = r.desc_end[4]; a.cls = kPackedOrder[4];
+        solve_group_body<P4::NV, P4::LPR, P4::EPL, FUSED, WARM>(a, b - r.blk_begin[4], lds_raw);
     }
 }
 
@@ -3278,8 +3295,11 @@ __global__ void lfr_warmup_kernel(int *p) { if (p) *p = 0; }
 namespace lfr {
 
 const SolveGeometry &solve_geometry() {
-    static const SolveGeometry g = {kPackedWaves, {8 * kPackedWaves, 4 * kPackedWaves, 2 * kPackedWaves, 2 * kPackedWaves, kPackedWaves, 1, 1, 1, 1},
-                                    kThreadsS, kThreadsM, kThreadsL, kThreadsG, kTeamMax, kTeamUnitsPerXcc, kTeamCtlWords, kTeamRedPerUnit};
+    static const SolveGeometry g = [] {
+        SolveGeometry s = {kPackedWaves, {}, kThreadsS, kThreadsM, kThreadsL, kThreadsG, kTeamMax, kTeamUnitsPerXcc, kTeamCtlWords, kTeamRedPerUnit};
+        for (int c = 0; c < KC_COUNT; ++c) s.comps_per_block[c] = c < kPackedClasses ? kPackedClass[c].G() * kPackedWaves : 1;
+        return s;
+    }();
     return g;
 }
 
@@ -3308,24 +3328,38 @@ void launch_packed(const KernelArgs &a, const PackedRanges &r, bool fused, int n
     else hipLaunchKernelGGL(solve_packed_kernel<false>, dim3(n_blocks), blk, 0, cs, a, r);
 }
 
+// the inverse of kPackedOrder: the slot of a packed class in PackedRanges, -1 for anything else
+constexpr int packed_slot(int cls) {
+    for (int i = 0; i < kPackedClasses; ++i) if (kPackedOrder[i] == cls) return i;
+    return -1;
+}
+static_assert(packed_slot(KC_G8) == kPackedClasses - 1 && packed_slot(KC_G64_4) == 0 && packed_slot(KC_BLOCK) == -1, "packed_slot");
+
+template <int KC>
+static void launch_group(const KernelArgs &a, bool fused, dim3 grid, dim3 blk, hipStream_t st) {
+    using P = PackedClass<KC>;
+    if (fused) hipLaunchKernelGGL((solve_group_kernel<P::NV, P::LPR, P::EPL, true>), grid, blk, 0, st, a);
+    else hipLaunchKernelGGL((solve_group_kernel<P::NV, P::LPR, P::EPL, false>), grid, blk, 0, st, a);
+}
+
 void launch_group_class(int cls, const KernelArgs &a, bool fused, int n_blocks, hipStream_t st) {
     const dim3 grid(n_blocks), blk(64 * kPackedWaves);
     if (a.x_start) {       // the warm form exists as solve_packed_kernel only: that launch with every block in this class's range
-        static const int kSlot[KC_BLOCK] = {4, 3, 2, 1, 0};      // PackedRanges' dispatch order: G64_4, G64_2, G32, G16, G8
-        static_assert(KC_G8 == 0 && KC_G16 == 1 && KC_G32 == 2 && KC_G64_2 == 3 && KC_G64_4 == 4, "packed classes");
+        const int slot = packed_slot(cls);
+        assert(slot >= 0);
         PackedRanges r;
-        for (int i = 0; i < 5; ++i) { r.desc_begin[i] = r.desc_end[i] = a.desc_begin; }
-        for (int i = 0; i < 6; ++i) r.blk_begin[i] = i <= kSlot[cls] ? 0 : n_blocks;
-        r.desc_begin[kSlot[cls]] = a.desc_begin; r.desc_end[kSlot[cls]] = a.desc_end;
+        for (int i = 0; i < kPackedClasses; ++i) { r.desc_begin[i] = r.desc_end[i] = a.desc_begin; }
+        for (int i = 0; i <= kPackedClasses; ++i) r.blk_begin[i] = i <= slot ? 0 : n_blocks;
+        r.desc_begin[slot] = a.desc_begin; r.desc_end[slot] = a.desc_end;
         launch_packed(a, r, false, n_blocks, st);
         return;
     }
     switch (cls) {
-        case lfr::KC_G8:    if (fused) hipLaunchKernelGGL((solve_group_kernel<8, 1, 3, true>), grid, blk, 0, st, a); else hipLaunchKernelGGL((solve_group_kernel<8, 1, 3, false>), grid, blk, 0, st, a); break;
-        case lfr::KC_G16:   if (fused) hipLaunchKernelGGL((solve_group_kernel<16, 1, 6, true>), grid, blk, 0, st, a); else hipLaunchKernelGGL((solve_group_kernel<16, 1, 6, false>), grid, blk, 0, st, a); break;
+        case lfr::KC_G8:    launch_group<KC_G8>(a, fused, grid, blk, st); break;
+        case lfr::KC_G16:   launch_group<KC_G16>(a, fused, grid, blk, st); break;
         case lfr::KC_G32:   break;     // retired class, never assigned
-        case lfr::KC_G64_2: if (fused) hipLaunchKernelGGL((solve_group_kernel<32, 1, 6, true>), grid, blk, 0, st, a); else hipLaunchKernelGGL((solve_group_kernel<32, 1, 6, false>), grid, blk, 0, st, a); break;
-        case lfr::KC_G64_4: if (fused) hipLaunchKernelGGL((solve_group_kernel<32, 2, 5, true>), grid, blk, 0, st, a); else hipLaunchKernelGGL((solve_group_kernel<32, 2, 5, false>), grid, blk, 0, st, a); break;
+        case lfr::KC_G64_2: launch_group<KC_G64_2>(a, fused, grid, blk, st); break;
+        case lfr::KC_G64_4: launch_group<KC_G64_4>(a, fused, grid, blk, st); break;
     }
 }
 
@@ -3524,7 +3558,11 @@ void debug_solve_block_kernel(int max_rows, int64_t lds_doubles, const int32_t *
 
 int lfr_debug_solve_damped(int device, int solver, int64_t n_sys, const int32_t *n_rows, const double *A, const double *damp, const double *g,
                            double *y, int32_t *status) {
-    static const int kLimit[7] = {8, 16, 24, 32, lfr::kBlockRowsS, lfr::kBlockRowsM, lfr::kBlockMaxRows};
+    // `solver` 0-3: the live packed classes in enum order (the C ABI's numbering: a class that is added or retired is edited here, in
+    // kGroups and in the switch below by hand; PackedClass refuses a retired one at compile time); 4-6: the three LDS classes.
+    // kLimit: the largest system each takes
+    using G8 = PackedClass<lfr::KC_G8>; using G16 = PackedClass<lfr::KC_G16>; using G64_2 = PackedClass<lfr::KC_G64_2>; using G64_4 = PackedClass<lfr::KC_G64_4>;
+    static const int kLimit[7] = {G8::max_rows, G16::max_rows, G64_2::max_rows, G64_4::max_rows, lfr::kBlockRowsS, lfr::kBlockRowsM, lfr::kBlockMaxRows};
     if (solver < 0 || solver > 6 || n_sys < 0 || n_sys > (1 << 24) || (n_sys > 0 && (!n_rows || !A || !damp || !g || !y || !status))) {
         lfr::set_error("bad argument"); return LFR_ERR_ARG;
     }
@@ -3559,13 +3597,13 @@ int lfr_debug_solve_damped(int device, int solver, int64_t n_sys, const int32_t 
     HIP_TRY(hipMemsetAsync(d_spins, 0, 4 * (size_t)n_sys, st));
     const int64_t *d_to = d_off, *d_vo = d_off + n_sys;
     if (!block) {
-        static const int kGroups[4] = {8, 4, 2, 1};
+        static const int kGroups[4] = {G8::G, G16::G, G64_2::G, G64_4::G};
         const dim3 grid((unsigned)((n_sys + kGroups[solver] - 1) / kGroups[solver]));
         switch (solver) {
-            case 0: hipLaunchKernelGGL((debug_solve_packed_kernel<8, 1>), grid, dim3(64), 0, st, n_sys, d_rows, d_to, d_vo, d_A, d_damp, d_g, d_y, d_status); break;
-            case 1: hipLaunchKernelGGL((debug_solve_packed_kernel<16, 1>), grid, dim3(64), 0, st, n_sys, d_rows, d_to, d_vo, d_A, d_damp, d_g, d_y, d_status); break;
-            case 2: hipLaunchKernelGGL((debug_solve_packed_kernel<32, 1>), grid, dim3(64), 0, st, n_sys, d_rows, d_to, d_vo, d_A, d_damp, d_g, d_y, d_status); break;
-            default: hipLaunchKernelGGL((debug_solve_packed_kernel<32, 2>), grid, dim3(64), 0, st, n_sys, d_rows, d_to, d_vo, d_A, d_damp, d_g, d_y, d_status); break;
+            case 0: hipLaunchKernelGGL((debug_solve_packed_kernel<G8::NV, G8::LPR>), grid, dim3(64), 0, st, n_sys, d_rows, d_to, d_vo, d_A, d_damp, d_g, d_y, d_status); break;
+            case 1: hipLaunchKernelGGL((debug_solve_packed_kernel<G16::NV, G16::LPR>), grid, dim3(64), 0, st, n_sys, d_rows, d_to, d_vo, d_A, d_damp, d_g, d_y, d_status); break;
+            case 2: hipLaunchKernelGGL((debug_solve_packed_kernel<G64_2::NV, G64_2::LPR>), grid, dim3(64), 0, st, n_sys, d_rows, d_to, d_vo, d_A, d_damp, d_g, d_y, d_status); break;
+            default: hipLaunchKernelGGL((debug_solve_packed_kernel<G64_4::NV, G64_4::LPR>), grid, dim3(64), 0, st, n_sys, d_rows, d_to, d_vo, d_A, d_damp, d_g, d_y, d_status); break;
         }
     } else {
         const int max_rows = kLimit[solver];
