@@ -2,7 +2,8 @@
 
 One object per source under csrc/_obj (rebuilt when the source or any header is newer), compiled in
 parallel, then linked: an edit of one source recompiles that file alone, and the forward kernels
-(lfr_solve.hip, the longest compile by far) only when they or a header change.
+(lfr_solve.hip, the longest compile by far) only when they or a header change.  At most MAX_JOBS
+compilers run at a time where that is set, and never more than 16.
 """
 import glob
 import os
@@ -29,6 +30,14 @@ def _flags():
     return ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC",
             "-munsafe-fp-atomics",          # hardware fp64 atomic add for the HBM-matrix kernel
             "-I", os.path.join(ROOT, "include"), "-I", CSRC] + os.environ.get("LFR_HIPCC_FLAGS", "").split()
+
+
+def _jobs():
+    try:
+        n = int(os.environ.get("MAX_JOBS", ""))
+    except ValueError:
+        n = os.cpu_count() or 1
+    return max(1, min(n, 16))
 
 
 def _header_mtime():
@@ -73,7 +82,7 @@ def build(force=False, verbose=False):
             print(" ".join(cmd), flush=True)
         subprocess.check_call(cmd)
 
-    with ThreadPoolExecutor(max_workers=max(1, min(len(stale), os.cpu_count() or 1))) as ex:
+    with ThreadPoolExecutor(max_workers=max(1, min(len(stale), _jobs()))) as ex:
         list(ex.map(compile_one, stale))
     open(tag_path, "w").write(flags_tag)
     cmd = [_hipcc(), "--offload-arch=gfx950", "-shared", "-fPIC"] + [os.path.join(OBJ, f + ".o") for f in SOURCES] + ["-o", OUT]
